@@ -60,9 +60,14 @@ def seed_of(config_id):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=100,
-                    help="untimed steps before the timed ones (default 100 = 0.3 s: the first 200-step block after 10 was 1 %% slower than the blocks behind it)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 200; C4 / C5: 5, C1: 5, --mode chain: 2, --mode baq / host-abi: 10)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before the timed ones (default 100 = 0.3 s: the first 200-step block after 10 was 1 %% slower "
+                         "than the blocks behind it; C1 / C4 / C5: 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="resident path: write what the last timed step returned to its caller (the SNV records, their filter "
+                         "verdicts and the batch's counters) as DIR/<name>.npy, float64")
     ap.add_argument("--config", choices=["C1"] + sorted(CONFIGS) + sorted(GENOME_CONFIGS), default="C3",
                     help="C3 (default, the metric) / C2: resident synthetic pileups; C4 / C5: a whole genome of reads through the "
                          "reads -> VCF chain, region- / BED-sharded over --gpus (strong scaling)")
@@ -118,8 +123,9 @@ def parse_args():
     ap.add_argument("--pageable", action="store_true",
                     help="--mode chain, one worker: the caller's read arrays in pageable memory (default: the per-base arrays "
                          "pinned, as the region binding keeps them)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed blocks of --steps steps: the first one is the reported value, all of them go into `repeats`")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed blocks of --steps steps: the first one is the reported value, all of them go into `repeats` "
+                         "(default 1: a run times exactly --steps steps)")
     ap.add_argument("--no-full-check", action="store_true",
                     help="N = 1: skip the whole-batch oracle run on all host cores (config.vcf_concordance then covers the "
                          "cpu_baseline sample only)")
@@ -1345,13 +1351,14 @@ def bench_c1(args):
     cfg = {"call_indels": False, "targets": False}
     times = []
     lines = None
-    for _ in range(max(args.warmup if args.warmup != 100 else 1, 1) + max(min(args.steps, 5), 1)):
+    n_warm = max(args.warmup if args.warmup is not None else 1, 1)
+    n_steps = max(args.steps if args.steps is not None else 5, 1)
+    for _ in range(n_warm + n_steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         lines = genome_sample_device_lines(cfg, caller, la, R, R["glen"])
         times.append(time.perf_counter() - t0)
     caller.close()
-    n_warm = max(args.warmup if args.warmup != 100 else 1, 1)
     t = float(np.mean(times[n_warm:]))
     same = lines == fx["vcf"]
     return {"metric": "pileup columns/sec, reads -> VCF, C1 shape (10.7 kb, 1 000 - 5 000x, lofreq call defaults)",
@@ -1366,18 +1373,58 @@ def bench_c1(args):
                        "reference_binary_seconds_in_the_build_container": fx.get("binary_seconds_in_the_build_container")}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+RECORD_FIELDS = ("col", "qual", "dp", "alt_raw_count", "sb", "ref_fw", "ref_rv", "alt_fw", "alt_rv", "hqa")
+
+
+def dump_outputs(out_dir, recs, keep, conf, st):
+    """--dump-outputs: what the last timed step handed its caller, one float64 array per field under out_dir.  A step that
+    returned more records than fit in DUMP_LIMIT_BYTES is written as a fixed, seeded sample of them (`records_row` says
+    which).  p-values are longdouble in the records: `records_pvalue` is their float64 rounding, `records_log_pvalue` the
+    natural log taken before rounding (it keeps p-values below the float64 range apart)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(recs)
+    per_row = 8 * (len(RECORD_FIELDS) + 6)
+    rows = np.arange(n)
+    if n * per_row > DUMP_LIMIT_BYTES - 4096:
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_LIMIT_BYTES - 4096) // per_row, replace=False))
+    r = recs[rows]
+    out = {"records_row": rows}
+    for f in RECORD_FIELDS:
+        out["records_" + f] = r[f]
+    out["records_ref"] = r["ref"].view(np.uint8)
+    out["records_alt"] = r["alt"].view(np.uint8)
+    pv = r["pvalue"]
+    out["records_pvalue"] = pv
+    with np.errstate(divide="ignore"):
+        out["records_log_pvalue"] = np.log(pv)
+    out["records_keep"] = np.asarray(keep)[rows]
+    out["batch"] = np.array([n, int(np.count_nonzero(keep)), int(st.n_tested), float(conf.bonf_subst),
+                             float(conf.num_snv_tests)])
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return sorted(out)
+
+
 def main():
     args = parse_args()
     if args.config == "C1":
         print(json.dumps(bench_c1(args)))
         return
     genome_cfg = args.config in GENOME_CONFIGS
+    if args.dump_outputs and (genome_cfg or args.mode != "resident"):
+        raise SystemExit("bench.py: --dump-outputs covers the resident path (--config C3 / C2, --mode resident)")
     if genome_cfg:
-        if args.steps == 200:                              # the defaults are C3's: a genome step takes ~0.3-0.6 s
+        if args.steps is None:                             # the defaults are C3's: a genome step takes ~0.3-0.6 s
             args.steps = 5
-        if args.warmup == 100:
+        if args.warmup is None:
             args.warmup = 1
         args.scaling = "strong"
+    steps_given = args.steps is not None
+    if args.steps is None:
+        args.steps = 200
+    if args.warmup is None:
+        args.warmup = 100
     cfg_idx, cfg_depth, cfg_cols, cfg_filter, cfg_sample = CONFIGS["C3" if genome_cfg else args.config]
     depth = args.depth or cfg_depth
     ncols = args.cols or cfg_cols
@@ -1386,12 +1433,6 @@ def main():
         # `python bench.py --gpus N` on its own: launch the N ranks (one process per GPU) the way the driver does --
         # the reference's parallel wrapper forks its own workers too (lofreq2_call_pparallel.py:590-667)
         raise SystemExit(spawn_ranks(args.gpus))
-    if genome_cfg:
-        # C4 / C5: four host threads, a context each, every context with a launch stream of its own (lfq_set_private_stream):
-        # with the three shared DP streams and the upload streams that is more streams than the runtime's default four
-        # hardware queues, and streams that share a queue wait for each other's launches (C4 286-302 ms per genome with four
-        # queues, 270-273 with eight; the shared stream: 288-297 / 292-305).  Read by the HIP runtime when it starts.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
 
@@ -1480,7 +1521,7 @@ def main():
     if args.mode in ("chain", "baq", "host-abi") and world > 1:
         raise SystemExit("bench.py: --mode %s measures one GPU; the sharded reads -> VCF runs are --config C4 / C5" % args.mode)
     if args.mode == "chain":
-        iters = max(args.steps // 100, 2)
+        iters = max(args.steps, 1) if steps_given else 2
         if args.workers > 1:
             caller.close()
             res = chain_workers(args.workers, iters)
@@ -1502,18 +1543,20 @@ def main():
         print(json.dumps(line))
         return
     if args.mode == "baq":
-        res = bench_baq(caller, la, 400000, 2000000, max(args.steps // 20, 3), want_idaq=bool(args.idaq))
+        iters = max(args.steps, 1) if steps_given else 10
+        res = bench_baq(caller, la, 400000, 2000000, iters, want_idaq=bool(args.idaq))
         line = {"metric": "reads/sec through BAQ (kpa_ext_glocal per read), resident read set", "value": res["reads_per_s"],
-                "unit": "reads/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["s_call"] * 1e3,
+                "unit": "reads/s", "n_gpus": 1, "steps": iters, "warmup": 1, "ms_per_step": res["s_call"] * 1e3,
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                 "config": {"workload": "baq: 400 K reads x 150 bp over 2 Mb", **res}}
         print(json.dumps(line))
         caller.close()
         return
     if args.mode == "host-abi":
-        res = bench_host_abi(caller, la, seed_of(2), 1000, 200000, args.plant_period, max(args.steps // 20, 3))
+        iters = max(args.steps, 1) if steps_given else 10
+        res = bench_host_abi(caller, la, seed_of(2), 1000, 200000, args.plant_period, iters)
         line = {"metric": "pileup columns/sec at depth 1000, host buffers through the C ABI", "value": res["columns_per_s"],
-                "unit": "columns/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+                "unit": "columns/s", "n_gpus": 1, "steps": iters, "warmup": 2,
                 "ms_per_step": res["ms_per_batch"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 "dtype": "f64", "data": "synthetic",
                 "config": {"workload": "host-abi: C2-shaped batches (200 k columns x 1000x) from host memory", **res}}
@@ -1852,6 +1895,10 @@ def main():
                              % (i, 1e3 * w, 1e3 * f, 1e3 * sb, 1e3 * (w + f + sb), kms))
 
     final_line = None
+    if rank == 0 and args.dump_outputs:
+        # (the keep mask is the one the step's VCF text was written with: the same records, threshold and filter)
+        dump_keep = la.filter_records(recs, la.snvqual_thresh(conf.sig, conf.bonf_subst), apply_defaults=cfg_filter)
+        dump_outputs(args.dump_outputs, recs, dump_keep, conf, st)
     if rank == 0:
         steps = max(args.steps, 1)
         ms_per_step = 1e3 * elapsed / steps

@@ -1,48 +1,22 @@
 """CPU tests of the BAQ oracle: the restated profile HMM against the reference's own
-kprobaln_ext.c object (compiled unmodified, oracle/_ref), bit for bit."""
+kprobaln_ext.c object (compiled unmodified, oracle/_ref), bit for bit: against its outputs stored in
+tests/golden/ref_parts.npz."""
 import numpy as np
 import pytest
 
-
-def _random_case(rng, lq, indel=0, n_frac=0.02):
-    """a read of length lq against a reference window; `indel` = reference minus query length"""
-    lr = lq + indel + int(rng.integers(0, 8))
-    ref = rng.integers(0, 4, lr).astype(np.uint8)
-    start = int(rng.integers(0, max(lr - lq - indel, 0) + 1))
-    if indel >= 0:
-        src = np.concatenate([ref[start:start + lq // 2], ref[start + lq // 2 + indel:start + lq + indel]])
-    else:
-        src = np.concatenate([ref[start:start + lq // 2], rng.integers(0, 4, -indel).astype(np.uint8),
-                              ref[start + lq // 2:start + lq + indel]])
-    query = src[:lq].copy()
-    if len(query) < lq:
-        query = np.concatenate([query, rng.integers(0, 4, lq - len(query)).astype(np.uint8)])
-    mism = rng.random(lq) < 0.03
-    query[mism] = (query[mism] + rng.integers(1, 4, int(mism.sum()))) % 4
-    query[rng.random(lq) < n_frac] = 4
-    ref[rng.random(lr) < n_frac / 2] = 4
-    qual = np.clip(np.round(rng.normal(32, 8, lq)), 0, 60).astype(np.uint8)
-    return ref, query, qual
+import ref_vectors as rv
 
 
 @pytest.mark.parametrize("seed", range(6))
 def test_hmm_restatement_equals_reference_object(oracle, seed):
-    if oracle.ref_parts() is None or not hasattr(oracle.ref_parts(), "kpa_ext_glocal"):
-        pytest.skip("oracle/_ref/libref_parts.so (built from /root/reference) not present")
-    rng = np.random.default_rng(seed)
+    """the restatement on the seeded reads of oracle/ref_vectors.py against what the reference's kpa_ext_glocal returned for
+    them (tests/golden/ref_parts.npz; tests/test_ref_parts.py checks the file against the live object where it is built)"""
     n = 0
-    for _ in range(60):
-        lq = int(rng.integers(1, 160))
-        indel = int(rng.choice([0, 0, 0, 1, 3, -2, 12, -9]))
-        if lq + indel < 1:
-            indel = 0
-        ref, query, qual = _random_case(rng, lq, indel)
-        bw = 7 if abs(len(ref) - lq) <= 7 else abs(len(ref) - lq) + 3
-        for d, e in ((0.00001, 0.4), (0.001, 0.1), (0.1, 0.4)):      # illumina, samtools' default, pacbio (kprobaln_ext.c:48-51)
-            a = oracle.kpa_glocal(ref, query, qual, d, e, bw, use_reference=True)
+    for ref, query, qual, bw, runs in rv.kpa_by_seed(rv.load(), seed):
+        for d, e, pr, state, q in runs:
             b = oracle.kpa_glocal(ref, query, qual, d, e, bw, use_reference=False)
-            assert a[0] == b[0]
-            assert (a[1] == b[1]).all() and (a[2] == b[2]).all()
+            assert pr == b[0]
+            assert (state == b[1]).all() and (q == b[2]).all()
             n += len(query)
     assert n > 5000
 

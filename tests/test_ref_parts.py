@@ -1,65 +1,69 @@
 """CPU tests: oracle pieces against the reference's OWN objects (fet.c, multtest.c, utils.c compiled
-unmodified into oracle/_ref/libref_parts.so by `make -C oracle ref`).  Skipped where the reference tree
-is not mounted (the GPU box)."""
+unmodified into oracle/_ref/libref_parts.so by `make -C oracle ref`).  Their outputs on the seeded cases are stored in
+tests/golden/ref_parts.npz (oracle/ref_vectors.py), so the comparisons run everywhere; where oracle/_ref is built, the
+stored outputs are checked against the live objects as well."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import ref_vectors as rv
+
 
 @pytest.fixture(scope="module")
-def ref(oracle):
-    r = oracle.ref_parts()
-    if r is None:
+def stored():
+    return rv.load()
+
+
+def test_stored_vectors_equal_live_reference(oracle, stored):
+    """tests/golden/ref_parts.npz is what the reference's objects compute on the cases of oracle/ref_vectors.py"""
+    R = oracle.ref_parts()
+    if R is None or not hasattr(R, "kpa_ext_glocal") or not hasattr(R, "binom"):
         pytest.skip("oracle/_ref not built (reference tree absent)")
-    return r
+    live = rv.compute(R)
+    assert sorted(live) == sorted(stored)
+    for k in live:
+        assert np.array_equal(live[k], stored[k]), k
 
 
-def test_fisher_exact_bitwise(oracle, ref):
-    rng = np.random.default_rng(0)
+def test_fisher_exact_bitwise(oracle, stored):
     L = oracle.lib()
-    for i in range(4000):
-        hi = 30 if i % 3 == 0 else 6000
-        a, b, c, d = [int(x) for x in rng.integers(0, hi, 4)]
+    for (a, b, c, d), want in zip(stored["fisher_in"], stored["fisher_out"]):
         o = [C.c_double() for _ in range(3)]
-        r = [C.c_double() for _ in range(3)]
-        q1 = L.orc_fisher_exact(a, b, c, d, *o)
-        q2 = ref.kt_fisher_exact(a, b, c, d, *r)
-        assert q1 == q2 and all(x.value == y.value for x, y in zip(o, r)), (a, b, c, d)
+        q1 = L.orc_fisher_exact(int(a), int(b), int(c), int(d), *o)
+        assert q1 == want[0] and all(x.value == y for x, y in zip(o, want[1:])), (a, b, c, d)
+    assert len(stored["fisher_in"]) == 4000
 
 
-def test_multtest_bitwise(oracle, ref):
-    rng = np.random.default_rng(1)
+def test_multtest_bitwise(oracle, stored):
     L = oracle.lib()
     dp = C.POINTER(C.c_double)
-    for n in (1, 2, 10, 50, 333):
-        for alpha in (0.001, 0.05, 0.25, 1.0):
-            p = np.round(rng.random(n) ** 3, 4)          # ties on purpose
-            a, b = p.copy(), p.copy()
-            L.orc_bonf_corr(a.ctypes.data_as(dp), n, 0)
-            ref.bonf_corr(b.ctypes.data_as(dp), n, 0)
-            assert np.array_equal(a, b)
-            a, b = p.copy(), p.copy()
-            L.orc_holm_bonf_corr(a.ctypes.data_as(dp), n, alpha, 0)
-            ref.holm_bonf_corr(b.ctypes.data_as(dp), n, alpha, 0)
-            assert np.array_equal(a, b)
-            for ntests in (0, 2 * n):
-                rej = (C.c_long * n)()
-                n1 = L.orc_fdr(p.ctypes.data_as(dp), n, alpha, ntests, rej)
-                ptr = C.POINTER(C.c_long)()
-                n2 = ref.fdr(p.ctypes.data_as(dp), n, alpha, ntests, C.byref(ptr))
-                assert n1 == n2
-                assert sorted(rej[i] for i in range(n1)) == sorted(ptr[i] for i in range(n2))
+    ns = stored["mt_n"]
+    ps = rv.split(stored["mt_p"], ns)
+    bonf, holm = rv.split(stored["mt_bonf"], ns), rv.split(stored["mt_holm"], ns)
+    fdr = rv.split(stored["mt_fdr_idx"], stored["mt_fdr_n"])
+    for i, (n, alpha, p) in enumerate(zip(ns, stored["mt_alpha"], ps)):
+        n = int(n)
+        a = p.copy()
+        L.orc_bonf_corr(a.ctypes.data_as(dp), n, 0)
+        assert np.array_equal(a, bonf[i])
+        a = p.copy()
+        L.orc_holm_bonf_corr(a.ctypes.data_as(dp), n, alpha, 0)
+        assert np.array_equal(a, holm[i])
+        for j, ntests in enumerate((0, 2 * n)):
+            rej = (C.c_long * n)()
+            n1 = L.orc_fdr(p.ctypes.data_as(dp), n, alpha, ntests, rej)
+            assert n1 == stored["mt_fdr_n"][2 * i + j]
+            assert sorted(rej[k] for k in range(n1)) == fdr[2 * i + j].tolist()
+    assert len(ns) == 20
 
 
-def test_int_median_and_dbl_cmp(oracle, ref):
-    rng = np.random.default_rng(2)
+def test_int_median_and_dbl_cmp(oracle, stored):
     L = oracle.lib()
-    for n in (1, 2, 3, 10, 11, 100):
-        v = rng.integers(0, 42, n).astype(np.int32)
-        p = v.ctypes.data_as(C.POINTER(C.c_int))
-        assert L.orc_int_median(p, n) == ref.int_median(p, n)
+    for v, want in zip(rv.split(stored["median_v"], stored["median_len"]), stored["median_out"]):
+        v = np.ascontiguousarray(v, np.int32)
+        assert L.orc_int_median(v.ctypes.data_as(C.POINTER(C.c_int)), len(v)) == want
     L.orc_dbl_cmp.argtypes = [C.c_void_p, C.c_void_p]
-    for x, y in [(1.0, 1.0 + 1e-16), (1.0, 1.0 + 3e-16), (0.5, 0.25), (1e-20, 2e-20)]:
+    for (x, y), want in zip(stored["dbl_cmp_in"], stored["dbl_cmp_out"]):
         a, b = C.c_double(x), C.c_double(y)
-        assert L.orc_dbl_cmp(C.byref(a), C.byref(b)) == ref.dbl_cmp(C.byref(a), C.byref(b))
+        assert L.orc_dbl_cmp(C.byref(a), C.byref(b)) == want

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import ref_vectors as rv
 
 
 @pytest.mark.parametrize("path", gu.uniq_fixtures(), ids=lambda p: p.split("/")[-1])
@@ -23,36 +24,19 @@ def _phred(p):
 
 
 def _binom_cases():
-    rng = np.random.default_rng(2024)
-    cases = [(1, 0, 0.5), (1, 1, 0.5), (10, 0, 0.0), (10, 3, 1.0), (10, 10, 0.3), (370, 0, 0.95), (10000, 100, 0.5),
-             (10000, 3108, 0.5), (10000, 3107, 0.5), (100000, 49000, 0.5), (100000, 50, 0.001), (5, -1, 0.5), (5, 6, 0.5),
-             (0, 0, 0.5), (-3, 0, 0.5), (7, 2, -0.1), (7, 2, 1.5)]
-    afs = [0.001, 0.004, 0.01, 0.02, 0.05, 0.08, 0.15, 0.3, 0.5, 0.6, 0.95, 0.999]
-    for _ in range(6000):
-        n = int(rng.choice([5, 30, 100, 400, 1500, 10000, 60000]) * rng.uniform(0.5, 1.5)) + 1
-        af = float(rng.choice(afs))
-        mode = rng.integers(0, 4)
-        if mode == 0:
-            k = int(rng.integers(0, n + 1))
-        elif mode == 1:
-            k = int(min(n, max(0, rng.normal(n * af, 3 * np.sqrt(n * af * (1 - af)) + 1))))
-        elif mode == 2:
-            k = int(rng.integers(0, max(1, int(n * af / 4)) + 1))
-        else:
-            k = int(min(n, n * af * rng.uniform(0.2, 1.2)))
-        cases.append((n, k, af))
-    return cases
+    """-> [(n, k, af, the reference's (p, status))]: the seeded cases of oracle/ref_vectors.py with binom()'s outputs on them
+    (tests/golden/ref_parts.npz; tests/test_ref_parts.py checks the file against the live object where it is built)"""
+    v = rv.load()
+    return [(int(n), int(k), float(af), (float(p), int(st)))
+            for (n, k, af), p, st in zip(v["binom_in"], v["binom_p"], v["binom_status"])]
 
 
 def test_binom_restatement_equals_reference_cdflib(oracle):
     """orc_binom_cdf (sum of the binomial probabilities in 80-bit arithmetic) against the reference's OWN binom() --
     binom.c + cdflib90 compiled unmodified into oracle/_ref -- on ~6000 seeded (n, k, af): same status, same UQ phred
     integer wherever the reference's value is a normal double, p within 1e-11 relative there."""
-    if oracle.ref_binom(10, 3, 0.5) is None:
-        pytest.skip("oracle/_ref/libref_parts.so (with binom.c + cdflib90) not present")
     worst, n_cmp = 0.0, 0
-    for n, k, af in _binom_cases():
-        rp, rs = oracle.ref_binom(n, k, af)
+    for n, k, af, (rp, rs) in _binom_cases():
         op, os_ = oracle.binom_cdf(n, k, af)
         assert (rs == 0) == (os_ == 0), (n, k, af, rs, os_)
         if rs != 0:
@@ -70,11 +54,10 @@ def test_binom_restatement_equals_reference_cdflib(oracle):
 
 def test_product_binom_equals_oracle_and_reference(oracle):
     """lfq_binom_cdf (host code of the product: tail summation from the largest term with exact ratios) against the
-    oracle on the same cases, and against the reference's cdflib where present"""
+    oracle on the same cases, and against the reference's cdflib"""
     import lofreq_amd as la
-    have_ref = oracle.ref_binom(10, 3, 0.5) is not None
     worst = 0.0
-    for n, k, af in _binom_cases():
+    for n, k, af, (rp, _) in _binom_cases():
         gp, gs = la.binom_cdf(n, k, af)
         op, os_ = oracle.binom_cdf(n, k, af)
         assert gs == os_, (n, k, af, gs, os_)
@@ -85,10 +68,8 @@ def test_product_binom_equals_oracle_and_reference(oracle):
             worst = max(worst, abs(gp - op) / op)
         else:
             assert gp < 1e-306
-        if have_ref:
-            rp, _ = oracle.ref_binom(n, k, af)
-            if rp >= 2.3e-308:
-                assert _phred(gp) == _phred(rp), (n, k, af, gp, rp)
+        if rp >= 2.3e-308:
+            assert _phred(gp) == _phred(rp), (n, k, af, gp, rp)
     assert worst < 1e-11, worst
 
 

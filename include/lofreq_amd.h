@@ -39,7 +39,8 @@ extern "C" {
  * bindings in integration/ and the Python loader do. */
 /* 4: lfq_set_batch_gate, lfq_last_baq_times; lfq_call_snvs_collect refuses h_counts for a batch whose dense entries are sparse. */
 /* 5: lfq_set_private_stream. */
-#define LFQ_ABI_VERSION 6
+/* 7: lfq_set_max_depth, lfq_readset_kept_reads. */
+#define LFQ_ABI_VERSION 7
 
 typedef enum lfq_status {
     LFQ_OK = 0,
@@ -427,6 +428,10 @@ int lfq_readset_pileup_snv(lfq_ctx *ctx, lfq_readset *rs, int64_t region_begin, 
                            lfq_tracks *tracks_out, int64_t *col_pos_out);
 int lfq_readset_pileup_indels(lfq_ctx *ctx, lfq_readset *rs, int64_t region_begin, int64_t region_end, int min_plp_idq,
                               const lfq_indel_columns **cols_out, int64_t *col_pos_out);
+/* The reads the pileups of this read set take under the context's current lfq_set_max_depth: keep_out_or_null[r] = 1 for a
+ * kept read, 0 for a dropped one; *n_kept_out_or_null = how many are kept (every read without a cap).  Decided once per read
+ * set and cap value, on the host, and shared by both pileups.  LFQ_ERR_INVALID for unsorted reads under a cap. */
+int lfq_readset_kept_reads(lfq_ctx *ctx, lfq_readset *rs, uint8_t *keep_out_or_null, int64_t *n_kept_out_or_null);
 /* copies of the resident tags for writing them back to the BAM; NULL = not wanted.  tag_flags as lfq_baq_idaq_batch */
 int lfq_readset_fetch_tags(lfq_ctx *ctx, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out,
                            uint8_t *tag_flags);
@@ -479,6 +484,18 @@ int lfq_set_pileup_nt_packed(lfq_ctx *ctx, int on);
  * read, an atomic cursor per column): the same columns and the same observations per column, but in no fixed ORDER within a
  * column, so that the last bits of a p-value can differ from run to run (QUAL and every integer output do not). */
 int lfq_set_pileup_unsorted(lfq_ctx *ctx, int on);
+/* -d / --max-depth of `lofreq call` (mplp_conf_t.max_depth, plp.c:120, set with bam_mplp_set_maxcnt, plp.c:1391-1392) for
+ * the read-level pileups of this context: lfq_readset_pileup_snv / _indels and lfq_pileup_snv_tracks / lfq_pileup_indel_columns.
+ * It is htslib's rule (bam_plp_push), not a per-column clamp.  On the reads in file order: the first read that starts at a
+ * position P is always kept; every later read at P is dropped if at least max_depth of the KEPT reads before it reach P
+ * (exclusive end >= P: a read whose last base is P - 1 still counts).  A dropped read is in no column: a position covered by
+ * dropped reads only is no column at all.  Unsorted reads with a cap are LFQ_ERR_INVALID (the rule is defined on file order).
+ * LFQ_NO_MAX_DEPTH (the default): no cap, the pileups as without this call.  Not reproduced (htslib details no caller needs):
+ * with max_depth = 0 htslib drops the very first read of contig 0 when it starts at position 0.  A negative -d keeps only the
+ * first read of each start position in htslib, which is max_depth = 0 here: callers map it, because -1 (LFQ_NO_MAX_DEPTH) means
+ * no cap and every value below it is LFQ_ERR_INVALID. */
+#define LFQ_NO_MAX_DEPTH (-1)
+int lfq_set_max_depth(lfq_ctx *ctx, int64_t max_depth);
 int lfq_pack_nt_track(const uint8_t *nt_bytes, int64_t n_obs, uint8_t *packed_out);
 
 /* lfq_call_snvs_batch in two halves, for callers that keep more than one batch in flight (one context per batch in

@@ -69,6 +69,8 @@ struct lfq_region {
     int cur;                        /* buffer being filled */
     int open;                       /* lfq_region_begin called, lfq_region_end not yet */
     int64_t wo_idaq;
+    int64_t max_depth;              /* lfq_region_set_max_depth; LFQ_NO_MAX_DEPTH by default */
+    int max_depth_set;              /* lfq_region_set_max_depth was called: close takes the cap off the context again */
     /* outputs, grown on demand */
     int64_t *col_pos_i, pos_cap;
     lfq_snv_record *srec;
@@ -135,12 +137,27 @@ int lfq_region_open(lfq_region **out, lfq_ctx *ctx, lfq_conf *conf, const lfq_re
     r->o = *opts;
     r->emit = emit;
     r->user = user;
+    r->max_depth = LFQ_NO_MAX_DEPTH;
     buf_init(&r->buf[0]);
     buf_init(&r->buf[1]);
     /* the bulk of the indel columns (the quality arrays of the reads WITHOUT an event) stays on the device */
     lfq_set_indel_arrays_on_host(ctx, 0);
     *out = r;
     return LFQ_OK;
+}
+
+int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth)
+{
+    int rc;
+    if (!r || r->open || r->buf[0].started || r->buf[1].started) {
+        return LFQ_ERR_INVALID;                 /* (a region in flight was started under the cap it had) */
+    }
+    rc = lfq_set_max_depth(r->ctx, max_depth);
+    if (rc == LFQ_OK) {
+        r->max_depth = max_depth;
+        r->max_depth_set = 1;
+    }
+    return rc;
 }
 
 int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, int64_t ref_len, int64_t beg0, int64_t end0)
@@ -281,6 +298,15 @@ static int region_start(lfq_region *r, reg_buf *b)
     }
     if (r->o.use_sq) {                                                  /* plp.c:727-735; DEFAULT_MIN_BQ = 6 */
         rc = lfq_readset_source_qual(r->ctx, b->rs, r->o.def_nm_q, 6, NULL, NULL);
+        if (rc != LFQ_OK) {
+            lfq_readset_destroy(b->rs);
+            b->rs = NULL;
+            return rc;
+        }
+    }
+    if (r->max_depth != LFQ_NO_MAX_DEPTH) {
+        /* which reads the cap keeps: decided on the host now, while this region's BAQ kernels run (both pileups share it) */
+        rc = lfq_readset_kept_reads(r->ctx, b->rs, NULL, NULL);
         if (rc != LFQ_OK) {
             lfq_readset_destroy(b->rs);
             b->rs = NULL;
@@ -477,6 +503,9 @@ int lfq_region_close(lfq_region *r, int64_t *wo_idaq)
     if (r->buf[0].rs) lfq_readset_destroy(r->buf[0].rs);
     if (r->buf[1].rs) lfq_readset_destroy(r->buf[1].rs);
     lfq_set_indel_arrays_on_host(r->ctx, 1);
+    if (r->max_depth_set) {
+        lfq_set_max_depth(r->ctx, LFQ_NO_MAX_DEPTH);
+    }
     buf_free(&r->buf[0]);
     buf_free(&r->buf[1]);
     free(r->col_pos_i);

@@ -52,6 +52,13 @@ typedef struct lfq_region lfq_region;
 /* ctx: the worker's context (lfq_create on lfq_pick_device()); conf: the caller's, advanced by every region */
 int lfq_region_open(lfq_region **out, lfq_ctx *ctx, lfq_conf *conf, const lfq_region_opts *opts,
                     lfq_region_emit_fn emit, void *user);
+/* -d / --max-depth (mplp_conf_t.max_depth): the cap of bam_mplp_set_maxcnt (plp.c:1391-1392) on the reads of every region
+ * after this call; see lfq_set_max_depth.  Call it after lfq_region_open and before the first lfq_region_begin (a region in
+ * flight keeps the cap it was started with: LFQ_ERR_INVALID).  Default: LFQ_NO_MAX_DEPTH, no cap.  It is not a field of
+ * lfq_region_opts, whose size callers rely on.  The cap is the context's (lfq_set_max_depth) while the binding is open, and
+ * lfq_region_close takes it off again (LFQ_NO_MAX_DEPTH) if this call set it.  A negative `lofreq call -d` keeps only the first
+ * read of each start position in htslib, which is max_depth = 0 here: map it, do not pass -1 through. */
+int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth);
 /* `ref`: the contig, upper-cased (plp.c:652), valid until the NEXT lfq_region_end / lfq_region_close has returned */
 int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, int64_t ref_len, int64_t beg0, int64_t end0);
 /* one BAM record that passed the flag filters of plp.c:608-632, in file order (position-sorted).  The fields are

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LFQ_AMD_LIB") or os.path.join(_HERE, "liblofreq_amd.so")   # LFQ_AMD_LIB: another build of the same library (A/B runs)
 
 LFQ_OK = 0
-LFQ_ABI_VERSION = 6      # include/lofreq_amd.h; load() refuses a library built from another header
+LFQ_ABI_VERSION = 7      # include/lofreq_amd.h; load() refuses a library built from another header
 LFQ_ERR_CAPACITY = -4
 LFQ_USE_BAQ, LFQ_USE_MQ, LFQ_USE_SQ, LFQ_USE_IDAQ = 1, 2, 4, 8
 LFQ_PV_NONE, LFQ_PV_LOG, LFQ_PV_LOG_FECLAMP, LFQ_PV_UNDERFLOW = 0, 1, 2, 3
@@ -132,6 +132,7 @@ EXPORTS = [
     "lfq_set_pileup_nt_packed", "lfq_set_pileup_unsorted", "lfq_set_baq_hmm_params", "lfq_pack_nt_track", "lfq_shard_allgather", "lfq_shard_set_host_allgather", "lfq_shard_gather_start", "lfq_shard_gather_wait", "lfq_shard_shm_open", "lfq_shard_shm_unlink", "lfq_shard_shm_close", "lfq_call_snvs_collect_pvals", "lfq_device_count", "lfq_pick_device", "lfq_host_alloc", "lfq_host_free",
     "lfq_readset_create", "lfq_readset_destroy", "lfq_readset_baq", "lfq_readset_source_qual",
     "lfq_readset_pileup_snv", "lfq_readset_pileup_indels", "lfq_readset_fetch_tags",
+    "lfq_set_max_depth", "lfq_readset_kept_reads",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
 ]
@@ -257,6 +258,8 @@ def load():
     L.lfq_readset_pileup_snv.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.POINTER(Tracks), vp]
     L.lfq_readset_pileup_indels.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.POINTER(IndelColumnsC)), vp]
     L.lfq_readset_fetch_tags.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lfq_set_max_depth.argtypes = [vp, C.c_int64]
+    L.lfq_readset_kept_reads.argtypes = [vp, vp, vp, C.POINTER(C.c_int64)]
     L.lfq_source_qual_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, C.c_int, vp, vp, vp]
     L.lfq_format_indel_record.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p,
                                           C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -389,6 +389,7 @@ int lfq_create(lfq_ctx **out, int device_ordinal)
     c->dense_strand = 1;
     c->dense_counts = 1;
     c->indel_host_arrays = 1;
+    c->plp_max_depth = LFQ_NO_MAX_DEPTH;
     c->baq_par_d = 0.00001f;            /* kpa_ext_par_lofreq_illumina (kprobaln_ext.c:50) */
     c->baq_par_e = 0.4f;
     hipDeviceProp_t prop;
@@ -469,7 +470,7 @@ void lfq_destroy(lfq_ctx *c)
         for (int i = 0; i < 5; i++) {
             if (c->d_tmp[i]) (void)hipFree(c->d_tmp[i]);
         }
-        for (int k = 0; k < 5; k++) {                   /* 4 = LFQ_RSC_PINFL: pinned host memory */
+        for (int k = 0; k < 6; k++) {                   /* 4 = LFQ_RSC_PINFL: pinned host memory */
             if (c->rs_cache[k].p) (void)(k == 4 ? hipHostFree(c->rs_cache[k].p) : hipFree(c->rs_cache[k].p));
         }
         if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
@@ -926,6 +927,15 @@ int lfq_set_pileup_unsorted(lfq_ctx *c, int on)
         return LFQ_ERR_INVALID;
     }
     c->plp_unsorted_ok = on ? 1 : 0;
+    return LFQ_OK;
+}
+
+int lfq_set_max_depth(lfq_ctx *c, int64_t max_depth)
+{
+    if (!c || max_depth < LFQ_NO_MAX_DEPTH) {
+        return LFQ_ERR_INVALID;
+    }
+    c->plp_max_depth = max_depth;
     return LFQ_OK;
 }
 

@@ -319,7 +319,7 @@ struct lfq_ctx {
     /* the allocations of the read set destroyed last (reads, tags, read ends, tag flags, pinned flags): the next
      * lfq_readset_create / _baq takes them over when they are large enough -- a worker goes from region to region, and
      * hipMalloc + hipFree of 2 GB per region are milliseconds and a device synchronisation each */
-    struct { void *p; size_t cap; } rs_cache[5];
+    struct { void *p; size_t cap; } rs_cache[6];
     int priv_stream_on;
     hipStream_t priv_stream;         /* lfq_set_private_stream: this context's own launch stream (null = the device's shared one) */
     hipStream_t up_stream;           /* lfq_readset_create's uploads and the staging copies of host tracks (created on first use) */
@@ -349,6 +349,7 @@ struct lfq_ctx {
     int plp_nt_bytes;                /* lfq_set_pileup_nt_packed(ctx, 0): the device pileup hands out one nt byte per observation */
     int plp_unsorted_ok;             /* lfq_set_pileup_unsorted(ctx, 1): reads that are not position-sorted go to the read-major kernels
                                       * instead of being refused (a column's observations then arrive in no fixed order) */
+    int64_t plp_max_depth;           /* lfq_set_max_depth: mpileup's -d cap on the reads (LFQ_NO_MAX_DEPTH = none) */
     const uint8_t *sub_ref_host;
     double sub_t0, sub_t1;
     const float *detlim_af;          /* device: per-column allele frequency while lfq_uniq_detlim_batch runs, else null */

@@ -333,6 +333,9 @@ struct LfqPileupArgs {
     const uint8_t *sq;                    /* [n] per-read source quality byte or null */
     uint8_t *t_sq;
     const int32_t *pmax_end;              /* [n] sorted reads: max over reads 0..r of the end coordinate (exclusive); null = unsorted input */
+    const int32_t *read_idx;              /* [n] -d cap (lfq_set_max_depth): read r of the pileup is input read read_idx[r]; null =
+                                           * identity.  n_reads, pos and pmax_end are then those of the kept reads, every other
+                                           * per-read field is read through read_idx */
 };
 int lfq_launch_pileup_count(const LfqPileupArgs &a, void *stream);
 int lfq_launch_pileup_columns(const LfqPileupArgs &a, int scatter, void *stream);
@@ -356,9 +359,16 @@ struct LfqPlpIndelArgs {
     int32_t *cursor[2];                   /* [width] */
     int16_t *ne_q[2], *ne_mq[2];
     const int32_t *pmax_end;              /* sorted reads: see LfqPileupArgs; selects the column-major kernel */
+    const int32_t *read_idx;              /* kept reads under a -d cap: see LfqPileupArgs */
 };
 int lfq_launch_plp_indel(const LfqPlpIndelArgs &a, int scatter, void *stream);
 int lfq_launch_plp_indel_columns(const LfqPlpIndelArgs &a, int scatter, void *stream);
+/* the kept reads of a -d cap as the pileup kernels take them (read_idx / pos / pmax_end of LfqPileupArgs): keep[r] != 0 for a
+ * kept read; kept_idx / kept_pos / kept_pmax get one entry per kept read.  scratch: lfq_keep_compact_scratch(n) bytes, whose
+ * first n int32 the caller fills with the reads' exclusive ends (computed on the host with the keep decision) */
+int64_t lfq_keep_compact_scratch(int64_t n);
+int lfq_launch_keep_compact(const uint8_t *keep, const int32_t *pos, int64_t n, void *scratch, int32_t *kept_idx,
+                            int32_t *kept_pos, int32_t *kept_pmax, void *stream);
 int lfq_launch_flag_merge(uint8_t *fl, const uint8_t *tag, int64_t n, void *stream);
 int lfq_launch_skip_columns(int32_t *nb, const uint8_t *skip, int64_t n, void *stream);
 int lfq_launch_pack_nt(const uint8_t *nt_bytes, uint8_t *nt_packed, int64_t n_obs, void *stream);

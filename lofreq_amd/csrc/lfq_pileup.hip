@@ -18,15 +18,22 @@
 #include "lfq_internal.h"
 #include "lfq_device.h"
 
+/* pileup read r -> input read: identity, or the kept-read index of a -d cap (LfqPileupArgs.read_idx) */
+__device__ __forceinline__ int64_t lfq_plp_read(const int32_t *read_idx, int64_t r)
+{
+    return read_idx ? (int64_t)read_idx[r] : r;
+}
+
 __global__ __launch_bounds__(256) void lfq_pileup_count_kernel(LfqPileupArgs A)
 {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= A.n_reads) {
         return;
     }
-    const uint32_t *cg = A.cigar + A.cigar_off[r];
-    const int n_cigar = (int)(A.cigar_off[r + 1] - A.cigar_off[r]);
-    const uint8_t *qual = A.qual + A.seq_off[r];
+    const int64_t rr = lfq_plp_read(A.read_idx, r);
+    const uint32_t *cg = A.cigar + A.cigar_off[rr];
+    const int n_cigar = (int)(A.cigar_off[rr + 1] - A.cigar_off[rr]);
+    const uint8_t *qual = A.qual + A.seq_off[rr];
     int64_t x = A.pos[r];
     int y = 0;
     for (int k = 0; k < n_cigar; ++k) {
@@ -62,11 +69,12 @@ __global__ __launch_bounds__(256) void lfq_pileup_scatter_kernel(LfqPileupArgs A
     if (r >= A.n_reads) {
         return;
     }
-    const uint32_t *cg = A.cigar + A.cigar_off[r];
-    const int n_cigar = (int)(A.cigar_off[r + 1] - A.cigar_off[r]);
-    const int64_t s0 = A.seq_off[r];
+    const int64_t rr = lfq_plp_read(A.read_idx, r);
+    const uint32_t *cg = A.cigar + A.cigar_off[rr];
+    const int n_cigar = (int)(A.cigar_off[rr + 1] - A.cigar_off[rr]);
+    const int64_t s0 = A.seq_off[rr];
     const uint8_t *seq = A.seq + s0, *qual = A.qual + s0, *lb = A.baq ? A.baq + s0 : nullptr;
-    const uint32_t strand = A.reverse[r] ? 8u : 0u, mq = A.mapq[r];
+    const uint32_t strand = A.reverse[rr] ? 8u : 0u, mq = A.mapq[rr];
     int64_t x = A.pos[r];
     int y = 0;
     for (int k = 0; k < n_cigar; ++k) {
@@ -83,7 +91,7 @@ __global__ __launch_bounds__(256) void lfq_pileup_scatter_kernel(LfqPileupArgs A
                     A.t_baq[slot] = lb ? (uint8_t)(lb[y + j] >= 33 ? lb[y + j] - 33 : 255) : (uint8_t)255;
                     A.t_mq[slot] = (uint8_t)mq;
                     if (A.t_sq) {
-                        A.t_sq[slot] = A.sq[r];                                         /* plp.c:975-977 */
+                        A.t_sq[slot] = A.sq[rr];                                         /* plp.c:975-977 */
                     }
                 }
             }
@@ -131,14 +139,15 @@ __global__ __launch_bounds__(256) void lfq_plp_indel_kernel(LfqPlpIndelArgs A)
     if (r >= A.n_reads) {
         return;
     }
-    const uint32_t *cg = A.cigar + A.cigar_off[r];
-    const int n_cigar = (int)(A.cigar_off[r + 1] - A.cigar_off[r]);
-    const int64_t s0 = A.seq_off[r];
-    const int l_qseq = (int)(A.seq_off[r + 1] - s0);
-    const uint32_t fl = A.tag_flags ? A.tag_flags[r] : 3u;
+    const int64_t rr = lfq_plp_read(A.read_idx, r);
+    const uint32_t *cg = A.cigar + A.cigar_off[rr];
+    const int n_cigar = (int)(A.cigar_off[rr + 1] - A.cigar_off[rr]);
+    const int64_t s0 = A.seq_off[rr];
+    const int l_qseq = (int)(A.seq_off[rr + 1] - s0);
+    const uint32_t fl = A.tag_flags ? A.tag_flags[rr] : 3u;
     const uint8_t *bi = (A.bi && (fl & 1u)) ? A.bi + s0 : nullptr, *bd = (A.bd && (fl & 2u)) ? A.bd + s0 : nullptr;
-    const int rev = A.reverse[r] ? 1 : 0;
-    const int16_t mq = (int16_t)A.mapq[r];
+    const int rev = A.reverse[rr] ? 1 : 0;
+    const int16_t mq = (int16_t)A.mapq[rr];
     int64_t end = A.pos[r];                                 /* bam_endpos - 1: is_tail */
     for (int k = 0; k < n_cigar; ++k) {
         const int op = cg[k] & 0xf;
@@ -342,14 +351,16 @@ __global__ __launch_bounds__(256) void lfq_pileup_columns_kernel(LfqPileupArgs A
     for (int64_t r0 = lo; r0 < hi; r0 += 64) {
         const int64_t r = r0 + lane;
         int kind = 0, qpos = 0;
+        int64_t rr = 0;
         if (r < hi) {
-            const int64_t co = A.cigar_off[r];
-            kind = lfq_plp_locate(A.cigar + co, (int)(A.cigar_off[r + 1] - co), A.pos[r], p, &qpos);
+            rr = lfq_plp_read(A.read_idx, r);
+            const int64_t co = A.cigar_off[rr];
+            kind = lfq_plp_locate(A.cigar + co, (int)(A.cigar_off[rr + 1] - co), A.pos[r], p, &qpos);
         }
         int bq = 0;
         int64_t s0 = 0;
         if (kind == 1) {
-            s0 = A.seq_off[r];
+            s0 = A.seq_off[rr];
             bq = A.qual[s0 + qpos];
         }
         const bool kept = kind == 1 && bq >= A.min_plp_bq;
@@ -361,13 +372,13 @@ __global__ __launch_bounds__(256) void lfq_pileup_columns_kernel(LfqPileupArgs A
             if (kept) {
                 const uint64_t slot = base + n_kept + (uint64_t)__popcll(mk & ((1ull << lane) - 1ull));
                 const uint32_t code = A.seq[s0 + qpos];
-                A.t_nt[slot] = (uint8_t)((code > 4 ? 4u : code) | (A.reverse[r] ? 8u : 0u));
+                A.t_nt[slot] = (uint8_t)((code > 4 ? 4u : code) | (A.reverse[rr] ? 8u : 0u));
                 A.t_bq[slot] = (uint8_t)(bq > 93 ? 93 : bq);                                   /* plp.c:948-952 */
                 const uint32_t lb = A.baq ? A.baq[s0 + qpos] : 0u;
                 A.t_baq[slot] = A.baq ? (uint8_t)(lb >= 33 ? lb - 33 : 255) : (uint8_t)255;
-                A.t_mq[slot] = A.mapq[r];
+                A.t_mq[slot] = A.mapq[rr];
                 if (A.t_sq) {
-                    A.t_sq[slot] = A.sq[r];
+                    A.t_sq[slot] = A.sq[rr];
                 }
             }
             n_kept += (uint32_t)__popcll(mk);
@@ -559,8 +570,9 @@ __global__ __launch_bounds__(256) void lfq_pileup_tiles_kernel(LfqPileupArgs A)
             R.off0 = R.off1 = 0;
             R.split = 64;
             if (r < hi) {
-                const int64_t co = A.cigar_off[r], s0 = A.seq_off[r];
-                const int nc = (int)(A.cigar_off[r + 1] - co);
+                const int64_t rr = lfq_plp_read(A.read_idx, r);
+                const int64_t co = A.cigar_off[rr], s0 = A.seq_off[rr];
+                const int nc = (int)(A.cigar_off[rr + 1] - co);
                 const uint32_t *cg = A.cigar + co;
                 R = lfq_tile_resolve(cg, nc, A.pos[r], s0, p0, tile);
                 if (R.nw > 0) {
@@ -592,9 +604,9 @@ __global__ __launch_bounds__(256) void lfq_pileup_tiles_kernel(LfqPileupArgs A)
                     }
                 }
                 if (SCATTER && first && R.cm) {
-                    s_mq[rt] = A.mapq[r];
-                    s_rev[rt] = A.reverse[r] ? 8 : 0;
-                    s_sq[rt] = A.sq ? A.sq[r] : 0;
+                    s_mq[rt] = A.mapq[rr];
+                    s_rev[rt] = A.reverse[rr] ? 8 : 0;
+                    s_sq[rt] = A.sq ? A.sq[rr] : 0;
                 }
             }
             if (first) {
@@ -766,15 +778,16 @@ __global__ __launch_bounds__(256) void lfq_plp_indel_columns_kernel(LfqPlpIndelA
         bool tail = false;
         int16_t mq = 0;
         if (r < hi) {
-            const int64_t co = A.cigar_off[r], s0 = A.seq_off[r];
-            const int l_qseq = (int)(A.seq_off[r + 1] - s0);
-            kind = lfq_plp_locate_indel(A.cigar + co, (int)(A.cigar_off[r + 1] - co), A.pos[r], p, l_qseq, &qpos, &indel, &tail);
+            const int64_t rr = lfq_plp_read(A.read_idx, r);
+            const int64_t co = A.cigar_off[rr], s0 = A.seq_off[rr];
+            const int l_qseq = (int)(A.seq_off[rr + 1] - s0);
+            kind = lfq_plp_locate_indel(A.cigar + co, (int)(A.cigar_off[rr + 1] - co), A.pos[r], p, l_qseq, &qpos, &indel, &tail);
             if (kind) {
-                const uint32_t fl = A.tag_flags ? A.tag_flags[r] : 3u;
+                const uint32_t fl = A.tag_flags ? A.tag_flags[rr] : 3u;
                 iq = (A.bi && (fl & 1u) && qpos >= 0) ? (int)A.bi[s0 + qpos] - 33 : 0;           /* plp.c:1023-1059 */
                 dq = (A.bd && (fl & 2u) && qpos >= 0) ? (int)A.bd[s0 + qpos] - 33 : 0;
-                rev = A.reverse[r] ? 1 : 0;
-                mq = (int16_t)A.mapq[r];
+                rev = A.reverse[rr] ? 1 : 0;
+                mq = (int16_t)A.mapq[rr];
             }
         }
         const bool pass = kind != 0 && !(iq < A.min_plp_idq || dq < A.min_plp_idq);              /* :1062 */
@@ -998,10 +1011,11 @@ __global__ __launch_bounds__(256) void lfq_plp_indel_tiles_kernel(LfqPlpIndelArg
             R.slow = false;
             uint32_t fl = 0;
             if (r < hi) {
-                const int64_t co = A.cigar_off[r], s0 = A.seq_off[r];
-                R = lfq_tile_resolve_indel(A.cigar + co, (int)(A.cigar_off[r + 1] - co), A.pos[r], s0, p0, tile);
-                const uint32_t tf = A.tag_flags ? A.tag_flags[r] : 3u;
-                fl = ((A.bi && (tf & 1u)) ? 1u : 0u) | ((A.bd && (tf & 2u)) ? 2u : 0u) | (A.reverse[r] ? 4u : 0u) | (R.slow ? 8u : 0u);
+                const int64_t rr = lfq_plp_read(A.read_idx, r);
+                const int64_t co = A.cigar_off[rr], s0 = A.seq_off[rr];
+                R = lfq_tile_resolve_indel(A.cigar + co, (int)(A.cigar_off[rr + 1] - co), A.pos[r], s0, p0, tile);
+                const uint32_t tf = A.tag_flags ? A.tag_flags[rr] : 3u;
+                fl = ((A.bi && (tf & 1u)) ? 1u : 0u) | ((A.bd && (tf & 2u)) ? 2u : 0u) | (A.reverse[rr] ? 4u : 0u) | (R.slow ? 8u : 0u);
                 if (R.nw > 0) {
                     if (first && (fl & 1u)) {
                         lfq_tile_fetch(&s_row[0][rt][0], A.bi, R.a0, R.nw);
@@ -1064,11 +1078,11 @@ __global__ __launch_bounds__(256) void lfq_plp_indel_tiles_kernel(LfqPlpIndelArg
                             : (dp == (int)((evdp[sc] >> 16) & 255u)) ? evv2[sc] : 0;
                 } else if (any) {
                     /* resolved per position, as the column-major kernel does */
-                    const int64_t r = r0 + t, co = A.cigar_off[r], s0 = A.seq_off[r];
+                    const int64_t r = r0 + t, rr = lfq_plp_read(A.read_idx, r), co = A.cigar_off[rr], s0 = A.seq_off[rr];
                     int qpos = 0;
                     bool tl = false;
-                    const int kind = lfq_plp_locate_indel(A.cigar + co, (int)(A.cigar_off[r + 1] - co), A.pos[r], p0 + dp,
-                                                          (int)(A.seq_off[r + 1] - s0), &qpos, &indel, &tl);
+                    const int kind = lfq_plp_locate_indel(A.cigar + co, (int)(A.cigar_off[rr + 1] - co), A.pos[r], p0 + dp,
+                                                          (int)(A.seq_off[rr + 1] - s0), &qpos, &indel, &tl);
                     covered = kind == 1;
                     any = kind != 0;
                     is_tail = covered && tl;
@@ -1438,5 +1452,150 @@ int lfq_launch_plp_compact_apply(const int32_t *cov, const int32_t *nb, int64_t 
     hipLaunchKernelGGL(lfq_plp_compact_apply_kernel, dim3((unsigned)ntiles), dim3(LFQ_PC_THREADS), 0, (hipStream_t)stream, cov, nb,
                        width, begin, ref, ref_len, tile_cols, (const unsigned long long *)tile_obs, totals, col_index, col_off,
                        ref_base, cov_c, nb_c, col_pos);
+    return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
+}
+
+
+/* ------------------------------------------------------------------------------------------ */
+/* kept reads of a -d cap (lfq_set_max_depth), on the device                                   */
+/* ------------------------------------------------------------------------------------------ */
+/* The host decides which reads the cap keeps (lfq_readset.hip: the rule runs over start positions in file order and is
+ * sequential); what the pileup kernels need from it is a compacted read list -- the input index, the start and the running
+ * maximum of the exclusive ends over the KEPT reads only, so that their window searches and their work scale with the kept
+ * reads.  A scan and a scatter of the mask in three small kernels, the pattern of the column compaction above: per tile of
+ * 4096 reads its kept count and the largest end of its kept reads, one block scans the tile values, then every tile writes its
+ * kept reads.  The ends come from the host, which computed them for the decision. */
+#define LFQ_KC_THREADS 256
+#define LFQ_KC_ITEMS 16
+#define LFQ_KC_TILE (LFQ_KC_THREADS * LFQ_KC_ITEMS)
+
+static inline int64_t lfq_kc_al(int64_t b) { return (b + 255) / 256 * 256; }
+
+int64_t lfq_keep_compact_scratch(int64_t n)
+{
+    const int64_t ntiles = (n + LFQ_KC_TILE - 1) / LFQ_KC_TILE;
+    return lfq_kc_al(n * 4) + lfq_kc_al(ntiles * 4) + lfq_kc_al(ntiles * 4);
+}
+
+/* inclusive scan of (count, max) over the threads of the block */
+__device__ __forceinline__ void lfq_kc_block_scan(int32_t &n, int32_t &m, int32_t *s_n, int32_t *s_m)
+{
+    const int t = (int)threadIdx.x;
+    s_n[t] = n;
+    s_m[t] = m;
+    __syncthreads();
+    for (int d = 1; d < LFQ_KC_THREADS; d <<= 1) {
+        const int32_t pn = t >= d ? s_n[t - d] : 0;
+        const int32_t pm = t >= d ? s_m[t - d] : INT32_MIN;
+        __syncthreads();
+        s_n[t] += pn;
+        s_m[t] = max(s_m[t], pm);
+        __syncthreads();
+    }
+    n = s_n[t];
+    m = s_m[t];
+}
+
+__global__ __launch_bounds__(LFQ_KC_THREADS) void lfq_keep_tiles_kernel(const uint8_t *__restrict__ keep,
+                                                                       const int32_t *__restrict__ ends, int64_t n,
+                                                                       int32_t *__restrict__ tile_n, int32_t *__restrict__ tile_m)
+{
+    __shared__ int32_t s_n[LFQ_KC_THREADS], s_m[LFQ_KC_THREADS];
+    const int64_t r0 = (int64_t)blockIdx.x * LFQ_KC_TILE + (int64_t)threadIdx.x * LFQ_KC_ITEMS;
+    int32_t cnt = 0, mx = INT32_MIN;
+    for (int i = 0; i < LFQ_KC_ITEMS; i++) {
+        const int64_t r = r0 + i;
+        if (r >= n) {
+            break;
+        }
+        if (keep[r]) {
+            cnt++;
+            mx = max(mx, ends[r]);
+        }
+    }
+    lfq_kc_block_scan(cnt, mx, s_n, s_m);
+    if (threadIdx.x == LFQ_KC_THREADS - 1) {
+        tile_n[blockIdx.x] = cnt;
+        tile_m[blockIdx.x] = mx;
+    }
+}
+
+/* one block: tile_n -> exclusive scan, tile_m -> exclusive running maximum (INT32_MIN before the first tile), in place */
+__global__ __launch_bounds__(LFQ_KC_THREADS) void lfq_keep_sums_kernel(int64_t ntiles, int32_t *__restrict__ tile_n,
+                                                                      int32_t *__restrict__ tile_m)
+{
+    __shared__ int32_t s_n[LFQ_KC_THREADS], s_m[LFQ_KC_THREADS];
+    int32_t base_n = 0, base_m = INT32_MIN;
+    for (int64_t t0 = 0; t0 < ntiles; t0 += LFQ_KC_THREADS) {
+        const int64_t t = t0 + threadIdx.x;
+        const int32_t n_in = t < ntiles ? tile_n[t] : 0;
+        const int32_t m_in = t < ntiles ? tile_m[t] : INT32_MIN;
+        int32_t cn = n_in, cm = m_in;
+        lfq_kc_block_scan(cn, cm, s_n, s_m);
+        /* exclusive maximum: the inclusive one of the thread before, or the running value for thread 0 */
+        const int32_t prev_m = threadIdx.x > 0 ? s_m[threadIdx.x - 1] : INT32_MIN;
+        if (t < ntiles) {
+            tile_n[t] = base_n + cn - n_in;
+            tile_m[t] = max(base_m, prev_m);
+        }
+        base_n += s_n[LFQ_KC_THREADS - 1];
+        base_m = max(base_m, s_m[LFQ_KC_THREADS - 1]);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(LFQ_KC_THREADS) void lfq_keep_apply_kernel(const uint8_t *__restrict__ keep,
+                                                                       const int32_t *__restrict__ pos, int64_t n,
+                                                                       const int32_t *__restrict__ ends,
+                                                                       const int32_t *__restrict__ tile_n,
+                                                                       const int32_t *__restrict__ tile_m,
+                                                                       int32_t *__restrict__ kept_idx, int32_t *__restrict__ kept_pos,
+                                                                       int32_t *__restrict__ kept_pmax)
+{
+    __shared__ int32_t s_n[LFQ_KC_THREADS], s_m[LFQ_KC_THREADS];
+    const int64_t r0 = (int64_t)blockIdx.x * LFQ_KC_TILE + (int64_t)threadIdx.x * LFQ_KC_ITEMS;
+    int32_t cnt = 0, mx = INT32_MIN;
+    for (int i = 0; i < LFQ_KC_ITEMS; i++) {
+        const int64_t r = r0 + i;
+        if (r < n && keep[r]) {
+            cnt++;
+            mx = max(mx, ends[r]);
+        }
+    }
+    const int32_t cnt_own = cnt;
+    lfq_kc_block_scan(cnt, mx, s_n, s_m);
+    int64_t k = (int64_t)tile_n[blockIdx.x] + (cnt - cnt_own);
+    int32_t run = max(tile_m[blockIdx.x], threadIdx.x > 0 ? s_m[threadIdx.x - 1] : INT32_MIN);
+    for (int i = 0; i < LFQ_KC_ITEMS; i++) {
+        const int64_t r = r0 + i;
+        if (r >= n) {
+            break;
+        }
+        if (keep[r]) {
+            run = max(run, ends[r]);
+            kept_idx[k] = (int32_t)r;
+            kept_pos[k] = pos[r];
+            kept_pmax[k] = run;
+            k++;
+        }
+    }
+}
+
+int lfq_launch_keep_compact(const uint8_t *keep, const int32_t *pos, int64_t n, void *scratch, int32_t *kept_idx,
+                            int32_t *kept_pos, int32_t *kept_pmax, void *stream)
+{
+    if (n <= 0) {
+        return LFQ_OK;
+    }
+    const int64_t ntiles = (n + LFQ_KC_TILE - 1) / LFQ_KC_TILE;
+    uint8_t *sc = (uint8_t *)scratch;
+    const int32_t *ends = (const int32_t *)sc;
+    int32_t *tile_n = (int32_t *)(sc + lfq_kc_al(n * 4));
+    int32_t *tile_m = (int32_t *)(sc + lfq_kc_al(n * 4) + lfq_kc_al(ntiles * 4));
+    hipLaunchKernelGGL(lfq_keep_tiles_kernel, dim3((unsigned)ntiles), dim3(LFQ_KC_THREADS), 0, (hipStream_t)stream, keep, ends, n,
+                       tile_n, tile_m);
+    hipLaunchKernelGGL(lfq_keep_sums_kernel, dim3(1), dim3(LFQ_KC_THREADS), 0, (hipStream_t)stream, ntiles, tile_n, tile_m);
+    hipLaunchKernelGGL(lfq_keep_apply_kernel, dim3((unsigned)ntiles), dim3(LFQ_KC_THREADS), 0, (hipStream_t)stream, keep, pos, n,
+                       ends, tile_n, tile_m, kept_idx, kept_pos, kept_pmax);
     return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
 }

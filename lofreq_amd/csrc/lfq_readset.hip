@@ -4,6 +4,8 @@
  */
 #include "lfq_ctx.h"
 
+#include <queue>
+
 extern "C" {
 
 /* ---- resident read set ------------------------------------------------------------------------------------
@@ -11,7 +13,7 @@ extern "C" {
  * copy and leave their per-base results (lb, ai, ad, sq) there for the next stage.  The host arrays handed to
  * lfq_readset_create stay the caller's and must outlive the read set: the sparse host-side steps (geometry from the
  * CIGARs, the indel event tables) read them in place. */
-enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4 };
+enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5 };
 
 static void rs_cache_free(int kind, void *p)
 {
@@ -62,7 +64,7 @@ static void rs_cache_give(lfq_ctx *c, int kind, void *p, size_t cap)
 #define LFQ_UP_CHUNKS 6
 struct lfq_readset {
     lfq_ctx *c;
-    size_t cap[5];                      /* capacities of blob, tag_blob, d_pmax, d_tagfl, h_fl_pin (rs_cache_*) */
+    size_t cap[6];                      /* capacities of blob, tag_blob, d_pmax, d_tagfl, h_fl_pin, d_keep (rs_cache_*) */
     int64_t n, n_bases, n_cig, ref_len;
     const int32_t *pos;
     const int64_t *cigar_off, *seq_off;
@@ -84,6 +86,17 @@ struct lfq_readset {
     bool baq_pending, baq_idaq;
     int32_t *d_pmax;                    /* position-sorted reads: running maximum of the end coordinates (lazily) */
     int pmax_state;                     /* 0 unknown, 1 sorted (d_pmax valid), 2 unsorted */
+    /* -d cap (lfq_set_max_depth): the reads both pileups take, decided once per cap value (readset_keep) */
+    bool keep_valid;                    /* a decision for the cap keep_for has been made; keep_rc is its result */
+    int64_t keep_for;
+    int keep_rc;                        /* LFQ_OK, or LFQ_ERR_INVALID for reads that are not position-sorted */
+    int64_t n_kept;
+    std::vector<uint8_t> keep;          /* [n] 1 = kept; empty when the cap drops nothing (the pileups then run as without it) */
+    std::vector<int32_t> keep_end;      /* [n] exclusive end of every read (with a mask: what the compaction kernels take) */
+    uint8_t *d_keep;                    /* device: the mask, the kept reads' read_idx / pos / pmax_end, compaction scratch */
+    bool keep_dev_valid;                /* d_keep holds the kept reads of the decision for keep_dev_for */
+    int64_t keep_dev_for;
+    hipEvent_t ev_keep;                 /* the compaction kernels are done (the two pileups may run on different streams) */
     /* lfq_readset_create returns while the reads are still crossing PCIe (a helper thread feeds the copies of the caller's
      * pageable arrays to the upload stream): host-only work of the next step -- the BAQ geometry -- runs meanwhile, and
      * every step calls readset_upload_wait before its first device operation on the read set */
@@ -213,6 +226,8 @@ void lfq_readset_destroy(lfq_readset *rs)
         rs_cache_give(rs->c, LFQ_RSC_BLOB, rs->blob, rs->cap[LFQ_RSC_BLOB]);
         rs_cache_give(rs->c, LFQ_RSC_TAGS, rs->tag_blob, rs->cap[LFQ_RSC_TAGS]);
         rs_cache_give(rs->c, LFQ_RSC_PMAX, rs->d_pmax, rs->cap[LFQ_RSC_PMAX]);
+        rs_cache_give(rs->c, LFQ_RSC_KEEP, rs->d_keep, rs->cap[LFQ_RSC_KEEP]);
+        if (rs->ev_keep) (void)hipEventDestroy(rs->ev_keep);
         delete rs;
     }
 }
@@ -244,6 +259,9 @@ int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_
     rs->h_fl_pin = nullptr;
     memset(rs->cap, 0, sizeof(rs->cap));
     rs->pmax_state = 0;
+    rs->keep_valid = rs->keep_dev_valid = false;
+    rs->d_keep = nullptr;
+    rs->ev_keep = nullptr;
     rs->up_thread = nullptr;
     rs->up_stage.store(0);
     rs->up_chunks.store(0);
@@ -511,6 +529,200 @@ static const int32_t *readset_pmax(lfq_ctx *c, lfq_readset *rs, hipStream_t st)
 static bool readset_unsorted_ok(const lfq_ctx *c, const lfq_readset *rs)
 {
     return rs->n == 0 || c->plp_unsorted_ok || lfq_knobs().pileup_atomic;
+}
+
+/* ---- -d / --max-depth (lfq_set_max_depth) --------------------------------------------------------------------
+ * htslib's bam_plp_push does not push a read that starts at the iterator's current position while its node pool holds more
+ * than maxcnt reads (bam_mplp_set_maxcnt, plp.c:1391-1392).  On the reads in file order: the first read at a start position P
+ * is always kept, every later one is dropped when at least max_depth KEPT reads before it have an exclusive end >= P.  A
+ * recurrence over the start positions, sequential by nature -- so the host decides, once per read set and cap value, and the
+ * device gets a compacted read list (lfq_launch_keep_compact).
+ *   1. ends and the running maximum of the ends, split over the lfq_for_reads threads (as readset_pmax);
+ *   2. the proof, over the runs of equal start in parallel: if every read were kept, at most (end of the run) - (first read
+ *      whose running maximum reaches P) reads would count at the last read of a run at P.  Within the cap at every run:
+ *      nothing is dropped, no mask, the pileups run exactly as without a cap;
+ *   3. otherwise one walk over the reads with a min-heap of the kept reads' ends (reads * log depth). */
+static int readset_keep(lfq_ctx *c, lfq_readset *rs)
+{
+    const int64_t md = c->plp_max_depth;
+    if (md == LFQ_NO_MAX_DEPTH) {
+        return LFQ_OK;
+    }
+    if (rs->keep_valid && rs->keep_for == md) {
+        return rs->keep_rc;
+    }
+    if (rs->keep_dev_valid) {
+        /* the cap changed between the pileups of this read set: the kernels of the earlier pileup may still read the kept-read
+         * list (and the copies its mask and ends came from), on either of the two streams the pileups use -- both drain before
+         * any of it is rewritten */
+        LFQ_TRY_HIP(hipStreamSynchronize(c->stream));
+        if (c->dps) LFQ_TRY_HIP(hipStreamSynchronize(c->dps));
+        rs->keep_dev_valid = false;
+    }
+    rs->keep_valid = true;
+    rs->keep_for = md;
+    rs->keep_rc = LFQ_OK;
+    rs->keep.clear();
+    rs->keep_end.clear();
+    const int64_t n = rs->n;
+    rs->n_kept = n;
+    if (n == 0) {
+        return LFQ_OK;
+    }
+    std::vector<int32_t> end((size_t)n), pmax((size_t)n);
+    int32_t part_max[LFQ_HOST_PARTS];
+    bool part_sorted[LFQ_HOST_PARTS];
+    int parts = 1;
+    lfq_for_reads(n, [&](int64_t r0, int64_t r1, int part) {
+        int32_t run = INT32_MIN;
+        bool sorted = true;
+        for (int64_t r = r0; r < r1; r++) {
+            const uint32_t *cg = rs->cigar + rs->cigar_off[r];
+            const int nc = (int)(rs->cigar_off[r + 1] - rs->cigar_off[r]);
+            int64_t e = rs->pos[r];
+            for (int k = 0; k < nc; k++) {
+                const int op = cg[k] & 0xf;
+                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) {
+                    e += cg[k] >> 4;
+                }
+            }
+            end[(size_t)r] = (int32_t)std::min<int64_t>(e, INT32_MAX);
+            run = std::max(run, end[(size_t)r]);
+            pmax[(size_t)r] = run;
+            sorted = sorted && (r == 0 || rs->pos[r] >= rs->pos[r - 1]);
+        }
+        part_max[part] = run;
+        part_sorted[part] = sorted;
+    }, &parts);
+    for (int q = 0; q < parts; q++) {
+        if (!part_sorted[q]) {
+            rs->keep_rc = LFQ_ERR_INVALID;          /* the rule is defined on file order; bam_mplp_auto refuses such files */
+            return rs->keep_rc;
+        }
+    }
+    if (parts > 1) {
+        int32_t before[LFQ_HOST_PARTS];
+        before[0] = INT32_MIN;
+        for (int q = 1; q < parts; q++) {
+            before[q] = std::max(before[q - 1], part_max[q - 1]);
+        }
+        lfq_for_reads(n, [&](int64_t r0, int64_t r1, int part) {
+            for (int64_t r = r0; r < r1 && pmax[(size_t)r] < before[part]; r++) {
+                pmax[(size_t)r] = before[part];
+            }
+        });
+    }
+    /* 2. the proof: reads before the first one whose running maximum reaches P end before P */
+    std::atomic<bool> drops{false};
+    lfq_for_reads(n, [&](int64_t r0, int64_t r1, int) {
+        for (int64_t r = r0; r < r1 && !drops.load(std::memory_order_relaxed); r++) {
+            if (r > 0 && rs->pos[r] == rs->pos[r - 1]) {
+                continue;                           /* not the first read of its run */
+            }
+            const int32_t P = rs->pos[r];
+            int64_t r_end = r + 1;
+            while (r_end < n && rs->pos[r_end] == P) {
+                r_end++;
+            }
+            const int64_t lo = std::lower_bound(pmax.begin(), pmax.begin() + r, P) - pmax.begin();
+            if (r_end - lo > md) {
+                drops.store(true, std::memory_order_relaxed);
+            }
+        }
+    });
+    if (!drops.load()) {
+        return LFQ_OK;
+    }
+    /* 3. the walk */
+    rs->keep.assign((size_t)n, 0);
+    std::priority_queue<int32_t, std::vector<int32_t>, std::greater<int32_t>> live;   /* ends of the kept reads still counted */
+    int64_t kept = 0;
+    for (int64_t r = 0; r < n; r++) {
+        const int32_t P = rs->pos[r];
+        const bool first = r == 0 || P != rs->pos[r - 1];
+        if (first) {
+            while (!live.empty() && live.top() < P) {
+                live.pop();
+            }
+        }
+        if (first || (int64_t)live.size() < md) {
+            rs->keep[(size_t)r] = 1;
+            live.push(end[(size_t)r]);
+            kept++;
+        }
+    }
+    rs->n_kept = kept;
+    if (kept == n) {
+        rs->keep.clear();                           /* (the bound of step 2 is not tight: nothing dropped after all) */
+    } else {
+        rs->keep_end.swap(end);                     /* the ends go to the device with the mask: one rule for them, here */
+    }
+    return LFQ_OK;
+}
+
+/* the kept reads on the device for the pileup kernels: the mask up, the compaction kernels on `st`, an event behind them for
+ * the other pileup's stream.  -> *kept_idx (null: every read is kept, the kernels run as without a cap) */
+static int readset_keep_device(lfq_ctx *c, lfq_readset *rs, hipStream_t st, const int32_t **kept_idx, const int32_t **kept_pos,
+                               const int32_t **kept_pmax)
+{
+    *kept_idx = *kept_pos = *kept_pmax = nullptr;
+    LFQ_TRY(readset_keep(c, rs));
+    if (c->plp_max_depth == LFQ_NO_MAX_DEPTH || rs->keep.empty()) {
+        return LFQ_OK;
+    }
+    const int64_t n = rs->n;
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t o_idx = al(n), o_pos = o_idx + al(n * 4), o_pmax = o_pos + al(n * 4), o_scr = o_pmax + al(n * 4),
+                  total = o_scr + lfq_keep_compact_scratch(n);
+    if (!rs->keep_dev_valid || rs->keep_dev_for != c->plp_max_depth) {
+        if (!rs->d_keep || rs->cap[LFQ_RSC_KEEP] < (size_t)total) {
+            if (rs->d_keep) {
+                rs_cache_give(c, LFQ_RSC_KEEP, rs->d_keep, rs->cap[LFQ_RSC_KEEP]);
+                rs->d_keep = nullptr;
+            }
+            rs->d_keep = (uint8_t *)rs_cache_take(c, LFQ_RSC_KEEP, (size_t)total, &rs->cap[LFQ_RSC_KEEP]);
+            if (!rs->d_keep) {
+                return LFQ_ERR_NOMEM;
+            }
+        }
+        if (!rs->ev_keep) {
+            LFQ_TRY_HIP(hipEventCreateWithFlags(&rs->ev_keep, hipEventDisableTiming));
+        }
+        uint8_t *d = rs->d_keep;
+        LFQ_TRY_HIP(hipMemcpyAsync(d, rs->keep.data(), (size_t)n, hipMemcpyHostToDevice, st));
+        LFQ_TRY_HIP(hipMemcpyAsync(d + o_scr, rs->keep_end.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));   /* ends: scratch head */
+        LFQ_TRY(lfq_launch_keep_compact(d, (const int32_t *)rs->d_pos, n, d + o_scr, (int32_t *)(d + o_idx), (int32_t *)(d + o_pos),
+                                        (int32_t *)(d + o_pmax), st));
+        LFQ_TRY_HIP(hipEventRecord(rs->ev_keep, st));
+        rs->keep_dev_valid = true;
+        rs->keep_dev_for = c->plp_max_depth;
+    } else {
+        LFQ_TRY_HIP(hipStreamWaitEvent(st, rs->ev_keep, 0));
+    }
+    *kept_idx = (const int32_t *)(rs->d_keep + o_idx);
+    *kept_pos = (const int32_t *)(rs->d_keep + o_pos);
+    *kept_pmax = (const int32_t *)(rs->d_keep + o_pmax);
+    return LFQ_OK;
+}
+
+int lfq_readset_kept_reads(lfq_ctx *c, lfq_readset *rs, uint8_t *keep_out, int64_t *n_kept_out)
+{
+    if (!c || !rs || rs->c != c) {
+        return LFQ_ERR_INVALID;
+    }
+    LFQ_TRY(readset_keep(c, rs));
+    const bool capped = c->plp_max_depth != LFQ_NO_MAX_DEPTH;
+    if (keep_out && rs->n > 0) {
+        if (capped && !rs->keep.empty()) {
+            memcpy(keep_out, rs->keep.data(), (size_t)rs->n);
+        } else {
+            memset(keep_out, 1, (size_t)rs->n);
+        }
+    }
+    if (n_kept_out) {
+        *n_kept_out = capped ? rs->n_kept : rs->n;
+    }
+    return LFQ_OK;
 }
 
 int lfq_readset_fetch_tags(lfq_ctx *c, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out, uint8_t *tag_flags)
@@ -1116,6 +1328,17 @@ int lfq_readset_pileup_snv(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, in
     if (!sorted && !readset_unsorted_ok(c, rs)) {
         return LFQ_ERR_INVALID;             /* as mpileup: bam_mplp_auto stops at a file that is not coordinate-sorted (plp.c:1406-1447) */
     }
+    {
+        /* -d cap: the kernels walk the kept reads only (null: the cap drops nothing, or there is none) */
+        const int32_t *k_idx, *k_pos, *k_pmax;
+        LFQ_TRY(readset_keep_device(c, rs, ps, &k_idx, &k_pos, &k_pmax));
+        if (k_idx) {
+            A.n_reads = rs->n_kept;
+            A.read_idx = k_idx;
+            A.pos = k_pos;
+            A.pmax_end = k_pmax;
+        }
+    }
     LFQ_TRY(sorted ? lfq_launch_pileup_columns(A, 0, ps) : lfq_launch_pileup_count(A, ps));
     /* columns from the counters on the device (lfq_launch_plp_compact_*): the host waits once, for three numbers */
     LfqPin<int64_t> tot(c, 4);
@@ -1245,9 +1468,13 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
     std::vector<Ev> evs_part[LFQ_HOST_PARTS];                    /* per thread, concatenated in read order below */
     /* (host arrays only: runs while the counter kernel of step 2 does) */
     auto scan_events = [&]() {
+    const uint8_t *kept = (c->plp_max_depth != LFQ_NO_MAX_DEPTH && rs->keep_valid && !rs->keep.empty()) ? rs->keep.data() : nullptr;
     lfq_for_reads(n, [&](int64_t r_begin, int64_t r_end, int part) {
     std::vector<Ev> &evs = evs_part[part];
     for (int64_t r = r_begin; r < r_end; r++) {
+        if (kept && !kept[r]) {
+            continue;                       /* dropped by the -d cap: in no column */
+        }
         const uint32_t *cg = rd->cigar + rd->cigar_off[r];
         const int n_cigar = (int)(rd->cigar_off[r + 1] - rd->cigar_off[r]);
         const int64_t s0 = rd->seq_off[r];
@@ -1422,6 +1649,17 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
             A.pmax_end = readset_pmax(c, rs, ps);
             if (!A.pmax_end && !readset_unsorted_ok(c, rs)) {
                 rc = LFQ_ERR_INVALID;       /* not coordinate-sorted: refused like mpileup does (lfq_set_pileup_unsorted) */
+            }
+        }
+        if (rc == LFQ_OK) {
+            /* -d cap: the kept reads only, the same decision as the SNV pileup's (the column lists must agree) */
+            const int32_t *k_idx, *k_pos, *k_pmax;
+            rc = readset_keep_device(c, rs, ps, &k_idx, &k_pos, &k_pmax);
+            if (rc == LFQ_OK && k_idx) {
+                A.n_reads = rs->n_kept;
+                A.read_idx = k_idx;
+                A.pos = k_pos;
+                A.pmax_end = k_pmax;
             }
         }
         if (rc == LFQ_OK) {

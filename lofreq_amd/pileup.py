@@ -7,6 +7,22 @@ import numpy as np
 from . import _lib
 from .baq import _OPS
 
+LFQ_NO_MAX_DEPTH = -1
+
+
+class _MaxDepth:
+    """lfq_set_max_depth on the caller's context for the duration of one call (None: no cap), back to none afterwards"""
+
+    def __init__(self, caller, max_depth):
+        self.h = caller.h
+        self.v = LFQ_NO_MAX_DEPTH if max_depth is None else int(max_depth)
+
+    def __enter__(self):
+        _lib.check(_lib.load().lfq_set_max_depth(self.h, self.v), "lfq_set_max_depth")
+
+    def __exit__(self, *exc):
+        _lib.load().lfq_set_max_depth(self.h, LFQ_NO_MAX_DEPTH)
+
 
 class DeviceTracks:
     """Tracks owned by the caller's context (valid until its next pileup call); quacks like a device PileupBatch."""
@@ -23,10 +39,11 @@ class DeviceTracks:
         return self._t
 
 
-def pileup_snv_tracks(caller, reads, ref, begin, end, lb=None, min_plp_bq=3, sq=None):
+def pileup_snv_tracks(caller, reads, ref, begin, end, lb=None, min_plp_bq=3, sq=None, max_depth=None):
     """reads: list of dicts {pos0, cigar [(op, len)], seq (codes 0..4), qual (phred), mapq, reverse};
     lb: list of the reads' lb tag bytes (from baq_batch) or None; sq: the reads' source-quality bytes (second
-    result of source_qual_batch) or None.  -> DeviceTracks"""
+    result of source_qual_batch) or None; max_depth: -d of `lofreq call` (lfq_set_max_depth), None = no cap.
+    -> DeviceTracks"""
     n = len(reads)
     pos = np.asarray([r["pos0"] for r in reads], np.int32)
     cig_off = np.zeros(n + 1, np.int64)
@@ -64,8 +81,9 @@ def pileup_snv_tracks(caller, reads, ref, begin, end, lb=None, min_plp_bq=3, sq=
         rd.sq = sq.ctypes.data
     t = _lib.Tracks()
     col_pos = np.zeros(max(end - begin, 1), np.int64)
-    _lib.check(_lib.load().lfq_pileup_snv_tracks(caller.h, C.byref(rd), int(begin), int(end), int(min_plp_bq),
-                                                 C.byref(t), col_pos.ctypes.data), "lfq_pileup_snv_tracks")
+    with _MaxDepth(caller, max_depth):
+        _lib.check(_lib.load().lfq_pileup_snv_tracks(caller.h, C.byref(rd), int(begin), int(end), int(min_plp_bq),
+                                                     C.byref(t), col_pos.ctypes.data), "lfq_pileup_snv_tracks")
     return DeviceTracks(t, col_pos[: int(t.ncols)].copy())
 
 
@@ -103,10 +121,10 @@ def _pack_reads(reads, ref, lb=None, sq=None):
     return rd, keep
 
 
-def pileup_indel_columns(caller, reads, ref, begin, end, min_plp_idq=0):
+def pileup_indel_columns(caller, reads, ref, begin, end, min_plp_idq=0, max_depth=None):
     """The indel fields of the pileup (`lfq_pileup_indel_columns`).  reads: as for pileup_snv_tracks, plus the
     optional per-read entries "bi", "bd", "ai", "ad" (tag bytes, uint8 arrays of the read's length, or None) and
-    "sq" (int).  -> (IndelColumns for call_indels / format_indel_record, positions of the columns)"""
+    "sq" (int); max_depth as for pileup_snv_tracks.  -> (IndelColumns for call_indels / format_indel_record, positions of the columns)"""
     from .indel import IndelColumns, _I32
     n = len(reads)
     rd, keep = _pack_reads(reads, ref)
@@ -129,9 +147,10 @@ def pileup_indel_columns(caller, reads, ref, begin, end, min_plp_idq=0):
         tags.sq = keep["sq"].ctypes.data
     out = C.POINTER(_lib.IndelColumnsC)()
     col_pos = np.zeros(max(end - begin, 1), np.int64)
-    _lib.check(_lib.load().lfq_pileup_indel_columns(caller.h, C.byref(rd), C.byref(tags), int(begin), int(end),
-                                                    int(min_plp_idq), C.byref(out), col_pos.ctypes.data),
-               "lfq_pileup_indel_columns")
+    with _MaxDepth(caller, max_depth):
+        _lib.check(_lib.load().lfq_pileup_indel_columns(caller.h, C.byref(rd), C.byref(tags), int(begin), int(end),
+                                                        int(min_plp_idq), C.byref(out), col_pos.ctypes.data),
+                   "lfq_pileup_indel_columns")
     return _indel_columns_from_c(out, col_pos, caller)
 
 
@@ -302,20 +321,32 @@ class ReadSet:
         _lib.check(self.L.lfq_readset_fetch_tags(self.caller.h, self.h, p(lb), p(ai), p(ad), p(fl)), "lfq_readset_fetch_tags")
         return lb, ai, ad, fl
 
-    def pileup_snv(self, begin, end, min_plp_bq=3, sync=False):
+    def kept_reads(self, max_depth=None):
+        """lfq_readset_kept_reads: which reads the pileups take under the cap -> (uint8 mask, number kept)"""
+        keep = np.zeros(max(self.n, 1), np.uint8)
+        n_kept = C.c_int64(-1)
+        with _MaxDepth(self.caller, max_depth):
+            _lib.check(self.L.lfq_readset_kept_reads(self.caller.h, self.h, keep.ctypes.data, C.byref(n_kept)),
+                       "lfq_readset_kept_reads")
+        return keep[: self.n], int(n_kept.value)
+
+    def pileup_snv(self, begin, end, min_plp_bq=3, sync=False, max_depth=None):
         """lfq_readset_pileup_snv returns when the scatter pass is queued: the tracks are complete in stream order (the calls
-        that take them are queued behind); sync=True waits, for code that reads the device memory itself"""
+        that take them are queued behind); sync=True waits, for code that reads the device memory itself.  max_depth: -d
+        of `lofreq call` (lfq_set_max_depth), None = no cap"""
         t = _lib.Tracks()
         col_pos = np.zeros(max(end - begin, 1), np.int64)
-        _lib.check(self.L.lfq_readset_pileup_snv(self.caller.h, self.h, int(begin), int(end), int(min_plp_bq), C.byref(t),
-                                                 col_pos.ctypes.data), "lfq_readset_pileup_snv")
+        with _MaxDepth(self.caller, max_depth):
+            _lib.check(self.L.lfq_readset_pileup_snv(self.caller.h, self.h, int(begin), int(end), int(min_plp_bq),
+                                                     C.byref(t), col_pos.ctypes.data), "lfq_readset_pileup_snv")
         if sync:
             self.caller.synchronize()
         return DeviceTracks(t, col_pos[: int(t.ncols)].copy())
 
-    def pileup_indels(self, begin, end, min_plp_idq=0):
+    def pileup_indels(self, begin, end, min_plp_idq=0, max_depth=None):
         out = C.POINTER(_lib.IndelColumnsC)()
         col_pos = np.zeros(max(end - begin, 1), np.int64)
-        _lib.check(self.L.lfq_readset_pileup_indels(self.caller.h, self.h, int(begin), int(end), int(min_plp_idq),
-                                                    C.byref(out), col_pos.ctypes.data), "lfq_readset_pileup_indels")
+        with _MaxDepth(self.caller, max_depth):
+            _lib.check(self.L.lfq_readset_pileup_indels(self.caller.h, self.h, int(begin), int(end), int(min_plp_idq),
+                                                        C.byref(out), col_pos.ctypes.data), "lfq_readset_pileup_indels")
         return _indel_columns_from_c(out, col_pos, self.caller)

@@ -66,6 +66,22 @@ def test_knob_selected_paths(knob, sel):
     assert " passed" in p.stdout and "failed" not in p.stdout.splitlines()[-1], tail
 
 
+EDGES = ["tests/test_gpu_dp_edges.py"]
+EDGE_CASES = [
+    ("LFQ_SPLIT_POOL_CELLS=0", EDGES),       # every big column on the unsplit big kernel, every mid column unsplit
+    ("LFQ_SEG_MAX=2", EDGES),                # two row segments per split column
+    ("LFQ_LIGHT_KERNEL=wave", EDGES + ["-k", "not screen_variant"]),    # no screen kernel (nothing to count retries of)
+    ("LFQ_SCREEN_ROUNDS=2", EDGES),          # screen survivors after two windows to the retry kernel
+    ("LFQ_BIG_ON_SIDE=1", EDGES),            # the unsplit big columns behind the big chain
+]
+
+
+@pytest.mark.parametrize("knob,sel", EDGE_CASES, ids=[c[0] for c in EDGE_CASES])
+def test_knob_selected_dp_edges(knob, sel):
+    """the DP boundary tests (K, depth and pruning edges of every route) under the fallback knobs"""
+    test_knob_selected_paths(knob, sel)
+
+
 _SKIP_PROBE = r"""
 import sys
 sys.path.insert(0, "tests")

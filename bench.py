@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- pileup columns/sec of the per-column SNV calling path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4|C5] [--mode resident|host-abi|chain|baq]
+    python bench.py --gpus N --steps K --warmup W [--config C3|C2|C4|C5] [--mode resident|host-abi|chain|baq] [--full]
 
 A step is one pass of the hot path (count -> running-Bonferroni scan -> Poisson-binomial DP -> host emit test /
 filter / VCF records) over one batch of synthetic pileup columns that are ALREADY RESIDENT IN HBM (generated on
@@ -13,18 +13,23 @@ the reference's call-parallel model) or, with `--scaling strong`, its bins of ON
 lofreq_amd.shard.plan_regions; the only exchange is the tested-column count all-gather + the record gather of
 lofreq_amd/shard.py.
 
-Prints ONE JSON line on rank 0 with these extra objects:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its line; its `roofline` and `dp` come
+from the timed steps' own HIP events and device counters.  `--full` adds, after that, everything the headline figure does not
+need: the counter passes, the CPU baselines, the whole-batch oracle check, config.secondary and the C1 / C2 / C4 / C5 child
+runs (C3), the BAQ roofline, sample concordance and PCIe-inclusive rate (C4 / C5).
+
+Prints ONE JSON line on rank 0 with these extra objects (those marked --full only in such a run):
   roofline      HBM roofline of the dominant kernel: bytes the launched instantiation moves (from the layout: the
                 library reports them per batch) / its HIP-event duration (events on the stream the kernel runs on,
-                taken inside the C library) / 8 TB/s.  `traffic` = HBM bytes per launch from rocprofv3 PMC passes
+                taken inside the C library) / 8 TB/s.  `traffic` (--full) = HBM bytes per launch from rocprofv3 PMC passes
                 that THIS run spawns on the same workload (FETCH_SIZE and WRITE_SIZE in separate passes, FETCH_SIZE
                 doubled for 16 B/lane streaming reads per MI355X_MICROARCH.md), or null when rocprofv3 is not usable.
                 `algorithmic_8d` keeps SURVEY 8(d)'s 4*depth+80 bytes per column figure (the kernel has to read only
                 1.5 of those 4 bytes, so that ratio can exceed 1 and is not called a fraction).
   dp            secondary figure: recurrence cells processed per step (device counters), cells/s over
-                the DP span, VALU-busy of the DP kernels from an SQ_INSTS_VALU pass.
-  cpu_baseline  the oracle (CPU restatement of the reference algorithm), one pinned core, bounded sample.
-  config.secondary   (N = 1) the two paths a caller outside this benchmark takes: `host_abi` = host buffers through
+                the DP span, VALU-busy of the DP kernels from an SQ_INSTS_VALU pass (--full).
+  cpu_baseline  (--full) the oracle (CPU restatement of the reference algorithm), one pinned core, bounded sample.
+  config.secondary   (--full, N = 1) the two paths a caller outside this benchmark takes: `host_abi` = host buffers through
                 lfq_call_snvs_batch(tracks_on_device = 0), PCIe included; `chain` = reads -> BAQ -> pileup -> calls.
 """
 import argparse
@@ -57,9 +62,14 @@ def seed_of(config_id):
     return 0x9E3779B97F4A7C15 ^ (config_id << 32)      # SURVEY 8d seed formula
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baselines, the whole-batch "
+                         "oracle check, the rocprofv3 counter passes, config.secondary, the C1 / C2 / C4 / C5 child runs, C4 / C5's "
+                         "BAQ roofline and PCIe-inclusive rate (default: set up, warm up, time the steps, print the line; "
+                         "the --no-* options below pick from what --full adds)")
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps (default 200; C4 / C5: 5, C1: 5, --mode chain: 2, --mode baq / host-abi: 10)")
     ap.add_argument("--warmup", type=int, default=None,
@@ -80,7 +90,8 @@ def parse_args():
                     help="C4 / C5: the timed steps upload every bin's reads from (pinned) host memory again -- the PCIe-inclusive "
                          "rate; default: the read sets are resident in HBM when the timed region starts (uploaded in the "
                          "warm-up), and the PCIe-inclusive rate of a few extra steps is reported beside `value`")
-    ap.add_argument("--no-upload-rate", action="store_true", help="C4 / C5: skip the extra steps that time the PCIe-inclusive rate")
+    ap.add_argument("--no-upload-rate", action="store_true",
+                    help="C4 / C5 with --full: skip the extra steps that time the PCIe-inclusive rate")
     ap.add_argument("--host-threads", type=int, default=6,
                     help="C4 / C5: host threads per rank, one context each, that work through the rank's bins (the host part "
                          "of one bin -- CIGAR geometry, event tables, test descriptors -- then runs under the kernels of another)")
@@ -93,9 +104,12 @@ def parse_args():
     ap.add_argument("--cols", type=int, default=None, help="columns per GPU (region shard)")
     ap.add_argument("--plant-period", type=int, default=997)
     ap.add_argument("--cpu-sample-cols", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic = null)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the host-abi / chain measurements of config.secondary")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip cpu_baseline (C4 / C5: and the sample concordance that goes with it)")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="with --full: skip the rocprofv3 counter passes (roofline.traffic = null)")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the host-abi / chain measurements of config.secondary")
     ap.add_argument("--nt-bytes", action="store_true",
                     help="one byte per observation in the nt track instead of the packed layout (LFQ_TRACKS_NT_PACKED)")
     ap.add_argument("--in-flight", type=int, default=0, choices=[0, 1, 2, 3, 4, 6, 8],
@@ -127,13 +141,19 @@ def parse_args():
                     help="timed blocks of --steps steps: the first one is the reported value, all of them go into `repeats` "
                          "(default 1: a run times exactly --steps steps)")
     ap.add_argument("--no-full-check", action="store_true",
-                    help="N = 1: skip the whole-batch oracle run on all host cores (config.vcf_concordance then covers the "
+                    help="N = 1 with --full: skip the whole-batch oracle run on all host cores (config.vcf_concordance then covers the "
                          "cpu_baseline sample only)")
     ap.add_argument("--full-check-procs", type=int, default=None, help="oracle processes of the whole-batch check")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="C3, N = 1: skip the short C2 / C4 / C5 child runs whose scalars (c2_*, c4_*, c5_*) the line's config carries")
+                    help="C3, N = 1 with --full: skip the short C1 / C2 / C4 / C5 child runs whose scalars (c1_* .. c5_*) the "
+                         "line's config carries")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else: every extra is off
+        args.no_pmc = args.no_cpu_baseline = args.no_full_check = args.no_secondary = True
+        args.no_other_configs = args.no_upload_rate = True
+    return args
 
 
 def cpu_model():
@@ -1111,7 +1131,7 @@ def bench_genome(args, cfg_name, caller, la, shard, dist, world, rank, dev, xdev
         dist.all_reduce(tot_cols)
     dt, called = float(tmax.item()), int(tot_cols.item())
     roof = base = concord = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:      # BAQ calls and counter passes of their own, the oracle's sample
         try:
             roof = genome_baq_roofline(args, cfg_name, cfg, caller, la, R, dev)
         except Exception as e:          # the measured line survives a failed counter pass
@@ -1165,11 +1185,12 @@ def bench_genome(args, cfg_name, caller, la, shard, dist, world, rank, dev, xdev
 def other_configs(budget_s=420.0):
     """BASELINE.json configs[1], [3], [4] (C2, C4, C5) as short runs of this same script in child processes, after the C3
     line's own work: their figures go into the C3 line's `config` as SCALARS (c2_*, c4_*, c5_*), so that one driver run
-    witnesses every config with its concordance flag.  A child that fails or runs out of time leaves `<cfg>_error`."""
+    witnesses every config with its concordance flag.  A child that fails or runs out of time leaves `<cfg>_error`.  The
+    children run with --full: their concordance, roofline and CPU baseline are what the scalars carry."""
     runs = [("c1", ["--config", "C1", "--steps", "2", "--warmup", "1"], 120),
-            ("c2", ["--config", "C2", "--steps", "60", "--warmup", "5", "--no-secondary", "--no-pmc", "--no-other-configs"], 150),
-            ("c4", ["--config", "C4", "--steps", "2", "--warmup", "1", "--no-pmc", "--cpu-sample-cols", "30000"], 200),
-            ("c5", ["--config", "C5", "--steps", "2", "--warmup", "1", "--no-pmc", "--cpu-sample-cols", "150000"], 200)]
+            ("c2", ["--config", "C2", "--steps", "60", "--warmup", "5", "--full", "--no-secondary", "--no-pmc", "--no-other-configs"], 150),
+            ("c4", ["--config", "C4", "--steps", "2", "--warmup", "1", "--full", "--no-pmc", "--cpu-sample-cols", "30000"], 200),
+            ("c5", ["--config", "C5", "--steps", "2", "--warmup", "1", "--full", "--no-pmc", "--cpu-sample-cols", "150000"], 200)]
     out = {}
     t_start = time.perf_counter()
     for name, argv, limit in runs:

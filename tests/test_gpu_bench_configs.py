@@ -20,7 +20,7 @@ def _run(cfg, gpus, vcf, scale):
     if gpus > 1:
         env["LFQ_BENCH_ONE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--gpus", str(gpus), "--steps", "1",
-                        "--warmup", "1", "--genome-scale", str(scale), "--vcf-out", vcf, "--no-pmc"] + ([] if gpus == 1 else ["--no-cpu-baseline"]),
+                        "--warmup", "1", "--genome-scale", str(scale), "--vcf-out", vcf, "--full", "--no-pmc"] + ([] if gpus == 1 else ["--no-cpu-baseline"]),
                        cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]

@@ -138,7 +138,7 @@ def test_bench_sharded_step_through_a_one_rank_rccl_communicator():
 
     def run(extra_env, *args):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--cols", "40000",
-                            "--repeats", "1", "--no-pmc", "--no-cpu-baseline", "--no-secondary"] + list(args),
+                            "--repeats", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--no-secondary"] + list(args),
                            env=dict(base, **extra_env), capture_output=True, text=True, timeout=400)
         assert p.returncode == 0, p.stderr[-2000:]
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

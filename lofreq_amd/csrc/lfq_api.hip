@@ -137,9 +137,8 @@ int lfq_make_params(const lfq_conf *conf, const lfq_tracks *tr, LfqParams *P, bo
     P->prune_slack = 1e-6;
     P->bonf_step = 3;
     P->bonf_reset_first = 1;
-    P->phase1_chunks = lfq_knobs().phase1_chunks;
-    P->seg_budget_mid = lfq_knobs().seg_budget_mid;
-    P->seg_budget_big = lfq_knobs().seg_budget_big;
+    P->phase1_chunks = LFQ_PHASE1_CHUNKS;
+    P->seg_budget_mid = P->seg_budget_big = LFQ_SEG_BUDGET;
     P->seg_max = lfq_knobs().seg_max >= 0 ? lfq_knobs().seg_max : LFQ_SEG_MAX;      /* (lfq_batch_device_impl: by the gate) */
     P->seg_max_mid = lfq_knobs().seg_max_mid >= 0 ? lfq_knobs().seg_max_mid : LFQ_SEG_MAX;
     if (indel_mode) {
@@ -704,7 +703,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         LFQ_TRY_HIP(hipEventRecord(c->ev_cnt[s][0], st));
         /* (a context that queues batches without a gate on the device's shared stream: its shallow count kernel takes half of a CU) */
         const bool ungated = c->batch_gate == LFQ_GATE_NONE && st == c->stream && !c->priv_stream_on && !single_stream;
-        LFQ_TRY(lfq_launch_count(T, c0, c1, P, c->d_luts, d_counts, c->d_flags, max_depth, st, ungated ? kn.count_shallow_wgs_none : 0));
+        LFQ_TRY(lfq_launch_count(T, c0, c1, P, c->d_luts, d_counts, c->d_flags, max_depth, st, ungated));
         c->cur_sparse_counts = P.sparse_counts && lfq_count_is_shallow(T, P, max_depth);
         LFQ_TRY_HIP(hipEventRecord(c->ev_cnt[s][1], st));
 
@@ -718,9 +717,9 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         }
         LFQ_TRY_HIP(hipEventRecord(c->ev_scan[s], dps));
         /* DP4 tuples of the mid / big class alleles with >= 16 alt bases -> host; Fisher tests start when they arrive.  On the
-         * dps stream behind the scan: in front of the screen kernel (the host starts 0.1-0.4 ms earlier) or behind it
-         * (LFQ_HEAVY_AFTER_SCREEN: one launch less between the scan and the light chain, which is what a shallow batch's
-         * period is made of when batches are gated on the chains' tails) */
+         * dps stream behind the screen kernel: in front of it the host starts 0.1-0.4 ms earlier, but that is one launch more
+         * between the scan and the light chain, which is what a shallow batch's period is made of when batches are gated on
+         * the chains' tails.  Behind the scan only where no screen kernel runs. */
         const bool sb_heavy = n_seg == 1 && !indel_mode && c->leader && !kn.no_sb_precompute;
         auto launch_heavy = [&]() -> int {
             if (P.lazy_strand) {        /* the count kernel left the strands out: count them for the heavy columns here */
@@ -737,12 +736,9 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
             c->lcv->notify_all();
             return LFQ_OK;
         };
-        const bool heavy_late = sb_heavy && kn.heavy_after_screen && !kn.skip_light && kn.light_kernel != 2;
-        if (sb_heavy && !heavy_late) {
+        const bool screen = !kn.skip_light && kn.light_kernel != 2;
+        if (sb_heavy && !screen) {
             LFQ_TRY(launch_heavy());
-        }
-        if (kn.tail_light == 2) {
-            LFQ_TRY(tail_record(c, 2, dps));
         }
         const int64_t seg_cols = c1 - c0;
         /* the light kernel is throughput work and persistent: it must leave wave slots for the short
@@ -753,7 +749,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
          * screen wavefront costs the count kernel a slot -- C3 2.82-2.84 -> 2.77-2.79 ms per step with one, C2 0.523-0.528 ->
          * 0.505-0.512 with one or two; shallow batches keep two (their chain is the longer part of a shorter period). */
         const int screen_auto = (c->batch_gate == LFQ_GATE_NONE && !indel_mode) ? (tr->max_col_obs >= 4096 ? 1 : 2) : 4;
-        const int light_waves_per_cu = kn.light_kernel == 0 ? (kn.screen_waves_per_cu >= 1 ? kn.screen_waves_per_cu : screen_auto) : 10;
+        const int light_waves_per_cu = kn.light_kernel == 0 ? screen_auto : 10;
         const int n_light_waves = (int)std::min<int64_t>((int64_t)c->n_cu * light_waves_per_cu, std::max<int64_t>(seg_cols / 8, 4));
         const int n_mid_waves = (int)std::min<int64_t>((int64_t)c->n_cu * 4, std::max<int64_t>(seg_cols, 4));
         const bool run_big = !kn.skip_big, run_mid = !kn.skip_mid;     /* profiling aid: run the DP classes in isolation */
@@ -833,10 +829,10 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
                 const int kh = indel_mode ? c->kreg_hint_indel : c->kreg_hint;
                 LFQ_TRY(lfq_launch_dp_quad(T, P, c->d_luts, d_counts, W, c->d_retry + c0, d_pvals, pvals_capacity,
                                            n_light_waves, kh, dps, 1));
-                if (kn.tail_light == 1) {       /* the retry kernel beside the next batch's count kernel, like the folds */
-                    LFQ_TRY(tail_record(c, 2, dps));
-                }
-                if (heavy_late) {
+                /* the light chain's tail event (what the next batch's count kernel waits for under LFQ_GATE_TAIL): the retry
+                 * kernel is a few hundred latency-bound wavefronts and runs beside that count kernel, like the folds */
+                LFQ_TRY(tail_record(c, 2, dps));
+                if (sb_heavy) {
                     LFQ_TRY(launch_heavy());
                 }
                 LFQ_TRY(lfq_launch_dp_quad(T, P, c->d_luts, d_counts, W, c->d_retry + c0, d_pvals, pvals_capacity,
@@ -844,7 +840,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
             }
         }
         LFQ_TRY_HIP(hipEventRecord(c->ev_light[s][1], dps));
-        if (kn.tail_light == 0 || (kn.tail_light == 1 && (kn.skip_light || kn.light_kernel == 2))) {
+        if (!screen) {
             LFQ_TRY(tail_record(c, 2, dps));
         }
         for (int i = 0; i < 2; i++) {
@@ -852,13 +848,13 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         }
     }
     /* Join.  A caller that passed its own stream gets everything joined back into it.  On the library's own streams
-     * (layer 2) the batch ends on the dps stream instead and `st` carries nothing but the memsets and count kernels:
+     * (layer 2) the batch ends on the big chain's stream instead and `st` carries nothing but the memsets and count kernels:
      * the count kernel of the NEXT batch (another context on the same device streams) then starts as soon as this
      * batch's count kernel is done and streams through HBM while this batch's DP kernels -- latency / issue-bound,
      * < 1 GB of traffic, on the high-priority streams -- run beside it. */
-    /* (LFQ_JOIN_ON_SIDE: on the big chain's stream, which is the last to end anyway -- the dps stream is then free for the NEXT
-     * batch's scan as soon as this batch's retry kernel is done, instead of when its last fold is) */
-    hipStream_t jn = (st != c->stream || single_stream) ? st : (kn.join_on_side ? side0 : dps);
+    /* (the big chain is the last to end anyway -- the dps stream is then free for the NEXT batch's scan as soon as this
+     * batch's retry kernel is done, instead of when its last fold is) */
+    hipStream_t jn = (st != c->stream || single_stream) ? st : side0;
     LFQ_TRY_HIP(hipEventRecord(c->ev[1], st));                     /* all count kernels done */
     LFQ_TRY_HIP(hipEventRecord(c->ev_join[0], side0));
     LFQ_TRY_HIP(hipEventRecord(c->ev_join[1], side1));

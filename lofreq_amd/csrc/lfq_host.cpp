@@ -87,30 +87,16 @@ const LfqKnobs &lfq_knobs(void)
             x.light_kernel = !strcmp(lk, "wave") ? 2 : 0;
         }
 #endif
-        x.screen_waves_per_cu = (int)LFQ_TUNE_I("LFQ_SCREEN_WAVES_PER_CU", -1);      /* < 1: by the context's gate and the batch's depth */
         x.screen_rounds = (int)std::max(1L, LFQ_TUNE_I("LFQ_SCREEN_ROUNDS", 24));
-        x.phase1_chunks = (int)std::max(1L, LFQ_TUNE_I("LFQ_PHASE1_CHUNKS", LFQ_PHASE1_CHUNKS));
         {
             const long both = LFQ_TUNE_I("LFQ_SEG_MAX", -1);
             const long big = LFQ_TUNE_I("LFQ_SEG_MAX_BIG", both), mid = LFQ_TUNE_I("LFQ_SEG_MAX_MID", both);
             x.seg_max = big < 0 ? -1 : (int)std::min((long)LFQ_SEG_MAX, std::max(2L, big));
             x.seg_max_mid = mid < 0 ? -1 : (int)std::min((long)LFQ_SEG_MAX, std::max(2L, mid));
         }
-        x.seg_budget_mid = (int)std::max(1L, LFQ_TUNE_I("LFQ_SEG_BUDGET_MID", 4096));
-        x.seg_budget_big = (int)std::max(1L, LFQ_TUNE_I("LFQ_SEG_BUDGET_BIG", 4096));
         x.split_pool_cells = (int)std::max(0L, LFQ_TUNE_I("LFQ_SPLIT_POOL_CELLS", 8L << 20));
         x.count_multi_below = LFQ_TUNE_I("LFQ_COUNT_MULTI_BELOW", 4096);
-        {
-            const long w = LFQ_TUNE_I("LFQ_COUNT_WAVES_PER_WG", 16);
-            x.count_waves_per_wg = (w == 4 || w == 8 || w == 12) ? (int)w : 16;
-        }
-        {
-            const long u = LFQ_TUNE_I("LFQ_COUNT_AHEAD_DEEP", 2);
-            x.count_ahead_deep = (u == 3 || u == 4) ? (int)u : 2;
-        }
-        x.count_cols_per_wave = (int)std::min(std::max(LFQ_TUNE_I("LFQ_COUNT_COLS_PER_WAVE", 1), 1L), 16L);
         x.big_on_side = LFQ_TUNE_HAS("LFQ_BIG_ON_SIDE");
-        x.sb_par_min_cost = LFQ_TUNE_I("LFQ_SB_PAR_MIN_COST", 4000);
         x.pileup_tiles = (int)LFQ_TUNE_I("LFQ_PILEUP_TILES", 1);
         x.baq_one_variant = LFQ_TUNE_HAS("LFQ_BAQ_ONE_VARIANT") ? 1 : 0;
         x.count_lpg4_below = LFQ_TUNE_I("LFQ_COUNT_LPG4_BELOW", 320);
@@ -119,13 +105,6 @@ const LfqKnobs &lfq_knobs(void)
         x.indel_host_pack = LFQ_TUNE_HAS("LFQ_INDEL_HOST_PACK");
         x.pileup_atomic = LFQ_TUNE_HAS("LFQ_PILEUP_ATOMIC");
         x.baq_lds = LFQ_TUNE_I("LFQ_BAQ_LDS", 1) != 0;
-        x.baq_idaq_beside = (int)LFQ_TUNE_I("LFQ_BAQ_IDAQ_BESIDE", 0);
-        x.tail_light = (int)std::min(2L, std::max(0L, LFQ_TUNE_I("LFQ_TAIL_LIGHT", 1)));
-        x.count_shallow_wgs_none = (int)std::min(4L, std::max(0L, LFQ_TUNE_I("LFQ_COUNT_SHALLOW_WGS_NONE", 2)));
-        x.count_lean_lds_pad = (int)std::min(160000L, std::max(0L, LFQ_TUNE_I("LFQ_COUNT_LEAN_LDS_PAD", 0)));
-        x.count_shallow_lds_pad = (int)std::min(120000L, std::max(0L, LFQ_TUNE_I("LFQ_COUNT_SHALLOW_LDS_PAD", 0)));
-        x.join_on_side = (int)LFQ_TUNE_I("LFQ_JOIN_ON_SIDE", 1);
-        x.heavy_after_screen = (int)LFQ_TUNE_I("LFQ_HEAVY_AFTER_SCREEN", 1);
         (void)geti;
         (void)has;
         return x;
@@ -740,8 +719,9 @@ int lfq_finalize_pvals(const lfq_conf *conf, const lfq_col_pvals *pvals, int64_t
         for (int64_t j = 0; j < nm; j++) {
             cost += records[miss[(size_t)j]].alt_fw + records[miss[(size_t)j]].alt_rv;
         }
-        /* waking the pool costs more than a few cheap tables */
-        const int helpers = cost < lfq_knobs().sb_par_min_cost ? 0 : (int)std::min<int64_t>(LfqPool::instance().size(), nm / 4);
+        /* waking the pool costs more than a few cheap tables (a summed alt count of 4000; 20000 left a 200x batch's 700 tables
+         * of 10-30 alt bases, 0.22 ms of a host-paced 0.85 ms step, on one thread) */
+        const int helpers = cost < 4000 ? 0 : (int)std::min<int64_t>(LfqPool::instance().size(), nm / 4);
         LfqPool::instance().run(work, helpers);
         tf[4] = now();
         if (timing) {

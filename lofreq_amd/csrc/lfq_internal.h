@@ -122,6 +122,7 @@ struct LfqLong {              /* 128 bytes */
 #endif
 #define LFQ_SEG_SHORT_BELOW 48
 #define LFQ_PHASE1_CHUNKS 8       /* mid class: rows run unsplit before a surviving column is cut up (measured: 4..8 best) */
+#define LFQ_SEG_BUDGET 4096       /* row segments per class and batch (LfqParams::seg_budget_mid / _big) */
 #define LFQ_SPLIT_MAX_K 2016      /* 63 * 32: one wavefront at 32 cells per lane; the combine kernel keeps two
                                    * (K+1)-cell distributions in LDS */
 
@@ -182,9 +183,11 @@ struct LfqWork {
 #define LFQ_NKHIST 7
 #define LFQ_CNT_LONG0 16       /* +class: row-split columns per cells-per-lane class (LFQ_SEG_CLASSES) */
 
-/* ---- experiment / debugging knobs ----------------------------------------------------------------
+/* ---- environment knobs ---------------------------------------------------------------------------
  * Environment variables, read ONCE per process (first lfq_create / first use) into this struct; no entry point
- * calls getenv() on its own.  All optional; DESIGN.md "Environment knobs" documents them. */
+ * calls getenv() on its own.  All optional.  The release library reads ten, none of which changes a result; the others exist
+ * in the tuning build only, and each forces a path the release takes by itself for some input or context, so that
+ * tests/test_gpu_knobs.py can reach it. */
 /* Read bases are codes: 0..3 = A, C, G, T, 4 = N (seq_nt16_int of the BAM base; everything the HMM, the pileups and the tests
  * look at), and -- round 6 -- 5..15 = the other letters of htslib's seq_nt16_str in its order, "=MRSVWYHKDB".  Wherever the
  * reference compares the LETTER of a read base with a reference letter (idaq's repeat scan bam_md_ext.c:197, count_cigar_ops
@@ -207,25 +210,16 @@ struct LfqKnobs {
     int skip_light, skip_mid, skip_big;   /* LFQ_DEBUG_SKIP=light,mid,big: run the DP classes in isolation */
     int light_kernel;          /* LFQ_LIGHT_KERNEL=wave: 2 = one light column per wavefront instead of the screen kernel (the
                                 * kernel that serves K >= 32 anyway); 0 = screen (one light column per lane) */
-    int screen_waves_per_cu;   /* LFQ_SCREEN_WAVES_PER_CU (-1 = auto: 4, and for a context that queues its batches without a gate 1 for deep / 2 for
-                                * shallow batches): the screen is latency-bound per column, more wavefronts only crowd the other chains */
     int screen_rounds;         /* LFQ_SCREEN_ROUNDS (24): 16-row windows before a light column goes to the retry kernel */
-    int phase1_chunks;         /* LFQ_PHASE1_CHUNKS */
     int seg_max;               /* LFQ_SEG_MAX: both classes; LFQ_SEG_MAX_BIG / LFQ_SEG_MAX_MID: one of them (-1 = not given) */
     int seg_max_mid;
-    int seg_budget_mid, seg_budget_big;   /* LFQ_SEG_BUDGET_MID (4096), LFQ_SEG_BUDGET_BIG (4096) */
     int split_pool_cells;      /* LFQ_SPLIT_POOL_CELLS (8 Mi; 0 disables the row split) */
     long count_multi_below;    /* LFQ_COUNT_MULTI_BELOW (4096) */
-    int count_waves_per_wg;    /* LFQ_COUNT_WAVES_PER_WG (16; 4, 8): columns per workgroup of the one-column-per-wavefront count kernel */
-    int count_ahead_deep;      /* LFQ_COUNT_AHEAD_DEEP (2; 3, 4): chunks of 16 observations in flight per lane of the lean count kernel */
-    int count_cols_per_wave;   /* LFQ_COUNT_COLS_PER_WAVE (1; 2, 4): columns a wavefront of the lean count kernel takes one after the other,
-                                * all their headers requested when it starts */
     int big_on_side;           /* LFQ_BIG_ON_SIDE: the unsplit big columns behind the big chain instead of on the count kernel's stream
                                 * (a context with LFQ_GATE_NONE runs that way by itself) */
     int baq_one_variant;       /* LFQ_BAQ_ONE_VARIANT: every wavefront of the plain narrow-band BAQ launches through the instantiation with the N case */
     int pileup_tiles;          /* LFQ_PILEUP_TILES (1): SNV pileup of sorted reads by tiles of 64 positions; 0 = a wavefront per position */
     long host_loop_threads;    /* LFQ_HOST_LOOP_THREADS (8): threads (caller included) a host loop over reads / positions / events is cut for, at most 16 */
-    long sb_par_min_cost;      /* LFQ_SB_PAR_MIN_COST (4000; 20000 until the end of round 5: a 200x batch's 700 tables of 10-30 alt bases were 0.22 ms of a host-paced 0.85 ms step on one thread): summed alt counts of the strand-bias tests of a batch from which they go to the host pool */
     long count_lpg4_below, count_lpg8_below;   /* LFQ_COUNT_LPG4_BELOW (320), LFQ_COUNT_LPG8_BELOW (900): deepest column up to which 4 / 8 lanes share a column */
     long host_spin_us;         /* LFQ_HOST_SPIN_US (2000): how long the helper threads of the host loops spin for the next loop; -1 = no pool */
     int sync_upload;           /* LFQ_SYNC_UPLOAD: 1 = lfq_readset_create waits for its copies itself (no helper thread), 2 = helper thread whatever the size */
@@ -235,19 +229,8 @@ struct LfqKnobs {
     int indel_host_pack;       /* LFQ_INDEL_HOST_PACK */
     int pileup_atomic;         /* LFQ_PILEUP_ATOMIC: read-major pileup kernels even for sorted reads */
     int baq_lds;               /* LFQ_BAQ_LDS (1) */
-    int baq_idaq_beside;       /* LFQ_BAQ_IDAQ_BESIDE (0): the narrow-band reads with indels on a side stream beside the plain launches (a lone BAQ + IDAQ call 6.2 -> 5.3 ms per 400 K reads, the reads -> VCF chain 37.7 -> 39.0 ms per region: off) */
     long baq_scratch_mb;       /* LFQ_BAQ_SCRATCH_MB: -1 = from free HBM */
-    int tail_light;            /* LFQ_TAIL_LIGHT (1): where the light chain records the device's tail event (what the next batch's count
-                                * kernel waits for under LFQ_GATE_TAIL): 0 = behind the retry kernel, 1 = behind the screen kernel (the
-                                * retry kernel is a few hundred latency-bound wavefronts: beside the count kernel like the folds), 2 = behind the scan */
-    int count_shallow_wgs_none; /* LFQ_COUNT_SHALLOW_WGS_NONE (2): workgroups per CU of the shared-wavefront count kernel of a context whose batches are
-                                * queued without a gate (0 = as many as fit: four) -- the other half of every SIMD is what another batch's DP kernels run in */
-    int count_lean_lds_pad;    /* LFQ_COUNT_LEAN_LDS_PAD (0): bytes of unused dynamic LDS per workgroup of the lean count kernel */
-    int count_shallow_lds_pad; /* LFQ_COUNT_SHALLOW_LDS_PAD (0): bytes of unused dynamic LDS per workgroup of the shared-wavefront count kernel */
-    int join_on_side;          /* LFQ_JOIN_ON_SIDE (1): a batch's join (strand counts of its records, counters to the host) on the big chain's stream instead of the light chain's */
     int private_stream;        /* LFQ_PRIVATE_STREAM (0): lfq_create gives every context a launch stream of its own (lfq_set_private_stream) */
-    int heavy_after_screen;    /* LFQ_HEAVY_AFTER_SCREEN (1): the strand counts of the heavy columns (host Fisher precompute) behind the screen
-                                * kernel instead of in front of it: one launch less between the scan and the light chain */
 };
 const LfqKnobs &lfq_knobs(void);
 /* CPUs this process may actually use: the affinity mask and the cgroup's cpu.max quota, not the machine's core count
@@ -437,8 +420,8 @@ int lfq_launch_maxdepth(const LfqTracksDev &t, int32_t *d_gcounters, void *strea
 int lfq_launch_ntcount(const LfqTracksDev &t, int32_t *d_out, void *stream);
 bool lfq_count_is_shallow(const LfqTracksDev &t, const LfqParams &p, int64_t max_col_obs);
 int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqParams &p, const LfqLuts *d_luts,
-                     lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, int shallow_wgs_per_cu = 0);
-/* (shallow_wgs_per_cu: workgroups per CU the shared-wavefront count kernel may have resident, 0 = as many as fit) */
+                     lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, bool shallow_half_cu = false);
+/* (shallow_half_cu: the shared-wavefront count kernel keeps two workgroups per CU resident instead of as many as fit) */
 int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const uint8_t *d_flags,
                     const lfq_col_counts *d_counts, const LfqWork &w, void *stream, bool relist = false);
 /* -t / --approx-threshold (snpcaller.c:1128-1142): clears the flag byte of the listed columns the Poisson gate gives up;

@@ -1089,7 +1089,7 @@ __device__ __forceinline__ LfqColHdr lfq_load_col_hdr(const LfqCountArgs &T, int
     return h;
 }
 
-template <bool SAME_THR, int UNROLL>
+template <bool SAME_THR>
 __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq_col_counts *__restrict__ out,
                                                       uint8_t *__restrict__ flags, int64_t col, int lane, const LfqColHdr &H)
 {
@@ -1117,6 +1117,7 @@ __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq
         const uint2 *nt8 = reinterpret_cast<const uint2 *>(T.nt) + cbeg;
         const uint4 *bq16 = reinterpret_cast<const uint4 *>(T.bq) + cbeg;
         const int n_in = n_ch - 1;                                            /* interior chunks: 1 .. n_ch - 2 */
+        constexpr int UNROLL = 2;                                             /* chunks in flight per lane, as in lfq_count_column_fast */
 #ifdef LFQ_COUNT_STAMP
         st1 = wall_clock64() + (uint64_t)(n_ch & 0);
 #endif
@@ -1234,16 +1235,24 @@ __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq
     }
 }
 
-/* CPW columns per wavefront, one after the other (a workgroup: CPW runs of WAVES neighbouring columns).  The headers of all
- * of them are requested at once when the wavefront starts -- scalar loads, they cost no vector register --, so that only the first
- * column waits for its header: two dependent scalar round trips, 3.3 of the 14.9 us a wavefront of one column lives.  A wavefront
- * that lives on round trips moves its bytes in proportion to how few of them it needs, and beside another batch's DP kernels the
- * count kernel has fewer wavefronts resident, not slower ones (profiles/wave_stamps.py).  The loop over the columns is unrolled:
- * as a loop it kept lane-dependent values and constants in vector registers across the columns (46 instead of 30 registers). */
-template <bool SAME_THR, int WAVES, int UNROLL, int CPW>
-__global__ __launch_bounds__(64 * WAVES, 8) void lfq_count_lean_kernel(LfqCountArgs T, lfq_col_counts *__restrict__ out,
-                                                                    uint8_t *__restrict__ flags, int64_t c0, int64_t c1)
+/* One column per wavefront, LFQ_COUNT_WG_WAVES columns per workgroup: a 1024-thread workgroup retires sixteen columns at
+ * once -- a quarter of the workgroups of a 256-thread one to dispatch (C3: 2.42 against 2.46 ms per launch) and, for a caller
+ * that keeps several batches queued without a gate, four wave slots per SIMD freed at a time, room for any workgroup of the
+ * other batch's DP kernels (a 256-thread workgroup's single slots starve the 512-thread ones: profiles/NOTES.md). */
+#define LFQ_COUNT_WG_WAVES 16
+
+/* CPW columns per wavefront, one after the other (a workgroup: CPW runs of neighbouring columns), the headers of all of them
+ * requested at once when the wavefront starts -- scalar loads, they cost no vector register --, so that only the first column
+ * waits for its header: two dependent scalar round trips, 3.3 of the 14.9 us a wavefront of one column lives.  CPW is 1: with 2 / 4
+ * the kernel took 2.98 / 3.03 ms beside another batch's DP kernels against 2.88-2.93, alone 2.49 / 2.54 against 2.43-2.46 --
+ * workgroups that live twice as long cost more at the launch's edges than the header saves (profiles/NOTES.md).  The body is
+ * still spelled as the two unrolled loops it was measured with: written straight, the compiler orders the header's scalar
+ * loads differently (one instruction more), and this kernel is the step's dominant one. */
+template <bool SAME_THR>
+__global__ __launch_bounds__(64 * LFQ_COUNT_WG_WAVES, 8) void lfq_count_lean_kernel(LfqCountArgs T, lfq_col_counts *__restrict__ out,
+                                                                                     uint8_t *__restrict__ flags, int64_t c0, int64_t c1)
 {
+    constexpr int WAVES = LFQ_COUNT_WG_WAVES, CPW = 1;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t first = c0 + (int64_t)blockIdx.x * (WAVES * CPW) + wave;
     if (first >= c1) {
@@ -1259,27 +1268,22 @@ __global__ __launch_bounds__(64 * WAVES, 8) void lfq_count_lean_kernel(LfqCountA
     for (int j = 0; j < CPW; j++) {
         const int64_t col = first + (int64_t)j * WAVES;
         if (col < c1) {
-            /* (the lane index afresh for every column, from the execution mask: nothing lane-dependent, not even the index
-             * itself, stays in a vector register from one column to the next -- the kernel has to stay within 32) */
+            /* (the lane index afresh from the execution mask: nothing lane-dependent is live before the column starts -- the
+             * kernel has to stay within 32 vector registers) */
             int lane_j;
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_j));
-            lfq_count_column_lean<SAME_THR, UNROLL>(T, out, flags, col, lane_j, h[j]);
+            lfq_count_column_lean<SAME_THR>(T, out, flags, col, lane_j, h[j]);
         }
     }
 }
 
-/* one column per wavefront, WAVES columns per workgroup.  16 is the default (LFQ_COUNT_WAVES_PER_WG: 4, 8, 16): a 1024-thread
- * workgroup retires sixteen columns at once -- a quarter of the workgroups to dispatch (C3: 2.42 against 2.46 ms per
- * launch) and, for a caller that keeps several batches queued without a gate, four wave slots per SIMD freed at a time,
- * room for any workgroup of the other batch's DP kernels (a 256-thread workgroup's single slots starve the 512-thread
- * ones: profiles/NOTES.md). */
-template <bool PACKED, bool STRAND, bool SAME_THR, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void lfq_count_fast_kernel(LfqCountArgs T,
-                                                                    lfq_col_counts *__restrict__ out,
-                                                                    uint8_t *__restrict__ flags, int64_t c0, int64_t c1)
+template <bool PACKED, bool STRAND, bool SAME_THR>
+__global__ __launch_bounds__(64 * LFQ_COUNT_WG_WAVES) void lfq_count_fast_kernel(LfqCountArgs T,
+                                                                                  lfq_col_counts *__restrict__ out,
+                                                                                  uint8_t *__restrict__ flags, int64_t c0, int64_t c1)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t col = c0 + (int64_t)blockIdx.x * WAVES + wave;
+    const int64_t col = c0 + (int64_t)blockIdx.x * LFQ_COUNT_WG_WAVES + wave;
     if (col >= c1) {
         return;
     }
@@ -1665,7 +1669,7 @@ bool lfq_count_is_shallow(const LfqTracksDev &t, const LfqParams &p, int64_t max
 }
 
 int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqParams &p, const LfqLuts *d_luts,
-                     lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, int shallow_wgs_per_cu)
+                     lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, bool shallow_half_cu)
 {
     if (c1 <= c0) {
         return LFQ_OK;
@@ -1684,13 +1688,9 @@ int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqPar
             /* Unused dynamic LDS per workgroup = fewer workgroups per CU (33 / 37 KB each: four fit).  A context whose batches are
              * queued without a gate asks for two: its count kernel then leaves half of every SIMD's registers and wave slots to
              * the DP kernels of the batch before -- which otherwise start only where a count workgroup retires -- and is itself
-             * no slower (C2, four batches queued: 0.66 -> 0.56-0.59 ms per step, count kernel 0.33-0.38 ms either way).
-             * LFQ_COUNT_SHALLOW_LDS_PAD: the bytes directly (experiments). */
-            unsigned lds_pad = (unsigned)kn.count_shallow_lds_pad;
+             * no slower (C2, four batches queued: 0.66 -> 0.56-0.59 ms per step, count kernel 0.33-0.38 ms either way). */
             /* (not where four lanes share a column -- depth <= 320 --: 3.75 M x 200 0.86 ms per step with four workgroups, 1.14 with two) */
-            if (lds_pad == 0 && shallow_wgs_per_cu >= 1 && shallow_wgs_per_cu <= 3 && lpg > 4) {
-                lds_pad = shallow_wgs_per_cu == 1 ? 60000u : shallow_wgs_per_cu == 2 ? 44000u : 17000u;
-            }
+            const unsigned lds_pad = (shallow_half_cu && lpg > 4) ? 44000u : 0u;
 #define LFQ_LAUNCH_SHALLOW(ST)                                                                                       \
             do {                                                                                                     \
                 if (lpg == 4) hipLaunchKernelGGL((lfq_count_shallow_kernel<ST, 4>), dim3(nb), dim3(256), lds_pad, (hipStream_t)stream, t, p, d_counts, d_flags, c0, c1, rounds); \
@@ -1725,7 +1725,6 @@ int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqPar
         return LFQ_OK;
     }
     const bool strand = !p.lazy_strand || p.general;       /* the general path evaluates every observation anyway */
-    const LfqKnobs &kn = lfq_knobs();
     if (!p.general && !p.detlim_af) {
         /* default filters: the lean kernel, by layout x strand counts x "one threshold" */
         const bool same_thr = p.min_alt_bq4 == p.min_bq4;
@@ -1741,62 +1740,25 @@ int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqPar
         ca.min_cov = p.min_cov;
         ca.pad_ = 0;
         const int variant = (t.nt_packed ? 4 : 0) | (strand ? 2 : 0) | (same_thr ? 1 : 0);
-        const int wpw = kn.count_waves_per_wg;
-        const int cpw = kn.count_cols_per_wave >= 4 ? 4 : kn.count_cols_per_wave >= 2 ? 2 : 1;
-        const unsigned blocks = (unsigned)((c1 - c0 + (int64_t)wpw * cpw - 1) / ((int64_t)wpw * cpw));
+        const unsigned blocks = (unsigned)((c1 - c0 + LFQ_COUNT_WG_WAVES - 1) / LFQ_COUNT_WG_WAVES);
+        const dim3 wg(64 * LFQ_COUNT_WG_WAVES);
         if (t.nt_packed && !strand) {
             /* lazy record counts on the packed layout: the decision counts only */
-            /* (LFQ_COUNT_LEAN_LDS_PAD: unused dynamic LDS per workgroup -- the kernel has no LDS of its own, so this alone says
-             * how many workgroups a CU holds and how many wave slots stay free for another batch's DP kernels) */
-            const unsigned lean_pad = (unsigned)kn.count_lean_lds_pad;
-#define LFQ_LAUNCH_LC(SM, W, U, CP)                                                                                  \
-    hipLaunchKernelGGL((lfq_count_lean_kernel<SM, W, U, CP>), dim3(blocks), dim3(64 * W), lean_pad, (hipStream_t)stream, ca, d_counts, \
-                       d_flags, c0, c1)
-#define LFQ_LAUNCH_L(SM, W, U)                                                                                       \
-    do {                                                                                                             \
-        if (cpw == 4) LFQ_LAUNCH_LC(SM, W, U, 4);                                                                    \
-        else if (cpw == 2) LFQ_LAUNCH_LC(SM, W, U, 2);                                                               \
-        else LFQ_LAUNCH_LC(SM, W, U, 1);                                                                             \
-    } while (0)
-#define LFQ_LAUNCH_LU(SM, W)                                                                                         \
-    do {                                                                                                             \
-        if (kn.count_ahead_deep == 4) LFQ_LAUNCH_L(SM, W, 4);                                                        \
-        else if (kn.count_ahead_deep == 3) LFQ_LAUNCH_L(SM, W, 3);                                                   \
-        else LFQ_LAUNCH_L(SM, W, 2);                                                                                 \
-    } while (0)
-#define LFQ_LAUNCH_LW(SM)                                                                                            \
-    do {                                                                                                             \
-        if (wpw == 16) LFQ_LAUNCH_LU(SM, 16);                                                                        \
-        else if (wpw == 12) LFQ_LAUNCH_LU(SM, 12);                                                                   \
-        else if (wpw == 8) LFQ_LAUNCH_LU(SM, 8);                                                                     \
-        else LFQ_LAUNCH_LU(SM, 4);                                                                                   \
-    } while (0)
-            if (same_thr) LFQ_LAUNCH_LW(true); else LFQ_LAUNCH_LW(false);
-#undef LFQ_LAUNCH_LW
-#undef LFQ_LAUNCH_LU
-#undef LFQ_LAUNCH_L
-#undef LFQ_LAUNCH_LC
+            if (same_thr) hipLaunchKernelGGL((lfq_count_lean_kernel<true>), dim3(blocks), wg, 0, (hipStream_t)stream, ca, d_counts, d_flags, c0, c1);
+            else hipLaunchKernelGGL((lfq_count_lean_kernel<false>), dim3(blocks), wg, 0, (hipStream_t)stream, ca, d_counts, d_flags, c0, c1);
             LFQ_HIP_TRY(hipGetLastError());
             return LFQ_OK;
         }
-#define LFQ_LAUNCH_F(PK, ST, SM, W)                                                                                  \
-    hipLaunchKernelGGL((lfq_count_fast_kernel<PK, ST, SM, W>), dim3((unsigned)((c1 - c0 + W - 1) / W)), dim3(64 * W), 0,     \
-                       (hipStream_t)stream, ca, d_counts, d_flags, c0, c1)
-#define LFQ_LAUNCH_FW(PK, ST, SM)                                                                                    \
-    do {                                                                                                             \
-        if (wpw >= 12) LFQ_LAUNCH_F(PK, ST, SM, 16);                                                                 \
-        else if (wpw == 8) LFQ_LAUNCH_F(PK, ST, SM, 8);                                                              \
-        else LFQ_LAUNCH_F(PK, ST, SM, 4);                                                                            \
-    } while (0)
+#define LFQ_LAUNCH_F(PK, ST, SM)                                                                                     \
+    hipLaunchKernelGGL((lfq_count_fast_kernel<PK, ST, SM>), dim3(blocks), wg, 0, (hipStream_t)stream, ca, d_counts, d_flags, c0, c1)
         switch (variant) {
-        case 0: LFQ_LAUNCH_FW(false, false, false); break;
-        case 1: LFQ_LAUNCH_FW(false, false, true); break;
-        case 2: LFQ_LAUNCH_FW(false, true, false); break;
-        case 3: LFQ_LAUNCH_FW(false, true, true); break;
-        case 6: LFQ_LAUNCH_FW(true, true, false); break;
-        default: LFQ_LAUNCH_FW(true, true, true); break;
+        case 0: LFQ_LAUNCH_F(false, false, false); break;
+        case 1: LFQ_LAUNCH_F(false, false, true); break;
+        case 2: LFQ_LAUNCH_F(false, true, false); break;
+        case 3: LFQ_LAUNCH_F(false, true, true); break;
+        case 6: LFQ_LAUNCH_F(true, true, false); break;
+        default: LFQ_LAUNCH_F(true, true, true); break;
         }
-#undef LFQ_LAUNCH_FW
 #undef LFQ_LAUNCH_F
         LFQ_HIP_TRY(hipGetLastError());
         return LFQ_OK;

@@ -1071,16 +1071,11 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
         const int64_t waves_wide = (n_wide + 63) / 64, waves_b8 = (n_band8 + 63) / 64;
         const bool side_ok = n_narrow > 0 && c->side[0] != nullptr && c->side[1] != nullptr && !lfq_knobs().single_stream;
         const bool beside = side_ok && waves_wide + waves_b8 > 0 && waves_wide + waves_b8 < waves / 4;
-        /* The narrow-band reads with an indel operation (the IDAQ instantiation: 4 % of the bench's reads) as well, when every
-         * group has scratch slots of its own: behind the plain launches on the same stream they were a launch of a third of
-         * a round with the machine to itself (0.8 ms per 479 K reads); beside them they fill the plain launch's last round. */
-        const int64_t waves_i = (n_narrow - n_plain + 63) / 64;
-        const bool beside_i = side_ok && lfq_knobs().baq_idaq_beside && n_plain > 0 && waves_i > 0 && waves_i < waves / 4
-                              && (n_plain + 63) / 64 + waves_i + (beside ? waves_wide + waves_b8 : 0) <= waves;
-        /* (they share the band-8 launch's stream: the first side stream tends to be multiplexed onto the hardware queue of
-         * c->stream, where a launch waits for the one before it whatever stream it came from) */
-        const bool use_side0 = beside && n_wide > 0, use_side1 = (beside && n_band8 > 0) || beside_i;
-        int64_t waves_n = waves - (beside ? waves_wide + waves_b8 : 0) - (beside_i ? waves_i : 0);      /* slots of a narrow launch */
+        /* (The narrow-band reads with an indel operation -- the IDAQ instantiation: 4 % of the bench's reads -- stay behind the
+         * plain launches on c->stream: beside them a lone BAQ + IDAQ call went 6.2 -> 5.3 ms per 400 K reads, the reads -> VCF
+         * chain 37.7 -> 39.0 ms per region.) */
+        const bool use_side0 = beside && n_wide > 0, use_side1 = beside && n_band8 > 0;
+        int64_t waves_n = waves - (beside ? waves_wide + waves_b8 : 0);      /* slots of a narrow launch */
         const int64_t round = (int64_t)c->n_cu * 4;
         if ((n_narrow + 63) / 64 > waves_n && waves_n > round) {       /* more than one launch: whole rounds each */
             waves_n = waves_n / round * round;
@@ -1154,8 +1149,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             rc = readset_upload_wait_inputs(rs, {c->stream, c->side[0], c->side[1]});
         }
         if (use_side0 || use_side1) {
-            /* wide-band, band-8 and (beside_i) the narrow-band reads with indels on the side streams, beside the plain narrow-band
-             * launches; c->stream ends after them */
+            /* wide-band and band-8 reads on the side streams, beside the plain narrow-band launches; c->stream ends after them */
             if (rc == LFQ_OK && use_side0 && hipStreamWaitEvent(c->side[0], c->ev_join[0], 0) != hipSuccess) {
                 rc = LFQ_ERR_HIP;
             }
@@ -1167,12 +1161,6 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             if (rc == LFQ_OK && use_side1 && hipStreamWaitEvent(c->side[1], c->ev_join[0], 0) != hipSuccess) {
                 rc = LFQ_ERR_HIP;
             }
-            if (rc == LFQ_OK && beside_i) {
-                LfqBaqArgs Ai = at_slot(waves_n + (beside ? waves_b8 + waves_wide : 0));
-                Ai.first_read = (int32_t)n_plain;
-                rc = lfq_launch_baq(Ai, n_narrow - n_plain, 1, c->side[1]);
-                c->baq_launches++;
-            }
             if (rc == LFQ_OK && beside && n_band8 > 0) {
                 LfqBaqArgs Ab = at_slot(waves_n);
                 Ab.first_read = (int32_t)n_narrow;
@@ -1183,7 +1171,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
                 rc = LFQ_ERR_HIP;
             }
         }
-        for (int64_t first = n_plain; rc == LFQ_OK && !beside_i && first < n_narrow; first += waves_n * 64) {
+        for (int64_t first = n_plain; rc == LFQ_OK && first < n_narrow; first += waves_n * 64) {
             A.first_read = (int32_t)first;
             rc = lfq_launch_baq(A, std::min<int64_t>(waves_n * 64, n_narrow - first), 1, c->stream);
             c->baq_launches++;

@@ -1,8 +1,11 @@
-"""-m gpu: the code paths that only run under an environment knob (fallbacks for inputs the default route cannot take:
-no pool space, unsorted reads, wide bands, shallow / deep launch shapes; the measured-and-rejected A/B paths of rounds
-1-3 were deleted in round 4, profiles/NOTES.md) get the parity tests of their area, each in a process of its own with the
-knob set -- so that nothing that can be selected at run time is untested.  The knobs are read once per process
-(lfq_knobs(), lfq_internal.h); DESIGN.md lists them.
+"""-m gpu: the code paths that only run under an environment knob get the parity tests of their area, each in a process of
+its own with the knob set -- so that nothing that can be selected at run time is untested.  Every knob here forces a path the
+release library takes by itself for some input (no pool space, K >= 32, unsorted reads, wide bands, shallow / deep launch
+shapes, a context with LFQ_GATE_NONE); the measured-and-rejected A/B variants that no input could reach -- other workgroup
+shapes of the count kernels, LDS padding, the stream plan of round 4 -- are deleted with their knobs (profiles/NOTES.md).  The
+two-workgroups-per-CU launch of the shared-wavefront count kernel, which an ungated context makes, is covered where it
+happens: test_gpu_stability.py::test_submit_collect_dense_counts_without_strands.  The knobs are read once per process
+(lfq_knobs(), lfq_internal.h); DESIGN.md section 7 says which build reads which.
 
 Round 6: the release library reads ten variables, none of which changes a result; every other knob exists only in the tuning
 build lofreq_amd/liblofreq_amd_tune.so (the same objects, lfq_host.cpp compiled under -DLFQ_TUNE), which the child processes
@@ -35,15 +38,9 @@ CASES = [
     ("LFQ_COUNT_LPG4_BELOW=100000", DP),     # shared-wavefront count kernel: four lanes per column whatever the depth
     ("LFQ_COUNT_LPG8_BELOW=100000", DP),     # ... eight (and four for the shallowest batches)
     ("LFQ_COUNT_LPG4_BELOW=0", DP),          # ... never four
-    ("LFQ_COUNT_WAVES_PER_WG=4 LFQ_COUNT_MULTI_BELOW=0", DP),    # the lean count kernel with 4 columns per workgroup (default 16) ...
-    ("LFQ_COUNT_WAVES_PER_WG=8 LFQ_COUNT_MULTI_BELOW=0", DP),    # ... and 8, on every batch
     ("LFQ_SEG_MAX=2", DP),                   # a big column in two row segments, a mid-class column in one piece after its first stretch (what a context with LFQ_GATE_NONE runs)
     ("LFQ_SEG_MAX_MID=3 LFQ_SEG_MAX_BIG=4", DP),   # ... other segment counts per class
     ("LFQ_BIG_ON_SIDE=1", DP),               # the unsplit big columns behind the big chain (what a context with LFQ_GATE_NONE runs)
-    ("LFQ_JOIN_ON_SIDE=0 LFQ_TAIL_LIGHT=0 LFQ_HEAVY_AFTER_SCREEN=0", DP),   # the stream plan of round 4: join on the light chain's stream, tail event behind the retry kernel
-    ("LFQ_TAIL_LIGHT=2", DP),                # tail event of the light chain behind the scan
-    ("LFQ_COUNT_SHALLOW_LDS_PAD=44000", DP), # shared-wavefront count kernel with two workgroups per CU (what a context with LFQ_GATE_NONE launches)
-    ("LFQ_COUNT_LEAN_LDS_PAD=54000 LFQ_COUNT_WAVES_PER_WG=8 LFQ_COUNT_AHEAD_DEEP=4 LFQ_COUNT_MULTI_BELOW=0", DP),    # lean count kernel capped to three workgroups per CU
     ("LFQ_PRIVATE_STREAM=1", DP),            # every context with a launch stream of its own (lfq_set_private_stream) ...
     ("LFQ_PRIVATE_STREAM=1", CHAIN),         # ... on the read-set chain as well
     ("LFQ_PILEUP_TILES=0", PLP),             # a wavefront per position instead of tiles of 64 positions

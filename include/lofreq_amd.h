@@ -40,7 +40,8 @@ extern "C" {
 /* 4: lfq_set_batch_gate, lfq_last_baq_times; lfq_call_snvs_collect refuses h_counts for a batch whose dense entries are sparse. */
 /* 5: lfq_set_private_stream. */
 /* 7: lfq_set_max_depth, lfq_readset_kept_reads. */
-#define LFQ_ABI_VERSION 7
+/* 8: lfq_viterbi_batch, lfq_last_viterbi_times. */
+#define LFQ_ABI_VERSION 8
 
 typedef enum lfq_status {
     LFQ_OK = 0,
@@ -337,6 +338,57 @@ typedef struct lfq_baq_reads {
 int lfq_baq_batch(lfq_ctx *ctx, const lfq_baq_reads *reads, int baq_extended, uint8_t *lb_out);
 int lfq_baq_idaq_batch(lfq_ctx *ctx, const lfq_baq_reads *reads, int baq_extended, uint8_t *lb_out,
                        uint8_t *ai_out, uint8_t *ad_out, uint8_t *tag_flags);
+
+/* --- `lofreq viterbi`: the realignment of the reads with an indel, before alnqual ----------------
+ * fetch_func (lofreq_viterbi.c:107-345) + viterbi + left_align_indels (viterbi.c:99-330, 48-96) for a batch of reads of ONE
+ * contig, in the read layout of the BAQ call.  The caller skips unmapped reads (:148-151).  Per read, in this order:
+ *   1. Left as it is, with the status that says why: an H operation or an operation other than M = X I D S anywhere in the
+ *      CIGAR (:188-192, 208-212: the whole read, whatever came before) -> LFQ_VIT_SKIPPED_OP; no I / D operation (:216) ->
+ *      LFQ_VIT_NO_INDEL; every query base has quality 2 (:221; also a read without query bases) -> LFQ_VIT_ALL_Q2.  The hidden
+ *      --reclip option is not implemented.
+ *   2. Query = bases and qualities of the M = X I operations (soft clips dropped, :178-213), compared AS LETTERS
+ *      (LFQ_SEQ_LETTERS[code], htslib's seq_nt16_str) with the upper-cased reference (:161): an N in the read equals an N in
+ *      the reference.
+ *   3. q2def = def_qual (-q), or when that is negative int_median of the query's qualities other than 2 (utils.c:436-457: an
+ *      even count gives (a + b) / 2.0 truncated); it stands in for every quality of 2 (viterbi.c:188-192).
+ *   4. Window [max(0, pos - 10), min(ref_len, x + 10)), x = pos + the reference bases the CIGAR consumes (:250-259).  The
+ *      reference's stack buffer for it (:251) is not a limit here.
+ *   5. viterbi(): L = window length + 1 PER READ in the nine transition constants; bp = pow(10, -0.1 q), ep_match =
+ *      log10(1 - bp), ep_match_not = log10(bp / 3.), ep_ins = log10(.25); borders (double)INT_MIN, not -inf; argmax_d takes the
+ *      FIRST maximum (utils.c:87-98) of the terms in their written order (S M I D / S M I / M D); termination over M then I of
+ *      the last query row with `>`; the trace-back stops at a pointer S or at i == 0 || k == 0 and returns that k.  The tables
+ *      are computed on the host with the host's libm; the device adds and compares only, so the result is the reference's bit
+ *      for bit.
+ *   6. left_align_indels on the traced columns, then the run-length CIGAR of M / I / D with the original leading / trailing S
+ *      operation put back (:270-304); = and X come back as M.
+ *   7. pos = max(0, pos - 10) + k (:316-321).
+ * Qualities above 93 in a read that is realigned, def_qual above 93 and a realigned read with pos < 0 are LFQ_ERR_INVALID.
+ * What the caller still does: delete the NM / MC / MD / AS tags of EVERY read unless -k (:119-146), write
+ * pos and CIGAR back, and sort -- the output is no longer coordinate-sorted (:362).
+ * The result belongs to the context and is valid until its next lfq_viterbi_batch call.  cigar[cigar_off[r] .. cigar_off[r + 1])
+ * is read r's CIGAR in BAM encoding -- the input's for a read left as it is, so that the arrays can be taken whole. */
+#define LFQ_VIT_NO_INDEL 0
+#define LFQ_VIT_SKIPPED_OP 1
+#define LFQ_VIT_ALL_Q2 2
+#define LFQ_VIT_REALIGNED 3
+#define LFQ_VIT_STATUS_MASK 7
+#define LFQ_VIT_CHANGED 8          /* bit: position or CIGAR differ from the input (only ever set with LFQ_VIT_REALIGNED) */
+typedef struct lfq_viterbi_result {
+    int64_t n_reads;
+    const int32_t *pos;            /* [n] */
+    const uint8_t *status;         /* [n] LFQ_VIT_* */
+    const int64_t *cigar_off;      /* [n+1] */
+    const uint32_t *cigar;
+} lfq_viterbi_result;
+int lfq_viterbi_batch(lfq_ctx *ctx, const lfq_baq_reads *reads, int def_qual, const lfq_viterbi_result **out);
+/* the realignment kernels of the context's last lfq_viterbi_batch call on the device's clock (first launch -> last done),
+ * their number (the batch is cut by the scratch budget of the BAQ step), the call's reads and how many were realigned */
+typedef struct lfq_viterbi_times {
+    float ms_kernels;
+    int32_t n_launches;
+    int64_t n_reads, n_realigned;
+} lfq_viterbi_times;
+int lfq_last_viterbi_times(lfq_ctx *ctx, lfq_viterbi_times *t);
 
 /* --- device-side pileup: reads -> the packed SNV tracks of a region -------------------------
  * What compile_plp_col (plp.c:797-1017) builds per column, for all columns of [region_begin, region_end) at once,

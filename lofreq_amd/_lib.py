@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LFQ_AMD_LIB") or os.path.join(_HERE, "liblofreq_amd.so")   # LFQ_AMD_LIB: another build of the same library (A/B runs)
 
 LFQ_OK = 0
-LFQ_ABI_VERSION = 7      # include/lofreq_amd.h; load() refuses a library built from another header
+LFQ_ABI_VERSION = 8     # include/lofreq_amd.h; load() refuses a library built from another header
 LFQ_ERR_CAPACITY = -4
 LFQ_USE_BAQ, LFQ_USE_MQ, LFQ_USE_SQ, LFQ_USE_IDAQ = 1, 2, 4, 8
 LFQ_PV_NONE, LFQ_PV_LOG, LFQ_PV_LOG_FECLAMP, LFQ_PV_UNDERFLOW = 0, 1, 2, 3
@@ -66,6 +66,19 @@ class DpWork(C.Structure):
 class BaqReads(C.Structure):
     _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in (
         "pos", "cigar_off", "cigar", "seq_off", "seq", "qual", "ref")] + [("ref_len", C.c_int64)]
+
+
+LFQ_VIT_NO_INDEL, LFQ_VIT_SKIPPED_OP, LFQ_VIT_ALL_Q2, LFQ_VIT_REALIGNED = 0, 1, 2, 3
+LFQ_VIT_STATUS_MASK, LFQ_VIT_CHANGED = 7, 8
+
+
+class ViterbiResult(C.Structure):
+    """lfq_viterbi_result: owned by the context, valid until its next lfq_viterbi_batch call"""
+    _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in ("pos", "status", "cigar_off", "cigar")]
+
+
+class ViterbiTimes(C.Structure):
+    _fields_ = [("ms_kernels", C.c_float), ("n_launches", C.c_int32), ("n_reads", C.c_int64), ("n_realigned", C.c_int64)]
 
 
 class PileupReads(C.Structure):
@@ -132,7 +145,7 @@ EXPORTS = [
     "lfq_set_pileup_nt_packed", "lfq_set_pileup_unsorted", "lfq_set_baq_hmm_params", "lfq_pack_nt_track", "lfq_shard_allgather", "lfq_shard_set_host_allgather", "lfq_shard_gather_start", "lfq_shard_gather_wait", "lfq_shard_shm_open", "lfq_shard_shm_unlink", "lfq_shard_shm_close", "lfq_call_snvs_collect_pvals", "lfq_device_count", "lfq_pick_device", "lfq_host_alloc", "lfq_host_free",
     "lfq_readset_create", "lfq_readset_destroy", "lfq_readset_baq", "lfq_readset_source_qual",
     "lfq_readset_pileup_snv", "lfq_readset_pileup_indels", "lfq_readset_fetch_tags",
-    "lfq_set_max_depth", "lfq_readset_kept_reads",
+    "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
 ]
@@ -232,6 +245,8 @@ def load():
     L.lfq_filter_indel_records.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp]
     L.lfq_baq_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, vp]
     L.lfq_baq_idaq_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, vp, vp, vp, vp]
+    L.lfq_viterbi_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, C.POINTER(C.POINTER(ViterbiResult))]
+    L.lfq_last_viterbi_times.argtypes = [vp, C.POINTER(ViterbiTimes)]
     L.lfq_pileup_snv_tracks.argtypes = [vp, C.POINTER(PileupReads), C.c_int64, C.c_int64, C.c_int, C.POINTER(Tracks), vp]
     L.lfq_pileup_indel_columns.argtypes = [vp, C.POINTER(PileupReads), C.POINTER(PileupIndelTags), C.c_int64, C.c_int64,
                                            C.c_int, C.POINTER(C.POINTER(IndelColumnsC)), vp]

@@ -375,6 +375,7 @@ struct lfq_ctx {
     int cur_indel_mode;
     int sb_pending;                  /* strand-bias precomputes of this context not finished yet (under lm) */
     struct { void *p; size_t cap; int used; } pin_pool[LFQ_PIN_SLOTS];   /* LfqPin: pinned host temporaries */
+    struct LfqViterbiState *vit;     /* lfq_viterbi_batch: its result and device buffers (lfq_viterbi.hip; created on first use) */
 };
 
 template <typename T>
@@ -440,6 +441,7 @@ struct LfqPin {
 
 /* ---- internal functions that cross file boundaries (lfq_api.hip) ---- */
 int lfq_make_params(const lfq_conf *conf, const lfq_tracks *tr, LfqParams *P, bool indel_mode);
+void lfq_viterbi_release(lfq_ctx *c);      /* lfq_viterbi.hip: what lfq_destroy frees of lfq_ctx::vit */
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

@@ -41,7 +41,8 @@ extern "C" {
 /* 5: lfq_set_private_stream. */
 /* 7: lfq_set_max_depth, lfq_readset_kept_reads. */
 /* 8: lfq_viterbi_batch, lfq_last_viterbi_times. */
-#define LFQ_ABI_VERSION 8
+/* 9: lfq_indelqual_batch, lfq_readset_indelqual, lfq_readset_fetch_indelquals, lfq_last_indelqual_times. */
+#define LFQ_ABI_VERSION 9
 
 typedef enum lfq_status {
     LFQ_OK = 0,
@@ -390,6 +391,41 @@ typedef struct lfq_viterbi_times {
 } lfq_viterbi_times;
 int lfq_last_viterbi_times(lfq_ctx *ctx, lfq_viterbi_times *t);
 
+/* --- `lofreq indelqual`: the BI / BD per-base indel qualities, between alnqual and call -------------
+ * What `--call-indels` reads for every pileup entry (plp.c:1062) and a BAM that has not been through GATK BQSR lacks.  A batch
+ * of reads of ONE contig in the read layout of the BAQ call; reads->seq / reads->qual are not read and may be NULL.  bi_out /
+ * bd_out get the tag bytes (quality + 33) in the seq_off layout: what lfq_pileup_indel_tags.bi / .bd take.
+ *   LFQ_IDQ_UNIFORM (-u INT[,INT]; add_uniform / uniform_fetch_func, lofreq_indelqual.c:69-104, 218-258): every base of every
+ *      read gets ENCODE_Q(ins_qual + 33) in BI and ENCODE_Q(del_qual + 33) in BD -- a byte below '!' becomes '!', one above '~'
+ *      becomes '~' (:66).  Positions and CIGARs are not looked at, as in the reference.
+ *   LFQ_IDQ_DINDEL (--dindel -f ref.fa; dindel_fetch_func, :136-215): the contig is upper-cased (:155) and find_homopolymers
+ *      (:109-133) gives every position a count: the run length at the FIRST base of a homopolymer run, 1 everywhere else (runs
+ *      of N count).  The CIGAR walk (:173-198) gives a base aligned to reference position x by an M / = / X operation '!' if
+ *      x > ref_len - 2, else with c = the count of position x + 1, '!' if c > 18, else "!MMMLKEC@=<;:988776"[c] (DINDELQ, :42);
+ *      D advances x; every base of an I or S operation gets '!'; H does nothing.  BI and BD get the same string (:205, 211);
+ *      ins_qual / del_qual are not used.  The caller leaves out the reads the reference writes unchanged (UNMAP | SECONDARY |
+ *      QCFAIL | DUP, :144).  LFQ_ERR_INVALID for what the reference cannot do: any other operation (N, P, ...: fatal, :195), a
+ *      CIGAR whose query length differs from the read's seq_off span (the reference overruns its stack array, :168), pos < 0.
+ * An unknown mode is LFQ_ERR_INVALID; an empty batch launches nothing.
+ * What the caller still does: the flag mask, deleting old BI / BD tags and appending the new ones as Z tags
+ * (l_qseq bytes + NUL), and "Do not realign your BAM file afterwards!" (:332) -- viterbi comes BEFORE this step. */
+#define LFQ_IDQ_UNIFORM 1
+#define LFQ_IDQ_DINDEL 2
+typedef struct lfq_indelqual_conf {
+    int32_t mode;                  /* LFQ_IDQ_UNIFORM or LFQ_IDQ_DINDEL */
+    int32_t ins_qual, del_qual;    /* uniform mode: the two values of -u (one value given: both the same) */
+} lfq_indelqual_conf;
+int lfq_indelqual_batch(lfq_ctx *ctx, const lfq_baq_reads *reads, const lfq_indelqual_conf *conf, uint8_t *bi_out,
+                        uint8_t *bd_out);
+/* the kernels of the context's last lfq_indelqual_batch / lfq_readset_indelqual call on the device's clock, their number, the
+ * call's reads and bases */
+typedef struct lfq_indelqual_times {
+    float ms_kernels;
+    int32_t n_launches;
+    int64_t n_reads, n_bases;
+} lfq_indelqual_times;
+int lfq_last_indelqual_times(lfq_ctx *ctx, lfq_indelqual_times *t);
+
 /* --- device-side pileup: reads -> the packed SNV tracks of a region -------------------------
  * What compile_plp_col (plp.c:797-1017) builds per column, for all columns of [region_begin, region_end) at once,
  * directly in HBM in the lfq_tracks layout.  The host has done what mplp_func does per read (plp.c:600-700): flag /
@@ -487,6 +523,17 @@ int lfq_readset_kept_reads(lfq_ctx *ctx, lfq_readset *rs, uint8_t *keep_out_or_n
 /* copies of the resident tags for writing them back to the BAM; NULL = not wanted.  tag_flags as lfq_baq_idaq_batch */
 int lfq_readset_fetch_tags(lfq_ctx *ctx, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out,
                            uint8_t *tag_flags);
+
+/* `lofreq indelqual` as a step of the read set: BI / BD of every read computed on the device copy and kept there, for a read
+ * set created WITHOUT them (arrays the caller did upload are superseded: "Both will overwrite any existing values",
+ * lofreq_indelqual.c:331).  Every read then counts as having both tags, and lfq_readset_pileup_indels reads them from the
+ * device; the one base per indel event its host side needs is evaluated from the contig and the CIGAR, so that no per-base
+ * array crosses the link in either direction.  In Dindel mode BI and BD are one array on the device.  Any time after
+ * lfq_readset_create and before lfq_readset_pileup_indels; beside a BAQ step that is still running it takes another stream.
+ * lfq_indelqual_batch is this step and the fetch below around a temporary read set. */
+int lfq_readset_indelqual(lfq_ctx *ctx, lfq_readset *rs, const lfq_indelqual_conf *conf);
+/* copies of the resident BI / BD bytes for writing them to the BAM; NULL = not wanted.  LFQ_ERR_INVALID before the step ran */
+int lfq_readset_fetch_indelquals(lfq_ctx *ctx, lfq_readset *rs, uint8_t *bi_out, uint8_t *bd_out);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

@@ -71,6 +71,7 @@ struct lfq_region {
     int64_t wo_idaq;
     int64_t max_depth;              /* lfq_region_set_max_depth; LFQ_NO_MAX_DEPTH by default */
     int max_depth_set;              /* lfq_region_set_max_depth was called: close takes the cap off the context again */
+    lfq_indelqual_conf idq;         /* lfq_region_set_indelqual; mode 0 = off (the default) */
     /* outputs, grown on demand */
     int64_t *col_pos_i, pos_cap;
     lfq_snv_record *srec;
@@ -158,6 +159,19 @@ int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth)
         r->max_depth_set = 1;
     }
     return rc;
+}
+
+int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_null)
+{
+    if (!r || r->open || r->buf[0].started || r->buf[1].started
+        || (conf_or_null && conf_or_null->mode != LFQ_IDQ_UNIFORM && conf_or_null->mode != LFQ_IDQ_DINDEL)) {
+        return LFQ_ERR_INVALID;
+    }
+    memset(&r->idq, 0, sizeof(r->idq));
+    if (conf_or_null) {
+        r->idq = *conf_or_null;
+    }
+    return LFQ_OK;
 }
 
 int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, int64_t ref_len, int64_t beg0, int64_t end0)
@@ -296,6 +310,15 @@ static int region_start(lfq_region *r, reg_buf *b)
             return rc;
         }
     }
+    if (r->idq.mode && !b->any_bi && !b->any_bd) {
+        /* `lofreq indelqual` for a region whose reads came without BI / BD: computed on the device copy, beside the BAQ kernels */
+        rc = lfq_readset_indelqual(r->ctx, b->rs, &r->idq);
+        if (rc != LFQ_OK) {
+            lfq_readset_destroy(b->rs);
+            b->rs = NULL;
+            return rc;
+        }
+    }
     if (r->o.use_sq) {                                                  /* plp.c:727-735; DEFAULT_MIN_BQ = 6 */
         rc = lfq_readset_source_qual(r->ctx, b->rs, r->o.def_nm_q, 6, NULL, NULL);
         if (rc != LFQ_OK) {
@@ -369,7 +392,7 @@ static int region_finish(lfq_region *r, reg_buf *b)
     rc = grow_out(r, b->end - b->beg + 1);
     /* the consensus-indel gate of call_vars (:928-931) needs the indel fields even when no indel is called -- but
      * without BI / BD no event can win the consensus (its quality sum is 0, plp.c:1236-1270) */
-    if (rc == LFQ_OK && (r->o.call_indels || b->any_bi || b->any_bd)) {
+    if (rc == LFQ_OK && (r->o.call_indels || b->any_bi || b->any_bd || r->idq.mode)) {
         rc = lfq_readset_pileup_indels(r->ctx, b->rs, b->beg, b->end, r->o.min_plp_idq, &cols, r->col_pos_i);
         if (rc == LFQ_OK && !r->o.only_indels) {
             rc = region_snv_tracks(r, b);       /* its scatter pass runs under the host part of the indel tests below */

@@ -59,6 +59,13 @@ int lfq_region_open(lfq_region **out, lfq_ctx *ctx, lfq_conf *conf, const lfq_re
  * lfq_region_close takes it off again (LFQ_NO_MAX_DEPTH) if this call set it.  A negative `lofreq call -d` keeps only the first
  * read of each start position in htslib, which is max_depth = 0 here: map it, do not pass -1 through. */
 int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth);
+/* `lofreq indelqual` inside the binding (opt-in; default off): the reads of a region in which NO read came with a BI or BD tag
+ * (bi == bd == NULL in lfq_region_add_read) get their indel qualities from lfq_readset_indelqual, between the BAQ step and the
+ * indel pileup -- conf->mode LFQ_IDQ_DINDEL (`--dindel`, from the region's contig) or LFQ_IDQ_UNIFORM (`-u ins_qual,del_qual`).
+ * A region with tagged reads is taken as it is.  NULL switches it off again.  Same calling rule as lfq_region_set_max_depth:
+ * after lfq_region_open, before the first lfq_region_begin.  Not a field of lfq_region_opts, whose size callers rely on.
+ * Dindel mode fails a region (LFQ_ERR_INVALID from lfq_region_end) whose reads hold an N or P operation, as the command does. */
+int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_null);
 /* `ref`: the contig, upper-cased (plp.c:652), valid until the NEXT lfq_region_end / lfq_region_close has returned */
 int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, int64_t ref_len, int64_t beg0, int64_t end0);
 /* one BAM record that passed the flag filters of plp.c:608-632, in file order (position-sorted).  The fields are

@@ -469,7 +469,7 @@ void lfq_destroy(lfq_ctx *c)
         for (int i = 0; i < 5; i++) {
             if (c->d_tmp[i]) (void)hipFree(c->d_tmp[i]);
         }
-        for (int k = 0; k < 6; k++) {                   /* 4 = LFQ_RSC_PINFL: pinned host memory */
+        for (int k = 0; k < 7; k++) {                   /* 4 = LFQ_RSC_PINFL: pinned host memory */
             if (c->rs_cache[k].p) (void)(k == 4 ? hipHostFree(c->rs_cache[k].p) : hipFree(c->rs_cache[k].p));
         }
         if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
@@ -484,6 +484,8 @@ void lfq_destroy(lfq_ctx *c)
         if (c->d_detlim) (void)hipFree(c->d_detlim);
         if (c->ev_baq_t[0]) (void)hipEventDestroy(c->ev_baq_t[0]);
         if (c->ev_baq_t[1]) (void)hipEventDestroy(c->ev_baq_t[1]);
+        if (c->ev_idq_t[0]) (void)hipEventDestroy(c->ev_idq_t[0]);
+        if (c->ev_idq_t[1]) (void)hipEventDestroy(c->ev_idq_t[1]);
         if (c->d_baq_scr) (void)hipFree(c->d_baq_scr);
         if (c->d_baq_expect) (void)hipFree(c->d_baq_expect);
         if (c->d_baq_tmp8) (void)hipFree(c->d_baq_tmp8);

@@ -319,7 +319,7 @@ struct lfq_ctx {
     /* the allocations of the read set destroyed last (reads, tags, read ends, tag flags, pinned flags): the next
      * lfq_readset_create / _baq takes them over when they are large enough -- a worker goes from region to region, and
      * hipMalloc + hipFree of 2 GB per region are milliseconds and a device synchronisation each */
-    struct { void *p; size_t cap; } rs_cache[6];
+    struct { void *p; size_t cap; } rs_cache[7];
     int priv_stream_on;
     hipStream_t priv_stream;         /* lfq_set_private_stream: this context's own launch stream (null = the device's shared one) */
     hipStream_t up_stream;           /* lfq_readset_create's uploads and the staging copies of host tracks (created on first use) */
@@ -341,6 +341,8 @@ struct lfq_ctx {
     hipEvent_t ev_baq_t[2];          /* around the BAQ kernels of the last lfq_readset_baq / lfq_baq_batch call (timing; created on first use) */
     int32_t baq_launches;            /* kernel launches between them on the context's stream */
     int64_t baq_reads, baq_bases;    /* reads / bases of that call */
+    hipEvent_t ev_idq_t[2];          /* around the kernels of the last lfq_readset_indelqual / lfq_indelqual_batch call (created on first use) */
+    lfq_indelqual_times idq_times;   /* launches, reads and bases of that call (ms_kernels: from the events, when asked for) */
     int batch_gate;                  /* lfq_set_batch_gate: what this context's next count kernel waits for (LFQ_GATE_*) */
     int lazy_now;                    /* this batch: strand counts only for the columns of the sparse output */
     int64_t sub_ncols;               /* batch submitted with lfq_call_snvs_submit and not collected yet: its columns, else -1 */

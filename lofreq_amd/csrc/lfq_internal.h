@@ -352,6 +352,26 @@ int lfq_launch_plp_indel_columns(const LfqPlpIndelArgs &a, int scatter, void *st
 int64_t lfq_keep_compact_scratch(int64_t n);
 int lfq_launch_keep_compact(const uint8_t *keep, const int32_t *pos, int64_t n, void *scratch, int32_t *kept_idx,
                             int32_t *kept_pos, int32_t *kept_pmax, void *stream);
+/* `lofreq indelqual` (lfq_indelqual.hip).  Table: one Dindel byte per reference position of [tab_begin, tab_end), tab_begin a
+ * multiple of 16 and tab_end <= ref_len; the kernel stores whole 16-byte words, so `tab` holds the length rounded up to 16.
+ * Fill: bi / bd are 16-byte aligned and hold n_bases rounded up to 16; tab == null selects the uniform fill of ins_byte /
+ * del_byte, otherwise the Dindel string goes to bi alone (BD is the same string: the caller lets both pointers name one array).
+ * The CIGARs were checked on the host: only M I D S H = X, query length = the seq_off span. */
+struct LfqIdqArgs {
+    int64_t n_reads, n_bases;
+    const int32_t *pos;
+    const int64_t *cigar_off, *seq_off;
+    const uint32_t *cigar;
+    const uint8_t *tab;
+    int64_t tab_begin, tab_end;
+    uint32_t ins_byte, del_byte;
+    uint8_t *bi, *bd;
+};
+int lfq_launch_idq_table(const uint8_t *ref, int64_t ref_len, int64_t tab_begin, int64_t tab_end, uint8_t *tab, void *stream);
+int lfq_launch_idq_fill(const LfqIdqArgs &a, void *stream);
+/* host: the table byte of reference position x, and the Dindel byte of query base qpos of one read (its CIGAR walk) */
+uint8_t lfq_idq_ref_byte(const char *ref, int64_t ref_len, int64_t x);
+uint8_t lfq_idq_host_byte(const char *ref, int64_t ref_len, int64_t pos, const uint32_t *cigar, int n_cigar, int64_t qpos);
 int lfq_launch_flag_merge(uint8_t *fl, const uint8_t *tag, int64_t n, void *stream);
 int lfq_launch_skip_columns(int32_t *nb, const uint8_t *skip, int64_t n, void *stream);
 int lfq_launch_pack_nt(const uint8_t *nt_bytes, uint8_t *nt_packed, int64_t n_obs, void *stream);

@@ -13,7 +13,7 @@ extern "C" {
  * copy and leave their per-base results (lb, ai, ad, sq) there for the next stage.  The host arrays handed to
  * lfq_readset_create stay the caller's and must outlive the read set: the sparse host-side steps (geometry from the
  * CIGARs, the indel event tables) read them in place. */
-enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5 };
+enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5, LFQ_RSC_IDQ = 6 };
 
 static void rs_cache_free(int kind, void *p)
 {
@@ -64,7 +64,7 @@ static void rs_cache_give(lfq_ctx *c, int kind, void *p, size_t cap)
 #define LFQ_UP_CHUNKS 6
 struct lfq_readset {
     lfq_ctx *c;
-    size_t cap[6];                      /* capacities of blob, tag_blob, d_pmax, d_tagfl, h_fl_pin, d_keep (rs_cache_*) */
+    size_t cap[7];                      /* capacities of blob, tag_blob, d_pmax, d_tagfl, h_fl_pin, d_keep, idq_blob (rs_cache_*) */
     int64_t n, n_bases, n_cig, ref_len;
     const int32_t *pos;
     const int64_t *cigar_off, *seq_off;
@@ -77,6 +77,12 @@ struct lfq_readset {
     uint8_t *d_pos, *d_coff, *d_soff, *d_cig, *d_seq, *d_qual, *d_ref, *d_mapq, *d_rev, *d_bi, *d_bd, *d_lb, *d_ai,
             *d_ad, *d_fl, *d_sqb;
     bool has_lb, has_idaq, has_sqb, has_bi, has_bd;
+    /* lfq_readset_indelqual: BI / BD computed here (d_bi / d_bd then point into idq_blob, every read has both tags, and the
+     * host side of the indel pileup evaluates the bytes it needs instead of reading h_bi / h_bd) */
+    int idq_mode;                       /* 0: not run; LFQ_IDQ_UNIFORM / LFQ_IDQ_DINDEL */
+    uint8_t idq_ins, idq_del;           /* uniform mode: the two tag bytes */
+    uint8_t *idq_blob;                  /* BI | BD (uniform) or the one string both are (Dindel) | the position table */
+    hipEvent_t ev_idq;                  /* its kernels are done: the pileup may run on another stream */
     std::vector<uint8_t> fl;            /* per read: bit 0..3 = has BI / BD / ai / ad (host flags or from the device BAQ) */
     std::vector<int32_t> sq32;          /* source quality per read once computed */
     /* lfq_readset_baq returns when its kernels are queued: what follows on the device is ordered by the stream, what the
@@ -227,15 +233,21 @@ void lfq_readset_destroy(lfq_readset *rs)
         rs_cache_give(rs->c, LFQ_RSC_TAGS, rs->tag_blob, rs->cap[LFQ_RSC_TAGS]);
         rs_cache_give(rs->c, LFQ_RSC_PMAX, rs->d_pmax, rs->cap[LFQ_RSC_PMAX]);
         rs_cache_give(rs->c, LFQ_RSC_KEEP, rs->d_keep, rs->cap[LFQ_RSC_KEEP]);
+        if (rs->ev_idq) {
+            (void)hipEventSynchronize(rs->ev_idq);      /* (its stream need not be c->stream) */
+            (void)hipEventDestroy(rs->ev_idq);
+        }
+        rs_cache_give(rs->c, LFQ_RSC_IDQ, rs->idq_blob, rs->cap[LFQ_RSC_IDQ]);
         if (rs->ev_keep) (void)hipEventDestroy(rs->ev_keep);
         delete rs;
     }
 }
 
-int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_indel_tags *tg, lfq_readset **out)
+/* lfq_readset_create; rd->seq may be null here (lfq_indelqual_batch: its kernels read no bases) */
+static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_indel_tags *tg, lfq_readset **out)
 {
     if (!c || !rd || !out || rd->n_reads < 0
-        || (rd->n_reads > 0 && (!rd->pos || !rd->cigar_off || !rd->cigar || !rd->seq_off || !rd->seq || !rd->ref))) {
+        || (rd->n_reads > 0 && (!rd->pos || !rd->cigar_off || !rd->cigar || !rd->seq_off || !rd->ref))) {
         return LFQ_ERR_INVALID;
     }
     *out = nullptr;
@@ -262,6 +274,9 @@ int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_
     rs->keep_valid = rs->keep_dev_valid = false;
     rs->d_keep = nullptr;
     rs->ev_keep = nullptr;
+    rs->idq_mode = 0;
+    rs->idq_blob = nullptr;
+    rs->ev_idq = nullptr;
     rs->up_thread = nullptr;
     rs->up_stage.store(0);
     rs->up_chunks.store(0);
@@ -287,7 +302,7 @@ int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_
     /* per-base arrays only where there is something to put: device allocations of this size are not free.  The
      * outputs of lfq_readset_baq (lb, ai, ad) get their own allocation when that step runs. */
     const int64_t o_pos = take(n * 4), o_coff = take((n + 1) * 8), o_soff = take((n + 1) * 8), o_cig = take(rs->n_cig * 4),
-                  o_seq = take(nb + 16), o_qual = take(rd->qual ? nb + 16 : 0), o_ref = take(rs->ref_len + 1), o_mapq = take(n),
+                  o_seq = take(rd->seq ? nb + 16 : 0), o_qual = take(rd->qual ? nb + 16 : 0), o_ref = take(rs->ref_len + 1), o_mapq = take(n),
                   o_rev = take(n), o_bi = take(rs->h_bi ? nb + 16 : 0), o_bd = take(rs->h_bd ? nb + 16 : 0),
                   o_lb = take(rd->baq ? nb + 16 : 0), o_fl = take(n), o_sqb = take(n);
     rs->blob = (uint8_t *)rs_cache_take(c, LFQ_RSC_BLOB, (size_t)off, &rs->cap[LFQ_RSC_BLOB]);
@@ -355,7 +370,7 @@ int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_
     }
     for (int j = 0; j < n_chunks; j++) {
         const int64_t b0 = rd->seq_off[rs->up_bound[j]], b1 = rd->seq_off[rs->up_bound[j + 1]];
-        add(rs->d_seq + b0, rd->seq + b0, b1 - b0);
+        add(rs->d_seq + b0, rd->seq ? rd->seq + b0 : nullptr, b1 - b0);
         add(rs->d_qual + b0, rd->qual ? rd->qual + b0 : nullptr, b1 - b0);
         if (!todo.empty()) {
             todo.back().chunks_after = j + 1;
@@ -452,6 +467,14 @@ int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_
     }
     *out = rs;
     return LFQ_OK;
+}
+
+int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_indel_tags *tg, lfq_readset **out)
+{
+    if (rd && rd->n_reads > 0 && !rd->seq) {
+        return LFQ_ERR_INVALID;
+    }
+    return readset_create(c, rd, tg, out);
 }
 
 /* position-sorted reads (what mpileup requires) take the column-major pileup kernels, which find the reads that can
@@ -1247,6 +1270,201 @@ int lfq_last_baq_times(lfq_ctx *c, lfq_baq_times *t)
     return LFQ_OK;
 }
 
+/* `lofreq indelqual` on the resident reads (kernels: lfq_indelqual.hip) */
+int lfq_readset_indelqual(lfq_ctx *c, lfq_readset *rs, const lfq_indelqual_conf *conf)
+{
+    if (!c || !rs || rs->c != c || !conf || (conf->mode != LFQ_IDQ_UNIFORM && conf->mode != LFQ_IDQ_DINDEL)) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = rs->n, nb = rs->n_bases;
+    const bool dindel = conf->mode == LFQ_IDQ_DINDEL;
+    int64_t lo = INT64_MAX, hi = 0;         /* reference positions the M / = / X operations of the batch cover */
+    if (dindel && n > 0) {
+        /* what the reference cannot do (see the header), and the span of the table */
+        int64_t part_lo[LFQ_HOST_PARTS], part_hi[LFQ_HOST_PARTS];
+        bool part_bad[LFQ_HOST_PARTS];
+        int parts = 1;
+        lfq_for_reads(n, [&](int64_t r0, int64_t r1, int part) {
+            int64_t plo = INT64_MAX, phi = 0;
+            bool bad = false;
+            for (int64_t r = r0; r < r1; r++) {
+                int64_t x = rs->pos[r], y = 0;
+                bad = bad || x < 0;
+                for (int64_t k = rs->cigar_off[r]; k < rs->cigar_off[r + 1]; k++) {
+                    const int op = (int)(rs->cigar[k] & 0xf);
+                    const int64_t len = rs->cigar[k] >> 4;
+                    if (op == 0 || op == 7 || op == 8) {
+                        if (len > 0) {
+                            plo = std::min(plo, x);
+                            phi = std::max(phi, x + len);
+                        }
+                        x += len;
+                        y += len;
+                    } else if (op == 1 || op == 4) {
+                        y += len;
+                    } else if (op == 2) {
+                        x += len;
+                    } else if (op != 5) {
+                        bad = true;                 /* "unknown op" (lofreq_indelqual.c:195) */
+                    }
+                }
+                bad = bad || y != rs->seq_off[r + 1] - rs->seq_off[r];
+            }
+            part_lo[part] = plo;
+            part_hi[part] = phi;
+            part_bad[part] = bad;
+        }, &parts);
+        for (int q = 0; q < parts; q++) {
+            if (part_bad[q]) {
+                return LFQ_ERR_INVALID;
+            }
+            lo = std::min(lo, part_lo[q]);
+            hi = std::max(hi, part_hi[q]);
+        }
+    }
+    c->idq_times.ms_kernels = 0.f;
+    c->idq_times.n_launches = 0;
+    c->idq_times.n_reads = n;
+    c->idq_times.n_bases = nb;
+    if (n == 0 || nb == 0) {
+        rs->idq_mode = 0;
+        return LFQ_OK;
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    /* Nothing here reads what lfq_readset_baq writes: beside a BAQ step that is still running the kernels take the stream the
+     * indel pileup will take (see lfq_readset_pileup_indels); the event orders any other consumer behind them */
+    hipStream_t qs = (rs->baq_pending && c->dps && !lfq_knobs().single_stream) ? c->dps : c->stream;
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t tab_begin = lo < hi ? lo / 16 * 16 : 0, tab_end = lo < hi ? std::min(hi, rs->ref_len) : 0;
+    const int64_t each = al(nb + 16), o_tab = (dindel ? 1 : 2) * each;
+    const int64_t total = o_tab + (dindel ? al(std::max<int64_t>(tab_end - tab_begin, 0) + 16) : 0);
+    if (rs->ev_idq) {
+        LFQ_TRY_HIP(hipEventSynchronize(rs->ev_idq));       /* a second pass over the same read set: the first one's kernels are done */
+    } else {
+        LFQ_TRY_HIP(hipEventCreateWithFlags(&rs->ev_idq, hipEventDisableTiming));
+    }
+    if (!rs->idq_blob || rs->cap[LFQ_RSC_IDQ] < (size_t)total) {
+        rs_cache_give(c, LFQ_RSC_IDQ, rs->idq_blob, rs->cap[LFQ_RSC_IDQ]);
+        rs->idq_blob = (uint8_t *)rs_cache_take(c, LFQ_RSC_IDQ, (size_t)total, &rs->cap[LFQ_RSC_IDQ]);
+        if (!rs->idq_blob) {
+            return LFQ_ERR_NOMEM;
+        }
+    }
+    if (!c->ev_idq_t[0]) {
+        LFQ_TRY_HIP(hipEventCreate(&c->ev_idq_t[0]));
+        LFQ_TRY_HIP(hipEventCreate(&c->ev_idq_t[1]));
+    }
+    LfqIdqArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_reads = n;
+    A.n_bases = nb;
+    A.bi = rs->idq_blob;
+    A.bd = dindel ? rs->idq_blob : rs->idq_blob + each;
+    int rc = LFQ_OK;
+    if (dindel) {
+        rc = readset_upload_wait_inputs(rs, {qs});          /* positions, CIGARs, offsets and the contig are on the device */
+        A.pos = (const int32_t *)rs->d_pos;
+        A.cigar_off = (const int64_t *)rs->d_coff;
+        A.seq_off = (const int64_t *)rs->d_soff;
+        A.cigar = (const uint32_t *)rs->d_cig;
+        A.tab = rs->idq_blob + o_tab;
+        A.tab_begin = tab_begin;
+        A.tab_end = tab_end;
+    } else {
+        auto encode_q = [](int64_t q) { return (uint8_t)(q < 33 ? '!' : (q > 126 ? '~' : q)); };   /* ENCODE_Q, :66 */
+        rs->idq_ins = encode_q((int64_t)conf->ins_qual + 33);
+        rs->idq_del = encode_q((int64_t)conf->del_qual + 33);
+        A.ins_byte = rs->idq_ins;
+        A.del_byte = rs->idq_del;
+    }
+    if (rc == LFQ_OK && hipEventRecord(c->ev_idq_t[0], qs) != hipSuccess) {
+        rc = LFQ_ERR_HIP;
+    }
+    if (rc == LFQ_OK && dindel && tab_end > tab_begin) {
+        rc = lfq_launch_idq_table(rs->d_ref, rs->ref_len, tab_begin, tab_end, rs->idq_blob + o_tab, qs);
+        c->idq_times.n_launches++;
+    }
+    if (rc == LFQ_OK) {
+        rc = lfq_launch_idq_fill(A, qs);
+        c->idq_times.n_launches++;
+    }
+    if (rc == LFQ_OK && (hipEventRecord(c->ev_idq_t[1], qs) != hipSuccess || hipEventRecord(rs->ev_idq, qs) != hipSuccess)) {
+        rc = LFQ_ERR_HIP;
+    }
+    if (rc != LFQ_OK) {
+        (void)hipStreamSynchronize(qs);
+        return rc;
+    }
+    rs->idq_mode = conf->mode;
+    rs->d_bi = A.bi;
+    rs->d_bd = A.bd;
+    rs->has_bi = rs->has_bd = true;
+    rs->h_bi = rs->h_bd = nullptr;              /* superseded by the device result */
+    return LFQ_OK;
+}
+
+int lfq_readset_fetch_indelquals(lfq_ctx *c, lfq_readset *rs, uint8_t *bi_out, uint8_t *bd_out)
+{
+    if (!c || !rs || rs->c != c) {
+        return LFQ_ERR_INVALID;
+    }
+    if (rs->n == 0 || rs->n_bases == 0) {
+        return LFQ_OK;
+    }
+    if (!rs->idq_mode) {
+        return LFQ_ERR_INVALID;
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    LFQ_TRY_HIP(hipStreamWaitEvent(c->stream, rs->ev_idq, 0));
+    if (bi_out) LFQ_TRY_HIP(hipMemcpyAsync(bi_out, rs->d_bi, (size_t)rs->n_bases, hipMemcpyDeviceToHost, c->stream));
+    if (bd_out) LFQ_TRY_HIP(hipMemcpyAsync(bd_out, rs->d_bd, (size_t)rs->n_bases, hipMemcpyDeviceToHost, c->stream));
+    LFQ_TRY_HIP(hipStreamSynchronize(c->stream));
+    return LFQ_OK;
+}
+
+int lfq_indelqual_batch(lfq_ctx *c, const lfq_baq_reads *rd, const lfq_indelqual_conf *conf, uint8_t *bi_out, uint8_t *bd_out)
+{
+    if (!c || !rd || !conf || rd->n_reads < 0 || (conf->mode != LFQ_IDQ_UNIFORM && conf->mode != LFQ_IDQ_DINDEL)
+        || (rd->n_reads > 0 && (!rd->pos || !rd->cigar_off || !rd->cigar || !rd->seq_off || !rd->ref || !bi_out || !bd_out))) {
+        return LFQ_ERR_INVALID;
+    }
+    if (rd->n_reads == 0) {
+        memset(&c->idq_times, 0, sizeof(c->idq_times));
+        return LFQ_OK;
+    }
+    /* the read set of this step holds what its kernels read: positions, CIGARs, offsets, the contig -- no bases, no qualities */
+    lfq_pileup_reads pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.n_reads = rd->n_reads;
+    pr.pos = rd->pos; pr.cigar_off = rd->cigar_off; pr.cigar = rd->cigar; pr.seq_off = rd->seq_off;
+    pr.ref = rd->ref; pr.ref_len = rd->ref_len;
+    lfq_readset *rs = nullptr;
+    LFQ_TRY(readset_create(c, &pr, nullptr, &rs));
+    int rc = lfq_readset_indelqual(c, rs, conf);
+    if (rc == LFQ_OK) {
+        rc = lfq_readset_fetch_indelquals(c, rs, bi_out, bd_out);
+    }
+    lfq_readset_destroy(rs);
+    return rc;
+}
+
+int lfq_last_indelqual_times(lfq_ctx *c, lfq_indelqual_times *t)
+{
+    if (!c || !t) {
+        return LFQ_ERR_INVALID;
+    }
+    *t = c->idq_times;
+    if (t->n_launches > 0 && c->ev_idq_t[1]) {
+        LFQ_TRY_HIP(hipSetDevice(c->device));
+        LFQ_TRY_HIP(hipEventSynchronize(c->ev_idq_t[1]));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c->ev_idq_t[0], c->ev_idq_t[1]) == hipSuccess) {
+            t->ms_kernels = ms;
+        }
+    }
+    return LFQ_OK;
+}
+
 int lfq_pileup_snv_tracks(lfq_ctx *c, const lfq_pileup_reads *rd, int64_t region_begin, int64_t region_end,
                           int min_plp_bq, lfq_tracks *out, int64_t *col_pos_out)
 {
@@ -1449,6 +1667,19 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
     const uint8_t *t_bi = rs->h_bi, *t_bd = rs->h_bd, *t_ai = rs->h_ai, *t_ad = rs->h_ad, *t_fl = rs->fl.data();
     const int32_t *t_sq = rs->h_sq ? rs->h_sq : (rs->sq32.empty() ? nullptr : rs->sq32.data());
 
+    /* ... and BI / BD computed by lfq_readset_indelqual are evaluated for the event's base: q[0] = BI, q[1] = BD as qualities */
+    auto idq_at = [rs, rd](int64_t r, int qpos, int *q) {
+        if (qpos < 0) {
+            q[0] = q[1] = 0;
+        } else if (rs->idq_mode == LFQ_IDQ_UNIFORM) {
+            q[0] = (int)rs->idq_ins - 33;
+            q[1] = (int)rs->idq_del - 33;
+        } else {
+            q[0] = q[1] = (int)lfq_idq_host_byte(rd->ref, rd->ref_len, rd->pos[r], rd->cigar + rd->cigar_off[r],
+                                                 (int)(rd->cigar_off[r + 1] - rd->cigar_off[r]), qpos) - 33;
+        }
+    };
+
     double tm[8] = {lfq_now_ms(), 0, 0, 0, 0, 0, 0, 0};
     /* 1. events from the CIGARs, in read (= pileup) order */
     struct Ev { int64_t pos; int64_t read; int32_t qpos, indel; };
@@ -1470,6 +1701,7 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
         const uint32_t fl = t_fl[r];
         int64_t x = rd->pos[r];
         int y = 0;
+        int q_ev[2];
         for (int k = 0; k < n_cigar; ++k) {
             const int op = cg[k] & 0xf, l = cg[k] >> 4;
             if (op == 0 || op == 7 || op == 8 || op == 2 || op == 3) {
@@ -1498,8 +1730,11 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
                 if (indel != 0 && p >= region_begin && p < region_end) {
                     int qpos = is_del ? y : y + l - 1;
                     qpos = qpos < l_qseq ? qpos : l_qseq - 1;
-                    const int iq = (t_bi && (fl & 1u) && qpos >= 0) ? (int)t_bi[s0 + qpos] - 33 : 0;
-                    const int dq = (t_bd && (fl & 2u) && qpos >= 0) ? (int)t_bd[s0 + qpos] - 33 : 0;
+                    if (rs->idq_mode) {
+                        idq_at(r, qpos, q_ev);
+                    }
+                    const int iq = rs->idq_mode ? q_ev[0] : (t_bi && (fl & 1u) && qpos >= 0) ? (int)t_bi[s0 + qpos] - 33 : 0;
+                    const int dq = rs->idq_mode ? q_ev[1] : (t_bd && (fl & 2u) && qpos >= 0) ? (int)t_bd[s0 + qpos] - 33 : 0;
                     if (!(iq < min_plp_idq || dq < min_plp_idq)) {      /* plp.c:1062 */
                         evs.push_back({p, r, qpos, indel});
                     }
@@ -1580,6 +1815,9 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
         hipStream_t ps = (rs->baq_pending && c->dps && !lfq_knobs().single_stream) ? c->dps : c->stream;
         (void)readset_pmax(c, rs, ps);      /* (its small upload is waited for on this stream: before the stream itself waits) */
         LFQ_TRY(readset_upload_wait(rs, ps));
+        if (rs->ev_idq) {
+            LFQ_TRY_HIP(hipStreamWaitEvent(ps, rs->ev_idq, 0));
+        }
         auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
         const int64_t o_cnt = 0, o_cur = o_cnt + 9 * al(width * 4), o_off = o_cur + 2 * al(width * 4),
                       total = o_off + 2 * al(width * 8);
@@ -1605,7 +1843,7 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
         A.cigar = (const uint32_t *)rs->d_cig;
         A.bi = rs->has_bi ? rs->d_bi : nullptr;
         A.bd = rs->has_bd ? rs->d_bd : nullptr;
-        A.tag_flags = rs->d_fl;
+        A.tag_flags = rs->idq_mode ? nullptr : rs->d_fl;        /* lfq_readset_indelqual: every read has both */
         A.mapq = rs->d_mapq;
         A.reverse = rs->d_rev;
         A.begin = region_begin;
@@ -1740,7 +1978,13 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
                             const uint32_t fl = t_fl[e.read];
                             const uint8_t *qa = sd == 0 ? t_bi : t_bd;
                             const bool has_q = qa && (fl & (sd == 0 ? 1u : 2u));
-                            S.rd_q.push_back((int16_t)(has_q ? (int)qa[s0 + e.qpos] - 33 : 0));
+                            if (rs->idq_mode) {
+                                int q[2];
+                                idq_at(e.read, e.qpos, q);
+                                S.rd_q.push_back((int16_t)q[sd]);
+                            } else {
+                                S.rd_q.push_back((int16_t)(has_q ? (int)qa[s0 + e.qpos] - 33 : 0));
+                            }
                             S.rd_aq.push_back((int16_t)-1);                  /* filled when the BAQ kernels are through */
                             P.rd_ev[sd].push_back((int64_t)i);
                             S.rd_mq.push_back((int16_t)rd->mapq[e.read]);

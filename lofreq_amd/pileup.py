@@ -321,6 +321,15 @@ class ReadSet:
         _lib.check(self.L.lfq_readset_fetch_tags(self.caller.h, self.h, p(lb), p(ai), p(ad), p(fl)), "lfq_readset_fetch_tags")
         return lb, ai, ad, fl
 
+    def indelqual(self, mode="dindel", ins_qual=0, del_qual=None):
+        """lfq_readset_indelqual (`lofreq indelqual`): BI / BD computed on the device copy, for a read set created without"""
+        from .indelqual import readset_indelqual
+        readset_indelqual(self, mode, ins_qual, del_qual)
+
+    def fetch_indelquals(self):
+        from .indelqual import readset_fetch_indelquals
+        return readset_fetch_indelquals(self)
+
     def kept_reads(self, max_depth=None):
         """lfq_readset_kept_reads: which reads the pileups take under the cap -> (uint8 mask, number kept)"""
         keep = np.zeros(max(self.n, 1), np.uint8)

@@ -42,7 +42,7 @@ extern "C" {
 /* 7: lfq_set_max_depth, lfq_readset_kept_reads. */
 /* 8: lfq_viterbi_batch, lfq_last_viterbi_times. */
 /* 9: lfq_indelqual_batch, lfq_readset_indelqual, lfq_readset_fetch_indelquals, lfq_last_indelqual_times. */
-#define LFQ_ABI_VERSION 9
+#define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
     LFQ_OK = 0,
@@ -366,7 +366,7 @@ int lfq_baq_idaq_batch(lfq_ctx *ctx, const lfq_baq_reads *reads, int baq_extende
  * Qualities above 93 in a read that is realigned, def_qual above 93 and a realigned read with pos < 0 are LFQ_ERR_INVALID.
  * What the caller still does: delete the NM / MC / MD / AS tags of EVERY read unless -k (:119-146), write
  * pos and CIGAR back, and sort -- the output is no longer coordinate-sorted (:362).
- * The result belongs to the context and is valid until its next lfq_viterbi_batch call.  cigar[cigar_off[r] .. cigar_off[r + 1])
+ * The result belongs to the context and is valid until its next lfq_viterbi_batch or lfq_readset_viterbi call.  cigar[cigar_off[r] .. cigar_off[r + 1])
  * is read r's CIGAR in BAM encoding -- the input's for a read left as it is, so that the arrays can be taken whole. */
 #define LFQ_VIT_NO_INDEL 0
 #define LFQ_VIT_SKIPPED_OP 1
@@ -534,6 +534,28 @@ int lfq_readset_fetch_tags(lfq_ctx *ctx, lfq_readset *rs, uint8_t *lb_out, uint8
 int lfq_readset_indelqual(lfq_ctx *ctx, lfq_readset *rs, const lfq_indelqual_conf *conf);
 /* copies of the resident BI / BD bytes for writing them to the BAM; NULL = not wanted.  LFQ_ERR_INVALID before the step ran */
 int lfq_readset_fetch_indelquals(lfq_ctx *ctx, lfq_readset *rs, uint8_t *bi_out, uint8_t *bd_out);
+
+/* `lofreq viterbi` as a step of the read set, BEFORE every other step: the reads of `rs` are realigned, read by read exactly as
+ * lfq_viterbi_batch documents above (classification, query, q2def, window, Viterbi, left-alignment, new CIGAR, new pos, the same
+ * LFQ_ERR_INVALID cases), and *out is a NEW read set of the same reads with the new positions and CIGARs, STABLY SORTED BY NEW
+ * POSITION (ties keep their input order) -- ready for lfq_readset_baq / _indelqual / the pileups.  The input need not be sorted.
+ *   *result_or_null   the struct lfq_viterbi_batch gives for these reads, in the INPUT order; the context's, valid until its
+ *                     next viterbi call of either kind.
+ *   *order_or_null    [n] order[j] = input index of the read at place j of *out; owned by *out, valid until it is destroyed.
+ * `rs` is never modified: it stays valid and usable.  *out owns host copies of everything its host-side steps read (positions,
+ * CIGARs, offsets, mapq, strand, bases, qualities, uploaded BI / BD, the contig), made on the host from the caller's arrays in the
+ * new order; it depends neither on `rs` nor on the caller's arrays after the call, which need only outlive `rs` as before.  Both
+ * read sets are destroyed by the caller, in either order, before lfq_destroy.
+ * The per-base device arrays of *out (bases, qualities, uploaded BI / BD) are written ON THE DEVICE from those of `rs`: what
+ * crosses the link is per-read descriptors, the new positions, offsets and CIGARs going down and the traced states coming back.
+ * Uploaded BI / BD are carried along read by read as they are; that they still fit is the caller's business, as in the
+ * reference ("Do not realign your BAM file afterwards!", lofreq_indelqual.c:332).
+ * LFQ_ERR_INVALID: a read set created with reads->baq, reads->sq, tags->ai / ->ad / ->sq, or on which lfq_readset_baq,
+ * _source_qual or _indelqual has run (all of these depend on the alignment); def_qual > 93; out == NULL.
+ * n == 0 or no read to realign: no realignment kernel is launched (lfq_last_viterbi_times: n_launches 0) and *out is the input
+ * in its stable-sorted order.  The call blocks until *out is complete. */
+int lfq_readset_viterbi(lfq_ctx *ctx, lfq_readset *rs, int def_qual, lfq_readset **out,
+                        const lfq_viterbi_result **result_or_null, const int64_t **order_or_null);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

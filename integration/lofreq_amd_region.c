@@ -72,6 +72,7 @@ struct lfq_region {
     int64_t max_depth;              /* lfq_region_set_max_depth; LFQ_NO_MAX_DEPTH by default */
     int max_depth_set;              /* lfq_region_set_max_depth was called: close takes the cap off the context again */
     lfq_indelqual_conf idq;         /* lfq_region_set_indelqual; mode 0 = off (the default) */
+    int vit_on, vit_def_qual;       /* lfq_region_set_viterbi; off by default */
     /* outputs, grown on demand */
     int64_t *col_pos_i, pos_cap;
     lfq_snv_record *srec;
@@ -171,6 +172,16 @@ int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_nu
     if (conf_or_null) {
         r->idq = *conf_or_null;
     }
+    return LFQ_OK;
+}
+
+int lfq_region_set_viterbi(lfq_region *r, int on, int def_qual)
+{
+    if (!r || r->open || r->buf[0].started || r->buf[1].started || (on && def_qual > 93)) {
+        return LFQ_ERR_INVALID;
+    }
+    r->vit_on = on != 0;
+    r->vit_def_qual = def_qual;
     return LFQ_OK;
 }
 
@@ -300,6 +311,16 @@ static int region_start(lfq_region *r, reg_buf *b)
     rc = lfq_readset_create(r->ctx, &rd, &tg, &b->rs);
     if (rc != LFQ_OK) {
         return rc;
+    }
+    if (r->vit_on) {
+        /* `lofreq viterbi` + sort: a new read set that owns its host arrays takes the place of the uploaded one (blocks) */
+        lfq_readset *realigned = NULL;
+        rc = lfq_readset_viterbi(r->ctx, b->rs, r->vit_def_qual, &realigned, NULL, NULL);
+        lfq_readset_destroy(b->rs);
+        b->rs = realigned;
+        if (rc != LFQ_OK) {
+            return rc;
+        }
     }
     if (r->o.use_baq || r->o.use_idaq) {                                /* plp.c:667-683 */
         rc = lfq_readset_baq(r->ctx, b->rs, r->o.baq_extended, r->o.use_idaq ? 1 : 0);

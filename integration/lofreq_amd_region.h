@@ -66,6 +66,17 @@ int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth);
  * after lfq_region_open, before the first lfq_region_begin.  Not a field of lfq_region_opts, whose size callers rely on.
  * Dindel mode fails a region (LFQ_ERR_INVALID from lfq_region_end) whose reads hold an N or P operation, as the command does. */
 int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_null);
+/* `lofreq viterbi` inside the binding (opt-in; default off): with on != 0, lfq_region_end creates the region's read set, realigns
+ * it with lfq_readset_viterbi(def_qual: -q / --defqual, negative = the read's median quality), destroys the first read set and goes
+ * on -- BAQ, indelqual, pileups, calls -- with the new one, whose reads are sorted by their new positions: the binding replaces
+ * the `samtools sort` between `lofreq viterbi` and the next step.  lfq_region_end then BLOCKS for the realignment of the region
+ * it starts (the traced states come back to the host) instead of returning when the BAQ kernels are queued.
+ * Region edges: the reads handed in for a region are realigned as if `lofreq viterbi` had run on exactly those reads; a read
+ * that the realignment moves across a region's edge stays in the region it was handed in for, and reads handed in out of position
+ * order are accepted.  BI / BD tags handed in with the reads are carried along as they are.  def_qual above 93 is
+ * LFQ_ERR_INVALID, as is a read with a quality above 93 that would be realigned (from lfq_region_end).  Same calling rule as
+ * lfq_region_set_indelqual: after lfq_region_open, before the first lfq_region_begin.  Not a field of lfq_region_opts. */
+int lfq_region_set_viterbi(lfq_region *r, int on, int def_qual);
 /* `ref`: the contig, upper-cased (plp.c:652), valid until the NEXT lfq_region_end / lfq_region_close has returned */
 int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, int64_t ref_len, int64_t beg0, int64_t end0);
 /* one BAM record that passed the flag filters of plp.c:608-632, in file order (position-sorted).  The fields are

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LFQ_AMD_LIB") or os.path.join(_HERE, "liblofreq_amd.so")   # LFQ_AMD_LIB: another build of the same library (A/B runs)
 
 LFQ_OK = 0
-LFQ_ABI_VERSION = 9     # include/lofreq_amd.h; load() refuses a library built from another header
+LFQ_ABI_VERSION = 10    # include/lofreq_amd.h; load() refuses a library built from another header
 LFQ_ERR_CAPACITY = -4
 LFQ_USE_BAQ, LFQ_USE_MQ, LFQ_USE_SQ, LFQ_USE_IDAQ = 1, 2, 4, 8
 LFQ_PV_NONE, LFQ_PV_LOG, LFQ_PV_LOG_FECLAMP, LFQ_PV_UNDERFLOW = 0, 1, 2, 3
@@ -73,7 +73,7 @@ LFQ_VIT_STATUS_MASK, LFQ_VIT_CHANGED = 7, 8
 
 
 class ViterbiResult(C.Structure):
-    """lfq_viterbi_result: owned by the context, valid until its next lfq_viterbi_batch call"""
+    """lfq_viterbi_result: owned by the context, valid until its next lfq_viterbi_batch / lfq_readset_viterbi call"""
     _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in ("pos", "status", "cigar_off", "cigar")]
 
 
@@ -158,6 +158,7 @@ EXPORTS = [
     "lfq_readset_create", "lfq_readset_destroy", "lfq_readset_baq", "lfq_readset_source_qual",
     "lfq_readset_pileup_snv", "lfq_readset_pileup_indels", "lfq_readset_fetch_tags",
     "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
+    "lfq_readset_viterbi",
     "lfq_indelqual_batch", "lfq_readset_indelqual", "lfq_readset_fetch_indelquals", "lfq_last_indelqual_times",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
@@ -260,6 +261,7 @@ def load():
     L.lfq_baq_idaq_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, vp, vp, vp, vp]
     L.lfq_viterbi_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, C.POINTER(C.POINTER(ViterbiResult))]
     L.lfq_last_viterbi_times.argtypes = [vp, C.POINTER(ViterbiTimes)]
+    L.lfq_readset_viterbi.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.POINTER(ViterbiResult)), C.POINTER(vp)]
     L.lfq_indelqual_batch.argtypes = [vp, C.POINTER(BaqReads), C.POINTER(IndelqualConf), vp, vp]
     L.lfq_readset_indelqual.argtypes = [vp, vp, C.POINTER(IndelqualConf)]
     L.lfq_readset_fetch_indelquals.argtypes = [vp, vp, vp, vp]

@@ -444,6 +444,18 @@ struct LfqPin {
 /* ---- internal functions that cross file boundaries (lfq_api.hip) ---- */
 int lfq_make_params(const lfq_conf *conf, const lfq_tracks *tr, LfqParams *P, bool indel_mode);
 void lfq_viterbi_release(lfq_ctx *c);      /* lfq_viterbi.hip: what lfq_destroy frees of lfq_ctx::vit */
+/* lfq_viterbi.hip, for lfq_readset_viterbi: the device arrays of a read set whose host arrays are the `reads` of the call */
+struct LfqVitResident {
+    const int64_t *d_seq_off, *d_cigar_off;
+    const uint32_t *d_cigar;
+    const uint8_t *d_seq, *d_qual, *d_ref;
+};
+/* lfq_viterbi_batch; with `res`, query, q2def and windows are gathered on the device instead of packed and uploaded */
+int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *reads, int def_qual, const LfqVitResident *res,
+                    const lfq_viterbi_result **out);
+/* dst[k][new order] = src[k][old order] for up to four per-base arrays; returns when the kernel is done */
+int lfq_viterbi_permute(lfq_ctx *c, int64_t n_reads, int64_t n_bases, const int64_t *d_new_off, const int64_t *old_start,
+                        int n_arrays, const uint8_t *const *src, uint8_t *const *dst);
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

@@ -4,6 +4,7 @@
  */
 #include "lfq_ctx.h"
 
+#include <memory>
 #include <queue>
 
 extern "C" {
@@ -60,6 +61,15 @@ static void rs_cache_give(lfq_ctx *c, int kind, void *p, size_t cap)
         rs_cache_free(kind, p);
     }
 }
+
+/* what a read set made by lfq_readset_viterbi owns: the host arrays its host-side steps read, in its own read order */
+struct LfqReadsetOwned {
+    LfqVec<int32_t> pos;
+    LfqVec<int64_t> cigar_off, seq_off, order;
+    LfqVec<uint32_t> cigar;
+    LfqVec<uint8_t> mapq, reverse, flags, seq, qual, bi, bd;
+    LfqVec<char> ref;
+};
 
 #define LFQ_UP_CHUNKS 6
 struct lfq_readset {
@@ -119,6 +129,7 @@ struct lfq_readset {
     bool up_events;
     hipEvent_t ev_chunk[LFQ_UP_CHUNKS]; /* bases + qualities of the reads up to chunk j have landed */
     hipEvent_t ev_stage[2];             /* [0]: everything but BI / BD, [1]: all of it */
+    LfqReadsetOwned *own;               /* lfq_readset_viterbi's result: the host views above point into it (else null) */
 };
 
 /* the reads, qualities, CIGARs and the contig are on the device (BI / BD may still be on their way: the BAQ kernels do
@@ -239,12 +250,16 @@ void lfq_readset_destroy(lfq_readset *rs)
         }
         rs_cache_give(rs->c, LFQ_RSC_IDQ, rs->idq_blob, rs->cap[LFQ_RSC_IDQ]);
         if (rs->ev_keep) (void)hipEventDestroy(rs->ev_keep);
+        delete rs->own;
         delete rs;
     }
 }
 
-/* lfq_readset_create; rd->seq may be null here (lfq_indelqual_batch: its kernels read no bases) */
-static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_indel_tags *tg, lfq_readset **out)
+/* lfq_readset_create; rd->seq may be null here (lfq_indelqual_batch: its kernels read no bases).  bases_resident
+ * (lfq_readset_viterbi): the per-base device arrays -- seq, qual, BI, BD -- get their room but no copy; the caller fills them
+ * on the device before it hands the read set out */
+static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_indel_tags *tg, lfq_readset **out,
+                          bool bases_resident = false)
 {
     if (!c || !rd || !out || rd->n_reads < 0
         || (rd->n_reads > 0 && (!rd->pos || !rd->cigar_off || !rd->cigar || !rd->seq_off || !rd->ref))) {
@@ -283,6 +298,7 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     rs->up_nchunks = 1;
     rs->up_rc = LFQ_OK;
     rs->up_fl = nullptr;
+    rs->own = nullptr;
     rs->has_lb = rs->has_idaq = rs->has_sqb = rs->has_bi = rs->has_bd = false;
     const int64_t n = rs->n, nb = rs->n_bases;
     {
@@ -370,8 +386,8 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     }
     for (int j = 0; j < n_chunks; j++) {
         const int64_t b0 = rd->seq_off[rs->up_bound[j]], b1 = rd->seq_off[rs->up_bound[j + 1]];
-        add(rs->d_seq + b0, rd->seq ? rd->seq + b0 : nullptr, b1 - b0);
-        add(rs->d_qual + b0, rd->qual ? rd->qual + b0 : nullptr, b1 - b0);
+        add(rs->d_seq + b0, rd->seq && !bases_resident ? rd->seq + b0 : nullptr, b1 - b0);
+        add(rs->d_qual + b0, rd->qual && !bases_resident ? rd->qual + b0 : nullptr, b1 - b0);
         if (!todo.empty()) {
             todo.back().chunks_after = j + 1;
         }
@@ -379,8 +395,8 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     if (!todo.empty()) {
         todo.back().stage_after = 1;
     }
-    add(rs->d_bi, rs->h_bi, nb);
-    add(rs->d_bd, rs->h_bd, nb);
+    add(rs->d_bi, bases_resident ? nullptr : rs->h_bi, nb);
+    add(rs->d_bd, bases_resident ? nullptr : rs->h_bd, nb);
     if (!todo.empty()) {
         todo.back().stage_after = 2;
     }
@@ -2477,6 +2493,127 @@ int lfq_readset_source_qual(lfq_ctx *c, lfq_readset *rs, int def_nm_q, int min_b
     /* the byte of the packed sq track, resident for lfq_readset_pileup_snv */
     LFQ_TRY_HIP(hipMemcpy(rs->d_sqb, sqb.data(), (size_t)n, hipMemcpyHostToDevice));
     rs->has_sqb = true;
+    return LFQ_OK;
+}
+
+/* `lofreq viterbi` on the resident reads: a NEW read set of the same reads with the realigned positions and CIGARs, stably
+ * sorted by new position; `rs` itself is only read.  The realignment is lfq_viterbi_batch's (lfq_viterbi.hip) with query, q2def
+ * and windows gathered from the device copy; the per-base arrays of the new set are written on the device from those of `rs`,
+ * its host views are copies it owns (LfqReadsetOwned), so that it needs neither `rs` nor the caller's arrays afterwards. */
+int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset **out, const lfq_viterbi_result **result_out,
+                        const int64_t **order_out)
+{
+    if (result_out) *result_out = nullptr;
+    if (order_out) *order_out = nullptr;
+    if (out) *out = nullptr;
+    if (!c || !rs || rs->c != c || !out || def_qual > 93 || (rs->n > 0 && (!rs->seq || !rs->qual))) {
+        return LFQ_ERR_INVALID;
+    }
+    /* what depends on the alignment cannot be carried over: lb, ai / ad, source quality, BI / BD computed from the CIGARs */
+    if (rs->has_lb || rs->has_idaq || rs->has_sqb || rs->baq_pending || rs->idq_mode || rs->h_ai || rs->h_ad || rs->h_sq
+        || !rs->sq32.empty()) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = rs->n, nb = rs->n_bases;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    LFQ_TRY(readset_upload_wait(rs));               /* the gather and permute kernels read all of it */
+    lfq_baq_reads br;
+    memset(&br, 0, sizeof(br));
+    br.n_reads = n;
+    br.pos = rs->pos; br.cigar_off = rs->cigar_off; br.cigar = rs->cigar; br.seq_off = rs->seq_off;
+    br.seq = rs->seq; br.qual = rs->qual; br.ref = rs->ref; br.ref_len = rs->ref_len;
+    LfqVitResident dv;
+    memset(&dv, 0, sizeof(dv));
+    if (n > 0) {
+        dv.d_seq_off = (const int64_t *)rs->d_soff; dv.d_cigar_off = (const int64_t *)rs->d_coff;
+        dv.d_cigar = (const uint32_t *)rs->d_cig; dv.d_seq = rs->d_seq; dv.d_qual = rs->d_qual; dv.d_ref = rs->d_ref;
+    }
+    const lfq_viterbi_result *res = nullptr;
+    LFQ_TRY(lfq_viterbi_run(c, &br, def_qual, &dv, &res));
+
+    /* the new order: by new position, ties in input order */
+    LfqReadsetOwned *own = new LfqReadsetOwned();
+    std::unique_ptr<LfqReadsetOwned> own_guard(own);
+    own->order.resize((size_t)n);
+    for (int64_t r = 0; r < n; r++) {
+        own->order[(size_t)r] = r;
+    }
+    std::stable_sort(own->order.begin(), own->order.end(), [&](int64_t a, int64_t b) { return res->pos[a] < res->pos[b]; });
+    own->pos.resize((size_t)std::max<int64_t>(n, 1));
+    own->cigar_off.resize((size_t)n + 1);
+    own->seq_off.resize((size_t)n + 1);
+    own->flags.resize((size_t)std::max<int64_t>(n, 1));
+    if (rs->mapq) own->mapq.resize((size_t)std::max<int64_t>(n, 1));
+    if (rs->reverse) own->reverse.resize((size_t)std::max<int64_t>(n, 1));
+    own->cigar_off[0] = own->seq_off[0] = 0;
+    std::vector<int64_t> old_start((size_t)std::max<int64_t>(n, 1));
+    for (int64_t j = 0; j < n; j++) {
+        const int64_t r = own->order[(size_t)j];
+        own->pos[(size_t)j] = res->pos[r];
+        own->cigar_off[(size_t)j + 1] = own->cigar_off[(size_t)j] + (res->cigar_off[r + 1] - res->cigar_off[r]);
+        own->seq_off[(size_t)j + 1] = own->seq_off[(size_t)j] + (rs->seq_off[r + 1] - rs->seq_off[r]);
+        own->flags[(size_t)j] = rs->fl[(size_t)r];
+        if (rs->mapq) own->mapq[(size_t)j] = rs->mapq[r];
+        if (rs->reverse) own->reverse[(size_t)j] = rs->reverse[r];
+        old_start[(size_t)j] = rs->seq_off[r];
+    }
+    own->cigar.resize((size_t)own->cigar_off[(size_t)n] + 1);
+    own->seq.resize((size_t)nb + 1);
+    own->qual.resize((size_t)nb + 1);
+    if (rs->h_bi) own->bi.resize((size_t)nb + 1);
+    if (rs->h_bd) own->bd.resize((size_t)nb + 1);
+    own->ref.assign(rs->ref, rs->ref + rs->ref_len);
+    own->ref.push_back('\0');
+    lfq_for_reads(n, [&](int64_t j0, int64_t j1, int) {
+        for (int64_t j = j0; j < j1; j++) {
+            const int64_t r = own->order[(size_t)j];
+            const int64_t nc = res->cigar_off[r + 1] - res->cigar_off[r], len = rs->seq_off[r + 1] - rs->seq_off[r];
+            const int64_t s_old = rs->seq_off[r], s_new = own->seq_off[(size_t)j];
+            if (nc > 0) {
+                memcpy(own->cigar.data() + own->cigar_off[(size_t)j], res->cigar + res->cigar_off[r], (size_t)nc * 4);
+            }
+            if (len > 0) {
+                memcpy(own->seq.data() + s_new, rs->seq + s_old, (size_t)len);
+                memcpy(own->qual.data() + s_new, rs->qual + s_old, (size_t)len);
+                if (rs->h_bi) memcpy(own->bi.data() + s_new, rs->h_bi + s_old, (size_t)len);
+                if (rs->h_bd) memcpy(own->bd.data() + s_new, rs->h_bd + s_old, (size_t)len);
+            }
+        }
+    });
+
+    lfq_pileup_reads pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.n_reads = n;
+    pr.pos = own->pos.data(); pr.cigar_off = own->cigar_off.data(); pr.cigar = own->cigar.data();
+    pr.seq_off = own->seq_off.data(); pr.seq = own->seq.data(); pr.qual = own->qual.data();
+    pr.mapq = rs->mapq ? own->mapq.data() : nullptr; pr.reverse = rs->reverse ? own->reverse.data() : nullptr;
+    pr.ref = own->ref.data(); pr.ref_len = rs->ref_len;
+    lfq_pileup_indel_tags tg;
+    memset(&tg, 0, sizeof(tg));
+    tg.bi = rs->h_bi ? own->bi.data() : nullptr;
+    tg.bd = rs->h_bd ? own->bd.data() : nullptr;
+    tg.tag_flags = own->flags.data();
+    lfq_readset *ns = nullptr;
+    LFQ_TRY(readset_create(c, &pr, &tg, &ns, true));
+    ns->own = own_guard.release();
+    int rc = readset_upload_wait(ns);               /* the new offsets are on the device */
+    if (rc == LFQ_OK && n > 0 && nb > 0) {
+        const uint8_t *src[4];
+        uint8_t *dst[4];
+        int na = 0;
+        src[na] = rs->d_seq; dst[na++] = ns->d_seq;
+        src[na] = rs->d_qual; dst[na++] = ns->d_qual;
+        if (rs->h_bi) { src[na] = rs->d_bi; dst[na++] = ns->d_bi; }
+        if (rs->h_bd) { src[na] = rs->d_bd; dst[na++] = ns->d_bd; }
+        rc = lfq_viterbi_permute(c, n, nb, (const int64_t *)ns->d_soff, old_start.data(), na, src, dst);
+    }
+    if (rc != LFQ_OK) {
+        lfq_readset_destroy(ns);
+        return rc;
+    }
+    *out = ns;
+    if (result_out) *result_out = res;
+    if (order_out) *order_out = ns->own->order.data();
     return LFQ_OK;
 }
 

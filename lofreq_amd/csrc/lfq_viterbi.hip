@@ -12,6 +12,10 @@
  *           window, the tables; after the kernel left_align_indels (viterbi.c:48-96) and the run-length CIGAR
  *   device  lfq_viterbi_kernel: one wavefront per read, lanes along the query, 64 query rows a strip, one anti-diagonal a
  *           step; termination and trace-back by one lane
+ *
+ * lfq_readset_viterbi (lfq_readset.hip) realigns the reads of a resident read set through the same stages: the host walks the
+ * CIGARs (and the qualities of the reads with an indel) only, lfq_vit_gather_kernel builds query, q2def and windows from the
+ * read set's device arrays, and lfq_readset_permute_kernel writes the per-base arrays of the new read set in its read order.
  */
 #include "lfq_ctx.h"
 
@@ -220,6 +224,175 @@ __global__ __launch_bounds__(256) void lfq_viterbi_kernel(LfqVitArgs a)
     }
 }
 
+/* ---- the reads of a resident read set (lfq_readset_viterbi): query, q2def and window built where the bases are ---------- */
+
+struct LfqVitSrc {                          /* one read lfq_vit_gather_kernel works on, beside its LfqVitRead */
+    int64_t read;                           /* its index in the read set */
+    int32_t lower;                          /* window start */
+    int32_t pad_;
+};
+
+struct LfqVitGatherArgs {
+    const LfqVitRead *reads;
+    const LfqVitSrc *src;
+    const int64_t *seq_off, *cigar_off;     /* the read set's device arrays */
+    const uint32_t *cigar;
+    const uint8_t *seq, *qual, *ref;
+    uint8_t *qletter, *qeff, *win;          /* what LfqVitArgs takes */
+    int32_t n;
+    int32_t def_qual;                       /* -q; negative: the median of the read's qualities other than 2 */
+};
+
+/* One wavefront per read, lanes along the bases of a CIGAR operation.  The host has checked every read it lists: M = X I D S
+ * operations only, their query bases inside the read's span of seq / qual, the window inside the contig, no quality above 93
+ * and at least one other than 2.  First walk: the histogram of the qualities other than 2, 94 bins in LDS, and from it
+ * int_median (utils.c:436-457) -- element (m - 1) / 2 and element m / 2 of the sorted values are the same one for an odd
+ * count, and the mean of two qualities truncates like (a + b) / 2.0 does.  Second walk: letters and qualities. */
+__global__ __launch_bounds__(256) void lfq_vit_gather_kernel(LfqVitGatherArgs a)
+{
+    __shared__ int s_hist[4][96];
+    const int lane = threadIdx.x & 63, wl = threadIdx.x >> 6;
+    const int wv = blockIdx.x * 4 + wl;
+    const bool on = wv < a.n;               /* (no early return: the block's barriers below) */
+    int *hist = s_hist[wl];
+    for (int v = lane; v < 96; v += 64) {
+        hist[v] = 0;
+    }
+    __syncthreads();
+    LfqVitRead R = {};
+    LfqVitSrc S = {};
+    int64_t s0 = 0, c0 = 0, c1 = 0;
+    if (on) {
+        R = a.reads[wv];
+        S = a.src[wv];
+        s0 = a.seq_off[S.read];
+        c0 = a.cigar_off[S.read];
+        c1 = a.cigar_off[S.read + 1];
+    }
+    if (on && a.def_qual < 0) {
+        int64_t y = s0;
+        for (int64_t j = c0; j < c1; j++) {
+            const uint32_t cg = a.cigar[j];
+            const int op = (int)(cg & 0xf);
+            const int64_t len = cg >> 4;
+            if (op == 0 || op == 7 || op == 8 || op == 1) {
+                for (int64_t b = lane; b < len; b += 64) {
+                    const int qv = a.qual[y + b];
+                    if (qv != 2 && qv <= LFQ_VIT_MAXQ) {
+                        atomicAdd(&hist[qv], 1);
+                    }
+                }
+                y += len;
+            } else if (op == 4) {
+                y += len;
+            }
+        }
+    }
+    __syncthreads();
+    int q2def = a.def_qual;
+    if (on && a.def_qual < 0) {
+        int m = 0;
+        for (int v = 0; v <= LFQ_VIT_MAXQ; v++) {
+            m += hist[v];
+        }
+        const int i_lo = (m - 1) / 2, i_hi = m / 2;
+        int v_lo = -1, v_hi = -1, seen = 0;
+        for (int v = 0; v <= LFQ_VIT_MAXQ; v++) {       /* element i of the sorted values: the first v with more than i up to it */
+            seen += hist[v];
+            v_lo = (v_lo < 0 && seen > i_lo) ? v : v_lo;
+            v_hi = (v_hi < 0 && seen > i_hi) ? v : v_hi;
+        }
+        q2def = m > 0 ? (v_lo + v_hi) / 2 : 2;
+    }
+    if (on) {
+        int64_t y = s0, z = R.base_off;
+        for (int64_t j = c0; j < c1; j++) {
+            const uint32_t cg = a.cigar[j];
+            const int op = (int)(cg & 0xf);
+            const int64_t len = cg >> 4;
+            if (op == 0 || op == 7 || op == 8 || op == 1) {
+                for (int64_t b = lane; b < len && z + b < R.base_off + R.q; b += 64) {
+                    const uint32_t code = a.seq[y + b];
+                    const int qv = a.qual[y + b];
+                    a.qletter[z + b] = (uint8_t)(code > 15u ? 'N' : LFQ_SEQ_LETTERS[code]);
+                    a.qeff[z + b] = (uint8_t)(qv == 2 ? q2def : qv);
+                }
+                y += len;
+                z += len;
+            } else if (op == 4) {
+                y += len;
+            }
+        }
+        for (int j = lane; j < R.w; j += 64) {
+            const uint32_t ch = a.ref[(int64_t)S.lower + j];
+            a.win[R.win_off + j] = (uint8_t)(ch >= 'a' && ch <= 'z' ? ch - 32u : ch);       /* strtoupper (:161) */
+        }
+    }
+}
+
+#define LFQ_PERMUTE_ARRAYS 4                /* seq, qual, BI, BD */
+struct LfqPermuteArgs {
+    const int64_t *new_off;                 /* [n + 1] seq_off of the new order */
+    const int64_t *old_start;               /* [n] first base of the read at place j in the source arrays */
+    int64_t n_reads, n_bases;
+    int32_t n_arrays, pad_;
+    const uint8_t *src[LFQ_PERMUTE_ARRAYS];
+    uint8_t *dst[LFQ_PERMUTE_ARRAYS];       /* 16-byte aligned, n_bases + 16 bytes */
+};
+
+/* Each lane owns 16 aligned output bytes, finds the read of the first one by binary search in the new offsets (as
+ * lfq_idq_fill_kernel does) and copies from where that read lies in the source.  Source offsets have no alignment: 16 bytes of
+ * one read are one unaligned load that ends inside that read, bytes of a chunk that straddles reads are loaded one by one. */
+__global__ __launch_bounds__(256) void lfq_readset_permute_kernel(LfqPermuteArgs A)
+{
+    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (b0 >= A.n_bases) {
+        return;
+    }
+    int64_t lo = 0, hi = A.n_reads;             /* new_off[lo] <= b0 < new_off[hi] */
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (A.new_off[mid] <= b0) {
+            lo = mid;
+        } else {
+            hi = mid;
+        }
+    }
+    int64_t r = lo, r_begin = A.new_off[r], r_end = A.new_off[r + 1];
+    if (b0 + 16 <= r_end) {
+        const int64_t so = A.old_start[r] + (b0 - r_begin);
+        for (int k = 0; k < A.n_arrays; k++) {
+            uint4 v;
+            __builtin_memcpy(&v, A.src[k] + so, 16);
+            *(uint4 *)(A.dst[k] + b0) = v;
+        }
+        return;
+    }
+    int64_t from[16];                           /* source index of every byte, -1 behind the last base */
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int64_t b = b0 + i;
+        from[i] = -1;
+        if (b < A.n_bases) {
+            while (b >= r_end && r + 1 < A.n_reads) {       /* on to the next read with bases */
+                r++;
+                r_begin = r_end;
+                r_end = A.new_off[r + 1];
+            }
+            from[i] = A.old_start[r] + (b - r_begin);
+        }
+    }
+    for (int k = 0; k < A.n_arrays; k++) {
+        uint32_t out[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const uint32_t v = from[i] >= 0 ? A.src[k][from[i]] : 0u;
+            out[i >> 2] |= v << (8 * (i & 3));
+        }
+        *(uint4 *)(A.dst[k] + b0) = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+}
+
 /* ---- host ------------------------------------------------------------------------------------------------- */
 
 struct LfqViterbiState {
@@ -233,6 +406,8 @@ struct LfqViterbiState {
     uint8_t *d_in = nullptr, *d_ptr = nullptr, *d_states = nullptr;
     double *d_ho = nullptr;
     int64_t in_bytes = 0, ptr_bytes = 0, ho_doubles = 0, states_bytes = 0;
+    int64_t *d_perm = nullptr;              /* lfq_viterbi_permute: where each read of the new order begins in the old one */
+    int64_t perm_words = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     lfq_viterbi_times times;
 };
@@ -256,6 +431,7 @@ void lfq_viterbi_release(lfq_ctx *c)
     if (s->d_ptr) (void)hipFree(s->d_ptr);
     if (s->d_states) (void)hipFree(s->d_states);
     if (s->d_ho) (void)hipFree(s->d_ho);
+    if (s->d_perm) (void)hipFree(s->d_perm);
     for (hipEvent_t e : s->ev) {
         if (e) (void)hipEventDestroy(e);
     }
@@ -325,41 +501,53 @@ struct VitHostRead {
     int32_t q, w;
 };
 
-extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qual, const lfq_viterbi_result **out)
-{
-    if (!c || !rd || !out || rd->n_reads < 0 || def_qual > LFQ_VIT_MAXQ) {
-        return LFQ_ERR_INVALID;
-    }
-    const int64_t n = rd->n_reads;
-    if (n > 0 && (!rd->pos || !rd->cigar_off || !rd->seq_off || !rd->ref || rd->ref_len <= 0)) {
-        return LFQ_ERR_INVALID;
-    }
-    LfqViterbiState *S = vit_state(c);
-    *out = nullptr;
-    S->pos.assign(n, 0);
-    S->status.assign(n, LFQ_VIT_NO_INDEL);
-    S->cigar_off.assign(n + 1, 0);
-    S->cigar.clear();
-    memset(&S->times, 0, sizeof(S->times));
-    S->times.n_reads = n;
-
-    /* ---- fetch_func's walk over the CIGAR (lofreq_viterbi.c:171-248): status, query, q2def, window ---- */
+/* what the walk over the CIGARs leaves for the kernel and for the host stages behind it */
+struct VitPlan {
     std::vector<VitHostRead> work;
-    std::vector<uint8_t> qletter, qeff, win;
     std::vector<LfqVitRead> dev;
+    std::vector<LfqVitSrc> src;                 /* resident reads: where lfq_vit_gather_kernel finds each read */
     std::vector<LfqVitTp> tps;
     std::map<int, int> tp_of_w;
+    std::vector<uint8_t> qletter, qeff, win;    /* host reads: packed here; resident reads: built on the device */
+    int64_t q_total = 0, win_total = 0, st_total = 0;
+    bool packed = true;
+};
+
+/* f(index into seq / qual) for every query base of read r: the bases of its M = X I operations (lofreq_viterbi.c:178-213) */
+template <typename F>
+static void vit_for_query(const lfq_baq_reads *rd, int64_t r, F f)
+{
+    int64_t y = rd->seq_off[r];
+    for (int64_t j = rd->cigar_off[r]; j < rd->cigar_off[r + 1]; j++) {
+        const int64_t len = rd->cigar[j] >> 4;
+        const int op = rd->cigar[j] & 0xf;
+        if (op == 0 || op == 7 || op == 8 || op == 1) {
+            for (int64_t b = 0; b < len; b++) {
+                f(y + b);
+            }
+            y += len;
+        } else if (op == 4) {
+            y += len;
+        }
+    }
+}
+
+/* ---- fetch_func's walk over the CIGAR (lofreq_viterbi.c:171-248): status, query, q2def, window.  pack = false (reads that
+ * are resident on the device): query, q2def and window are left to lfq_vit_gather_kernel; the host looks at the CIGARs and at
+ * the qualities of the reads with an indel only ---- */
+static int vit_scan(LfqViterbiState *S, const lfq_baq_reads *rd, int def_qual, bool pack, VitPlan &P)
+{
+    const int64_t n = rd->n_reads;
     std::vector<int> rem;
-    int64_t st_total = 0;
+    P.packed = pack;
     for (int64_t r = 0; r < n; r++) {
         const int64_t c0 = rd->cigar_off[r], c1 = rd->cigar_off[r + 1], s0 = rd->seq_off[r], s1 = rd->seq_off[r + 1];
         if (c1 < c0 || s1 < s0 || (c1 > c0 && !rd->cigar) || (s1 > s0 && (!rd->seq || !rd->qual))) {
             return LFQ_ERR_INVALID;
         }
-        int64_t x = rd->pos[r], y = 0;
+        int64_t x = rd->pos[r], y = 0, z = 0;
         int indels = 0;
         bool skipped = false;
-        const size_t qbase = qletter.size();
         for (int64_t j = c0; j < c1 && !skipped; j++) {
             const int64_t len = rd->cigar[j] >> 4;
             const int op = rd->cigar[j] & 0xf;
@@ -367,11 +555,8 @@ extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qu
                 if (y + len > s1 - s0) {
                     return LFQ_ERR_INVALID;
                 }
-                for (int64_t b = 0; b < len; b++) {
-                    qletter.push_back((uint8_t)lfq_seq_letter(rd->seq[s0 + y + b]));
-                    qeff.push_back(rd->qual[s0 + y + b]);
-                }
                 y += len;
+                z += len;
                 if (op == 1) {
                     indels++;
                 } else {
@@ -387,18 +572,17 @@ extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qu
             }
         }
         uint8_t status = LFQ_VIT_REALIGNED;
-        const int64_t z = (int64_t)(qletter.size() - qbase);
         if (skipped) {
             status = LFQ_VIT_SKIPPED_OP;
         } else if (indels == 0) {
             status = LFQ_VIT_NO_INDEL;                                  /* :216 */
         } else {
             rem.clear();                                                /* check_Q2 / remain (:79-105) */
-            for (int64_t b = 0; b < z; b++) {
-                if (qeff[qbase + b] != 2) {
-                    rem.push_back(qeff[qbase + b]);
+            vit_for_query(rd, r, [&](int64_t b) {
+                if (rd->qual[b] != 2) {
+                    rem.push_back(rd->qual[b]);
                 }
-            }
+            });
             if (rem.empty()) {
                 status = LFQ_VIT_ALL_Q2;                                /* :221 */
             }
@@ -409,30 +593,42 @@ extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qu
             if (rd->pos[r] < 0 || upper <= lower || z > 0x3fffffff || upper - lower > 0x3fffffff) {
                 return LFQ_ERR_INVALID;
             }
-            int q2def = def_qual;
-            if (q2def < 0) {                                            /* int_median (utils.c:436-457), by counting */
-                int64_t hist[256] = {0};
-                for (int v : rem) {
-                    hist[v]++;
-                }
-                const int64_t m = (int64_t)rem.size();
-                auto at = [&](int64_t idx) {                            /* element idx of the sorted qualities */
-                    int v = 0;
-                    for (int64_t seen = hist[0]; seen <= idx; seen += hist[v]) {
-                        v++;
-                    }
-                    return v;
-                };
-                q2def = m % 2 == 0 ? (int)((at(m / 2) + at(m / 2 - 1)) / 2.0) : at(m / 2);
-            }
-            for (int64_t b = 0; b < z; b++) {
-                uint8_t &e = qeff[qbase + b];
-                if (e == 2) {
-                    e = (uint8_t)q2def;
-                }
-                if (e > LFQ_VIT_MAXQ) {
+            /* a quality above 93 has no emission: q2def, a given value or a median of these, is then in range as well */
+            for (int v : rem) {
+                if (v > LFQ_VIT_MAXQ) {
                     return LFQ_ERR_INVALID;
                 }
+            }
+            if (pack) {
+                int q2def = def_qual;
+                if (q2def < 0) {                                        /* int_median (utils.c:436-457), by counting */
+                    int64_t hist[256] = {0};
+                    for (int v : rem) {
+                        hist[v]++;
+                    }
+                    const int64_t m = (int64_t)rem.size();
+                    auto at = [&](int64_t idx) {                        /* element idx of the sorted qualities */
+                        int v = 0;
+                        for (int64_t seen = hist[0]; seen <= idx; seen += hist[v]) {
+                            v++;
+                        }
+                        return v;
+                    };
+                    q2def = m % 2 == 0 ? (int)((at(m / 2) + at(m / 2 - 1)) / 2.0) : at(m / 2);
+                }
+                vit_for_query(rd, r, [&](int64_t b) {
+                    P.qletter.push_back((uint8_t)lfq_seq_letter(rd->seq[b]));
+                    P.qeff.push_back(rd->qual[b] == 2 ? (uint8_t)q2def : rd->qual[b]);
+                });
+                for (int64_t p = lower; p < upper; p++) {
+                    P.win.push_back((uint8_t)toupper((unsigned char)rd->ref[p]));               /* strtoupper, :161 */
+                }
+            } else {
+                LfqVitSrc s;
+                s.read = r;
+                s.lower = (int32_t)lower;
+                s.pad_ = 0;
+                P.src.push_back(s);
             }
             VitHostRead h;
             h.r = r;
@@ -441,136 +637,166 @@ extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qu
             h.w = (int32_t)(upper - lower);
             LfqVitRead d;
             memset(&d, 0, sizeof(d));
-            d.base_off = (int64_t)qbase;
-            d.win_off = (int64_t)win.size();
-            d.st_off = st_total;
+            d.base_off = P.q_total;
+            d.win_off = P.win_total;
+            d.st_off = P.st_total;
             d.q = h.q;
             d.w = h.w;
-            auto it = tp_of_w.find(h.w);
-            if (it == tp_of_w.end()) {
-                it = tp_of_w.emplace(h.w, (int)tps.size()).first;
-                tps.push_back(vit_transitions(h.w));
+            auto it = P.tp_of_w.find(h.w);
+            if (it == P.tp_of_w.end()) {
+                it = P.tp_of_w.emplace(h.w, (int)P.tps.size()).first;
+                P.tps.push_back(vit_transitions(h.w));
             }
             d.tp_idx = it->second;
-            for (int64_t p = lower; p < upper; p++) {
-                win.push_back((uint8_t)toupper((unsigned char)rd->ref[p]));                     /* strtoupper, :161 */
-            }
-            st_total += (int64_t)h.q + h.w;
-            work.push_back(h);
-            dev.push_back(d);
-        } else {
-            qletter.resize(qbase);
-            qeff.resize(qbase);
+            P.q_total += h.q;
+            P.win_total += h.w;
+            P.st_total += (int64_t)h.q + h.w;
+            P.work.push_back(h);
+            P.dev.push_back(d);
         }
         S->status[r] = status;
         S->pos[r] = rd->pos[r];
     }
+    return LFQ_OK;
+}
 
-    /* ---- the kernel, over the compacted list, in chunks the scratch budget admits ---- */
-    const int64_t nw = (int64_t)work.size();
-    std::vector<uint8_t> states;
-    std::vector<LfqVitOut> outs(nw);
-    S->times.n_realigned = nw;
-    if (nw > 0) {
-        LFQ_TRY_HIP(hipSetDevice(c->device));
-        hipStream_t st = c->stream;
-        double emis[2 * (LFQ_VIT_MAXQ + 1)];
-        for (int qv = 0; qv <= LFQ_VIT_MAXQ; qv++) {                    /* viterbi.c:188-194; SANGERQUAL_TO_PROB, :40 */
-            const double bp = pow(10.0, -0.1 * qv);
-            emis[2 * qv] = log10(1 - bp);
-            emis[2 * qv + 1] = log10(bp / 3.);
-        }
-        /* one upload: descriptors | tables | query letters | qualities | windows */
-        auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-        const int64_t o_dev = 0, o_tp = al(o_dev + nw * (int64_t)sizeof(LfqVitRead));
-        const int64_t o_em = al(o_tp + (int64_t)tps.size() * (int64_t)sizeof(LfqVitTp));
-        const int64_t o_ql = al(o_em + (int64_t)sizeof(emis)), o_qe = al(o_ql + (int64_t)qletter.size());
-        const int64_t o_win = al(o_qe + (int64_t)qeff.size()), o_out = al(o_win + (int64_t)win.size());
-        const int64_t in_total = al(o_out + nw * (int64_t)sizeof(LfqVitOut));
-        LFQ_TRY(grow(&S->d_in, &S->in_bytes, in_total));
-        LFQ_TRY(grow(&S->d_states, &S->states_bytes, st_total));
-        /* chunks: as many reads as the budget -- half of the free memory, at most 32 GiB, or LFQ_BAQ_SCRATCH_MB -- holds */
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        int64_t budget = std::min<int64_t>((int64_t)32 << 30, (int64_t)(free_b / 2));
-        if (lfq_knobs().baq_scratch_mb >= 0) {
-            budget = (int64_t)lfq_knobs().baq_scratch_mb << 20;
-        }
-        std::vector<int64_t> chunk_begin(1, 0);
-        int64_t need_ptr = 0, need_ho = 0, cur_ptr = 0, cur_ho = 0;
-        for (int64_t i = 0; i < nw; i++) {
-            const int64_t pb = (int64_t)((work[i].q + 63) / 64) * lfq_vit_strip_bytes(work[i].w);
-            const int64_t hb = 2 * lfq_vit_ho_row(work[i].w);
-            if (i > chunk_begin.back() && cur_ptr + pb + (cur_ho + hb) * 8 > budget) {
-                chunk_begin.push_back(i);
-                cur_ptr = cur_ho = 0;
-            }
-            dev[i].ptr_off = cur_ptr;
-            dev[i].ho_off = cur_ho;
-            cur_ptr += pb;
-            cur_ho += hb;
-            need_ptr = std::max(need_ptr, cur_ptr);
-            need_ho = std::max(need_ho, cur_ho);
-        }
-        chunk_begin.push_back(nw);
-        LFQ_TRY(grow(&S->d_ptr, &S->ptr_bytes, need_ptr));
-        LFQ_TRY(grow(&S->d_ho, &S->ho_doubles, need_ho));
-        for (hipEvent_t &e : S->ev) {
-            if (!e) {
-                LFQ_TRY_HIP(hipEventCreate(&e));
-            }
-        }
-        LfqPin<uint8_t> pin(c, (size_t)in_total);
-        LFQ_PIN_OK(pin);
-        memcpy(pin.data() + o_dev, dev.data(), (size_t)nw * sizeof(LfqVitRead));
-        memcpy(pin.data() + o_tp, tps.data(), tps.size() * sizeof(LfqVitTp));
-        memcpy(pin.data() + o_em, emis, sizeof(emis));
-        memcpy(pin.data() + o_ql, qletter.data(), qletter.size());
-        memcpy(pin.data() + o_qe, qeff.data(), qeff.size());
-        memcpy(pin.data() + o_win, win.data(), win.size());
-        LFQ_TRY_HIP(hipMemcpyAsync(S->d_in, pin.data(), (size_t)o_out, hipMemcpyHostToDevice, st));
-        LfqVitArgs A;
-        memset(&A, 0, sizeof(A));
-        A.reads = (const LfqVitRead *)(S->d_in + o_dev);
-        A.tp = (const LfqVitTp *)(S->d_in + o_tp);
-        A.emis = (const double *)(S->d_in + o_em);
-        A.qletter = S->d_in + o_ql;
-        A.qeff = S->d_in + o_qe;
-        A.win = S->d_in + o_win;
-        A.ep_ins = log10(.25);                                          /* viterbi.c:130 */
-        A.ptr = S->d_ptr;
-        A.ho = S->d_ho;
-        A.states = S->d_states;
-        A.out = (LfqVitOut *)(S->d_in + o_out);
-        LFQ_TRY_HIP(hipEventRecord(S->ev[0], st));
-        for (size_t ch = 0; ch + 1 < chunk_begin.size(); ch++) {
-            A.first = (int32_t)chunk_begin[ch];
-            A.n = (int32_t)(chunk_begin[ch + 1] - chunk_begin[ch]);
-            hipLaunchKernelGGL(lfq_viterbi_kernel, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, st, A);
-            LFQ_TRY_HIP(hipGetLastError());
-            S->times.n_launches++;
-        }
-        LFQ_TRY_HIP(hipEventRecord(S->ev[1], st));
-        states.resize((size_t)st_total);
-        LfqPin<uint8_t> pin_out(c, (size_t)(st_total + nw * (int64_t)sizeof(LfqVitOut)));
-        LFQ_PIN_OK(pin_out);
-        LFQ_TRY_HIP(hipMemcpyAsync(pin_out.data(), S->d_states, (size_t)st_total, hipMemcpyDeviceToHost, st));
-        LFQ_TRY_HIP(hipMemcpyAsync(pin_out.data() + st_total, S->d_in + o_out, (size_t)nw * sizeof(LfqVitOut),
-                                   hipMemcpyDeviceToHost, st));
-        LFQ_TRY_HIP(hipStreamSynchronize(st));
-        memcpy(states.data(), pin_out.data(), (size_t)st_total);
-        memcpy(outs.data(), pin_out.data() + st_total, (size_t)nw * sizeof(LfqVitOut));
-        LFQ_TRY_HIP(hipEventElapsedTime(&S->times.ms_kernels, S->ev[0], S->ev[1]));
+/* ---- the kernels, over the compacted list, in chunks the scratch budget admits: traced states and where each trace ended.
+ * res = the device arrays of a resident read set, in the read order of the plan, or null (query and windows come from the
+ * plan's host arrays) ---- */
+static int vit_launch(lfq_ctx *c, LfqViterbiState *S, VitPlan &P, int def_qual, const LfqVitResident *res,
+                      std::vector<uint8_t> &states, std::vector<LfqVitOut> &outs)
+{
+    const int64_t nw = (int64_t)P.work.size(), st_total = P.st_total;
+    std::vector<LfqVitRead> &dev = P.dev;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    double emis[2 * (LFQ_VIT_MAXQ + 1)];
+    for (int qv = 0; qv <= LFQ_VIT_MAXQ; qv++) {                    /* viterbi.c:188-194; SANGERQUAL_TO_PROB, :40 */
+        const double bp = pow(10.0, -0.1 * qv);
+        emis[2 * qv] = log10(1 - bp);
+        emis[2 * qv + 1] = log10(bp / 3.);
     }
+    /* one upload: descriptors | tables | sources (resident reads) | query letters | qualities | windows (host reads) */
+    auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
+    const int64_t o_dev = 0, o_tp = al(o_dev + nw * (int64_t)sizeof(LfqVitRead));
+    const int64_t o_em = al(o_tp + (int64_t)P.tps.size() * (int64_t)sizeof(LfqVitTp));
+    const int64_t o_src = al(o_em + (int64_t)sizeof(emis)), o_ql = al(o_src + (int64_t)P.src.size() * (int64_t)sizeof(LfqVitSrc));
+    const int64_t o_qe = al(o_ql + P.q_total), o_win = al(o_qe + P.q_total), o_out = al(o_win + P.win_total);
+    const int64_t in_total = al(o_out + nw * (int64_t)sizeof(LfqVitOut));
+    const int64_t up_total = res ? o_ql : o_out;
+    LFQ_TRY(grow(&S->d_in, &S->in_bytes, in_total));
+    LFQ_TRY(grow(&S->d_states, &S->states_bytes, st_total));
+    /* chunks: as many reads as the budget -- half of the free memory, at most 32 GiB, or LFQ_BAQ_SCRATCH_MB -- holds */
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    int64_t budget = std::min<int64_t>((int64_t)32 << 30, (int64_t)(free_b / 2));
+    if (lfq_knobs().baq_scratch_mb >= 0) {
+        budget = (int64_t)lfq_knobs().baq_scratch_mb << 20;
+    }
+    std::vector<int64_t> chunk_begin(1, 0);
+    int64_t need_ptr = 0, need_ho = 0, cur_ptr = 0, cur_ho = 0;
+    for (int64_t i = 0; i < nw; i++) {
+        const int64_t pb = (int64_t)((P.work[i].q + 63) / 64) * lfq_vit_strip_bytes(P.work[i].w);
+        const int64_t hb = 2 * lfq_vit_ho_row(P.work[i].w);
+        if (i > chunk_begin.back() && cur_ptr + pb + (cur_ho + hb) * 8 > budget) {
+            chunk_begin.push_back(i);
+            cur_ptr = cur_ho = 0;
+        }
+        dev[i].ptr_off = cur_ptr;
+        dev[i].ho_off = cur_ho;
+        cur_ptr += pb;
+        cur_ho += hb;
+        need_ptr = std::max(need_ptr, cur_ptr);
+        need_ho = std::max(need_ho, cur_ho);
+    }
+    chunk_begin.push_back(nw);
+    LFQ_TRY(grow(&S->d_ptr, &S->ptr_bytes, need_ptr));
+    LFQ_TRY(grow(&S->d_ho, &S->ho_doubles, need_ho));
+    for (hipEvent_t &e : S->ev) {
+        if (!e) {
+            LFQ_TRY_HIP(hipEventCreate(&e));
+        }
+    }
+    LfqPin<uint8_t> pin(c, (size_t)up_total);
+    LFQ_PIN_OK(pin);
+    memcpy(pin.data() + o_dev, dev.data(), (size_t)nw * sizeof(LfqVitRead));
+    memcpy(pin.data() + o_tp, P.tps.data(), P.tps.size() * sizeof(LfqVitTp));
+    memcpy(pin.data() + o_em, emis, sizeof(emis));
+    if (res) {
+        memcpy(pin.data() + o_src, P.src.data(), P.src.size() * sizeof(LfqVitSrc));
+    } else {
+        memcpy(pin.data() + o_ql, P.qletter.data(), P.qletter.size());
+        memcpy(pin.data() + o_qe, P.qeff.data(), P.qeff.size());
+        memcpy(pin.data() + o_win, P.win.data(), P.win.size());
+    }
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_in, pin.data(), (size_t)up_total, hipMemcpyHostToDevice, st));
+    LfqVitArgs A;
+    memset(&A, 0, sizeof(A));
+    A.reads = (const LfqVitRead *)(S->d_in + o_dev);
+    A.tp = (const LfqVitTp *)(S->d_in + o_tp);
+    A.emis = (const double *)(S->d_in + o_em);
+    A.qletter = S->d_in + o_ql;
+    A.qeff = S->d_in + o_qe;
+    A.win = S->d_in + o_win;
+    A.ep_ins = log10(.25);                                          /* viterbi.c:130 */
+    A.ptr = S->d_ptr;
+    A.ho = S->d_ho;
+    A.states = S->d_states;
+    A.out = (LfqVitOut *)(S->d_in + o_out);
+    LFQ_TRY_HIP(hipEventRecord(S->ev[0], st));
+    if (res) {
+        LfqVitGatherArgs G;
+        memset(&G, 0, sizeof(G));
+        G.reads = A.reads;
+        G.src = (const LfqVitSrc *)(S->d_in + o_src);
+        G.seq_off = res->d_seq_off;
+        G.cigar_off = res->d_cigar_off;
+        G.cigar = res->d_cigar;
+        G.seq = res->d_seq;
+        G.qual = res->d_qual;
+        G.ref = res->d_ref;
+        G.qletter = S->d_in + o_ql;
+        G.qeff = S->d_in + o_qe;
+        G.win = S->d_in + o_win;
+        G.n = (int32_t)nw;
+        G.def_qual = def_qual;
+        hipLaunchKernelGGL(lfq_vit_gather_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, G);
+        LFQ_TRY_HIP(hipGetLastError());
+    }
+    for (size_t ch = 0; ch + 1 < chunk_begin.size(); ch++) {
+        A.first = (int32_t)chunk_begin[ch];
+        A.n = (int32_t)(chunk_begin[ch + 1] - chunk_begin[ch]);
+        hipLaunchKernelGGL(lfq_viterbi_kernel, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, st, A);
+        LFQ_TRY_HIP(hipGetLastError());
+        S->times.n_launches++;
+    }
+    LFQ_TRY_HIP(hipEventRecord(S->ev[1], st));
+    states.resize((size_t)st_total);
+    LfqPin<uint8_t> pin_out(c, (size_t)(st_total + nw * (int64_t)sizeof(LfqVitOut)));
+    LFQ_PIN_OK(pin_out);
+    LFQ_TRY_HIP(hipMemcpyAsync(pin_out.data(), S->d_states, (size_t)st_total, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(pin_out.data() + st_total, S->d_in + o_out, (size_t)nw * sizeof(LfqVitOut),
+                               hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    memcpy(states.data(), pin_out.data(), (size_t)st_total);
+    memcpy(outs.data(), pin_out.data() + st_total, (size_t)nw * sizeof(LfqVitOut));
+    LFQ_TRY_HIP(hipEventElapsedTime(&S->times.ms_kernels, S->ev[0], S->ev[1]));
+    return LFQ_OK;
+}
 
-    /* ---- left_align_indels, the run-length CIGAR with the clips put back, the new position (:262-321) ---- */
+/* ---- left_align_indels, the run-length CIGAR with the clips put back, the new position (:262-321); the result arrays ---- */
+static int vit_finish(LfqViterbiState *S, const lfq_baq_reads *rd, const VitPlan &P, const std::vector<uint8_t> &states,
+                      const std::vector<LfqVitOut> &outs)
+{
+    const int64_t n = rd->n_reads, nw = (int64_t)P.work.size();
     std::vector<std::vector<uint32_t>> new_cigar((size_t)nw);
     std::vector<int> bad((size_t)LFQ_HOST_PARTS, 0);
     lfq_for_reads(nw, [&](int64_t b, int64_t e, int part) {
         std::vector<char> ar, aq;
+        std::vector<uint8_t> ql;
         for (int64_t i = b; i < e; i++) {
-            const VitHostRead &h = work[(size_t)i];
-            const LfqVitRead &d = dev[(size_t)i];
+            const VitHostRead &h = P.work[(size_t)i];
+            const LfqVitRead &d = P.dev[(size_t)i];
             const LfqVitOut &o = outs[(size_t)i];
             const int cap = h.q + h.w;
             int n_mi = 0, n_md = 0;
@@ -588,11 +814,17 @@ extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qu
                 bad[part] = 1;
                 continue;
             }
+            const uint8_t *query = P.qletter.data() + d.base_off;
+            if (!P.packed) {                                /* resident reads: the letters are taken from the read again */
+                ql.clear();
+                vit_for_query(rd, h.r, [&](int64_t at) { ql.push_back((uint8_t)lfq_seq_letter(rd->seq[at])); });
+                query = ql.data();
+            }
             ar.resize((size_t)o.n_states);
             aq.resize((size_t)o.n_states);
             for (int j = 0; j < o.n_states; j++) {          /* tmp_ref / tmp_query (viterbi.c:281-296) */
-                ar[j] = stv[j] == 2 ? '*' : (char)win[(size_t)d.win_off + k++];
-                aq[j] = stv[j] == 3 ? '*' : (char)qletter[(size_t)d.base_off + qi++];
+                ar[j] = stv[j] == 2 ? '*' : (char)toupper((unsigned char)rd->ref[(int64_t)h.lower + k++]);
+                aq[j] = stv[j] == 3 ? '*' : (char)query[qi++];
             }
             vit_left_align(ar, aq);
             std::vector<uint32_t> &cg = new_cigar[(size_t)i];
@@ -652,7 +884,80 @@ extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qu
     S->res.status = S->status.data();
     S->res.cigar_off = S->cigar_off.data();
     S->res.cigar = S->cigar.data();
+    return LFQ_OK;
+}
+
+/* lfq_viterbi_batch (res = null), and the realignment of lfq_readset_viterbi: rd = the host arrays the read set was made
+ * from, res = its device copies */
+int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *rd, int def_qual, const LfqVitResident *res, const lfq_viterbi_result **out)
+{
+    if (!c || !rd || !out || rd->n_reads < 0 || def_qual > LFQ_VIT_MAXQ) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = rd->n_reads;
+    if (n > 0 && (!rd->pos || !rd->cigar_off || !rd->seq_off || !rd->ref || rd->ref_len <= 0)) {
+        return LFQ_ERR_INVALID;
+    }
+    LfqViterbiState *S = vit_state(c);
+    *out = nullptr;
+    S->pos.assign(n, 0);
+    S->status.assign(n, LFQ_VIT_NO_INDEL);
+    S->cigar_off.assign(n + 1, 0);
+    S->cigar.clear();
+    memset(&S->times, 0, sizeof(S->times));
+    S->times.n_reads = n;
+    VitPlan P;
+    LFQ_TRY(vit_scan(S, rd, def_qual, res == nullptr, P));
+    const int64_t nw = (int64_t)P.work.size();
+    std::vector<uint8_t> states;
+    std::vector<LfqVitOut> outs((size_t)nw);
+    S->times.n_realigned = nw;
+    if (nw > 0) {
+        LFQ_TRY(vit_launch(c, S, P, def_qual, res, states, outs));
+    }
+    LFQ_TRY(vit_finish(S, rd, P, states, outs));
     *out = &S->res;
+    return LFQ_OK;
+}
+
+extern "C" int lfq_viterbi_batch(lfq_ctx *c, const lfq_baq_reads *rd, int def_qual, const lfq_viterbi_result **out)
+{
+    return lfq_viterbi_run(c, rd, def_qual, nullptr, out);
+}
+
+/* the per-base arrays of a read set in a new read order (lfq_readset_viterbi): old_start[j] = where the read at place j begins in
+ * the source arrays (host; it goes down here), new_off = the seq_off of the new order on the device */
+int lfq_viterbi_permute(lfq_ctx *c, int64_t n_reads, int64_t n_bases, const int64_t *d_new_off, const int64_t *old_start,
+                        int n_arrays, const uint8_t *const *src, uint8_t *const *dst)
+{
+    if (n_reads <= 0 || n_bases <= 0 || n_arrays <= 0) {
+        return LFQ_OK;
+    }
+    if (n_arrays > LFQ_PERMUTE_ARRAYS) {
+        return LFQ_ERR_INVALID;
+    }
+    LfqViterbiState *S = vit_state(c);
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    LFQ_TRY(grow(&S->d_perm, &S->perm_words, n_reads));
+    LfqPin<int64_t> pin(c, (size_t)n_reads);
+    LFQ_PIN_OK(pin);
+    memcpy(pin.data(), old_start, (size_t)n_reads * sizeof(int64_t));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_perm, pin.data(), (size_t)n_reads * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    LfqPermuteArgs A;
+    memset(&A, 0, sizeof(A));
+    A.new_off = d_new_off;
+    A.old_start = S->d_perm;
+    A.n_reads = n_reads;
+    A.n_bases = n_bases;
+    A.n_arrays = n_arrays;
+    for (int a = 0; a < n_arrays; a++) {
+        A.src[a] = src[a];
+        A.dst[a] = dst[a];
+    }
+    const int64_t blocks = ((n_bases + 15) / 16 + 255) / 256;
+    hipLaunchKernelGGL(lfq_readset_permute_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY_HIP(hipStreamSynchronize(c->stream));          /* (the pinned offsets go back to the pool) */
     return LFQ_OK;
 }
 

@@ -321,6 +321,13 @@ class ReadSet:
         _lib.check(self.L.lfq_readset_fetch_tags(self.caller.h, self.h, p(lb), p(ai), p(ad), p(fl)), "lfq_readset_fetch_tags")
         return lb, ai, ad, fl
 
+    def viterbi(self, def_qual=-1):
+        """lfq_readset_viterbi (`lofreq viterbi`), before every other step: -> (a NEW ReadSet of the same reads, realigned and
+        stably sorted by new position; the result as viterbi_arrays returns it, in this set's read order; order).  This set
+        is not changed."""
+        from .viterbi import readset_viterbi
+        return readset_viterbi(self, def_qual)
+
     def indelqual(self, mode="dindel", ins_qual=0, del_qual=None):
         """lfq_readset_indelqual (`lofreq indelqual`): BI / BD computed on the device copy, for a read set created without"""
         from .indelqual import readset_indelqual

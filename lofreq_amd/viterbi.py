@@ -40,10 +40,8 @@ def pack_reads(reads, ref):
     return rd, (pos, cig_off, seq_off, cig, seq, qual, ref)
 
 
-def viterbi_arrays(caller, rd, def_qual=-1):
-    """lfq_viterbi_batch on a packed batch -> copies of (pos [n], status [n], cigar_off [n + 1], cigar)"""
-    res = C.POINTER(_lib.ViterbiResult)()
-    _lib.check(_lib.load().lfq_viterbi_batch(caller.h, C.byref(rd), int(def_qual), C.byref(res)), "lfq_viterbi_batch")
+def result_arrays(res):
+    """copies of a context-owned lfq_viterbi_result: (pos [n], status [n], cigar_off [n + 1], cigar)"""
     r = res.contents
     n = int(r.n_reads)
 
@@ -53,6 +51,33 @@ def viterbi_arrays(caller, rd, def_qual=-1):
         return np.frombuffer((C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr), dtype).copy()
     cig_off = arr(r.cigar_off, n + 1, np.int64)
     return arr(r.pos, n, np.int32), arr(r.status, n, np.uint8), cig_off, arr(r.cigar, int(cig_off[-1]), np.uint32)
+
+
+def viterbi_arrays(caller, rd, def_qual=-1):
+    """lfq_viterbi_batch on a packed batch -> copies of (pos [n], status [n], cigar_off [n + 1], cigar)"""
+    res = C.POINTER(_lib.ViterbiResult)()
+    _lib.check(_lib.load().lfq_viterbi_batch(caller.h, C.byref(rd), int(def_qual), C.byref(res)), "lfq_viterbi_batch")
+    return result_arrays(res)
+
+
+def readset_viterbi(rs, def_qual=-1):
+    """lfq_readset_viterbi: the reads of a resident ReadSet realigned into a NEW ReadSet, stably sorted by new position; `rs`
+    stays as it is.  -> (the new ReadSet, the result in the form viterbi_arrays returns and in the INPUT read order, order:
+    int64 [n], order[j] = input index of the read at place j of the new set)"""
+    res = C.POINTER(_lib.ViterbiResult)()
+    h, order_p = C.c_void_p(), C.c_void_p()
+    _lib.check(rs.L.lfq_readset_viterbi(rs.caller.h, rs.h, int(def_qual), C.byref(h), C.byref(res), C.byref(order_p)),
+               "lfq_readset_viterbi")
+    result = result_arrays(res)
+    n = rs.n
+    order = (np.frombuffer((C.c_char * (n * 8)).from_address(order_p.value), np.int64).copy() if n else np.zeros(0, np.int64))
+    new = type(rs).__new__(type(rs))
+    new.caller, new.L, new.n, new.h = rs.caller, rs.L, n, h
+    new._keep = {}                                  # the new read set owns its host arrays
+    lens = np.diff(np.asarray(rs.seq_off, np.int64))[:n]
+    new.seq_off = np.concatenate([[0], np.cumsum(lens[order])]).astype(np.int64)
+    rs.caller._readsets.add(new)
+    return new, result, order
 
 
 def viterbi_batch(caller, reads, ref, def_qual=-1):

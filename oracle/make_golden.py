@@ -855,6 +855,61 @@ def run_baq_iupac(name, seed):
     print("%s: %d reads, %d with ai, %d bytes" % (name, len(out), sum(1 for r in out if r["ai"]), os.path.getsize(path)))
 
 
+def run_baq_edges(name, max_bytes=120 * 1024):
+    """the reads of the BAQ boundary table (tests/baq_edges.py) -> `lofreq alnqual` -> lb / ai / ad of every read.  A read SAM
+    text cannot hold (no bases; a quality above 93) is named under "not_in_sam", a read the binary leaves without an lb tag
+    under "untagged"; "reads" holds the others, each with its table row.  The whole table where it fits into max_bytes,
+    else up to `per_row` representative reads of every row (baq_edges.representatives; the header field "coverage" says
+    which, "per_row" how many).  A read with an indel beyond the caps of the device's indel table (baq_edges.idaq_table)
+    goes to "reads_beyond_caps" with the binary's tags: there the library's documented result differs from the binary's
+    (include/lofreq_amd.h, lfq_baq_idaq_batch), so only the oracle is held to those tags."""
+    sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+    import baq_edges as be
+    genome = be.CONTIG.decode()
+    table = be.boundary_table()
+    for per_row in (None, 16, 12, 8):
+        in_sam = lambda r: len(r["seq"]) > 0 and int(r["qual"].max()) <= 93
+        not_in_sam = [r["name"] for row in table for r in row.reads if not in_sam(r)]         # of the whole table
+        picked = [(row.name, r) for row in table
+                  for r in (row.reads if per_row is None else be.representatives(row, per_row)) if in_sam(r)]
+        with tempfile.TemporaryDirectory() as tmp:
+            open(os.path.join(tmp, "t.fa"), "w").write(">chr1\n" + genome + "\n")
+            with open(os.path.join(tmp, "t.sam"), "w") as f:
+                f.write("@HD\tVN:1.0\tSO:unsorted\n@SQ\tSN:chr1\tLN:%d\n" % len(genome))
+                for i, (_, r) in enumerate(picked):
+                    f.write("%d:%s\t0\tchr1\t%d\t60\t%s\t*\t0\t0\t%s\t%s\n" % (
+                        i, r["name"], r["pos0"] + 1, "".join("%d%s" % (l, op) for op, l in r["cigar"]),
+                        "".join(be.LETTERS[c] for c in r["seq"]), "".join(chr(33 + int(q)) for q in r["qual"])))
+            subprocess.check_call([LOFREQ, "faidx", "t.fa"], cwd=tmp)
+            sam = subprocess.run([LOFREQ, "alnqual", "t.sam", "t.fa"], cwd=tmp, check=True, capture_output=True, text=True).stdout
+        out, beyond, untagged = [], [], []
+        for line in sam.splitlines():
+            if line.startswith("@"):
+                continue
+            f = line.split("\t")
+            tags = {t[:2]: t[5:] for t in f[11:]}
+            i, rname = f[0].split(":", 1)
+            if tags.get("lb") is None:
+                untagged.append(rname)
+                continue
+            capped = any(not x[3] for x in be.idaq_table(picked[int(i)][1], be.CONTIG, be.REF_LEN))
+            (beyond if capped else out).append({"name": rname, "row": picked[int(i)][0], "pos0": int(f[3]) - 1, "flag": int(f[1]), "cigar": f[5],
+                        "seq": f[9], "qual": f[10], "lb": tags.get("lb"), "ai": tags.get("ai"), "ad": tags.get("ad")})
+        assert len(out) + len(beyond) + len(untagged) == len(picked)
+        fix = {"name": name, "generator": "oracle/make_golden.py", "reference_binary": "lofreq 2.1.4 (dist tgz)",
+               "alnqual_args": [], "coverage": "the whole table" if per_row is None else "representative reads of every row", "per_row": per_row,
+               "not_in_sam": not_in_sam, "untagged": untagged, "genome": genome, "reads": out,
+               "reads_beyond_caps": beyond}
+        text = json.dumps(fix, separators=(",", ":"))
+        if len(text) <= max_bytes:
+            break
+    path = os.path.join(OUT, name + ".json")
+    open(path, "w").write(text)
+    print("%s: %s, %d reads + %d beyond the caps, %d untagged, %d not in SAM, %d with ai, %d with ad, %d bytes"
+          % (name, fix["coverage"], len(out), len(beyond), len(untagged), len(not_in_sam), sum(1 for r in out if r["ai"]),
+             sum(1 for r in out if r["ad"]), os.path.getsize(path)))
+
+
 def main_baq():
     mq_mix = [60] * 24 + [40, 30, 20, 10, 0, 255]
     sites = {70: [("+", "AC", 0.10)], 100: [("-", 3, 0.08)], 130: [("+", "G", 0.03), ("+", "GGT", 0.03)],
@@ -863,6 +918,7 @@ def main_baq():
     run_baq("baq_extended", 31, 330, 250, sites, mq_mix)
     run_baq("baq_plain", 32, 330, 250, sites, mq_mix, extra=("-e",))
     run_baq_iupac("baq_iupac", 33)
+    run_baq_edges("baq_edges")
 
 
 # ---- real-size fixtures: the reads are NOT stored, only how to make them (tests/golden_reads.py) ------------------------------
@@ -922,6 +978,8 @@ def main():
         return main_indels()
     if "--baq-only" in sys.argv:
         return main_baq()
+    if "--baq-edges-only" in sys.argv:
+        return run_baq_edges("baq_edges")
     if "--chain-only" in sys.argv:
         return main_chain()
     if "--pileup-only" in sys.argv:

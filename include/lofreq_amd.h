@@ -42,6 +42,7 @@ extern "C" {
 /* 7: lfq_set_max_depth, lfq_readset_kept_reads. */
 /* 8: lfq_viterbi_batch, lfq_last_viterbi_times. */
 /* 9: lfq_indelqual_batch, lfq_readset_indelqual, lfq_readset_fetch_indelquals, lfq_last_indelqual_times. */
+/* (10 still: lfq_readset_pileup_sites, lfq_readset_uniq, lfq_last_sites_times are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -781,13 +782,85 @@ int lfq_uniq_detlim_batch(lfq_ctx *ctx, const lfq_tracks *tracks, int tracks_on_
  * binom(coverage, alt_count, af) = P(X <= alt_count), X ~ Binomial(coverage, af) (binom.c:52-69 -> cdflib90's cdfbin),
  * uq_out[col] = PROB_TO_PHREDQUAL_SAFE(pvalue), the value of the UQ= INFO tag; -1 where the reference adds none
  * (coverage < 1, or cdfbin rejects its arguments).  SNVs only (indel variants take their count from the event table,
- * which is host data: lfq_indel_columns).  lfq_uniq_mtc then decides PASS / uq_<mtc> like apply_uniq_filter_mtc:
+ * which is host data: lfq_indel_columns; lfq_readset_uniq below counts them on the device).  lfq_uniq_mtc then decides PASS / uq_<mtc> like apply_uniq_filter_mtc:
  * mtc_type 1 bonf, 2 holm, 3 fdr (multtest.h; `lofreq uniq` defaults: fdr, alpha 0.001, ntests 0 = the number of
  * variants).  lfq_binom_cdf is the scalar test itself (status: cdfbin's code, 0 = ok). */
 int lfq_uniq_binom_batch(lfq_ctx *ctx, const lfq_tracks *tracks, int tracks_on_device, const float *af,
                          const char *alt_base, int32_t *uq_out, double *pvalue_or_null);
 int lfq_uniq_mtc(const int32_t *uq, int64_t n, int mtc_type, double alpha, int64_t ntests, uint8_t *pass);
 double lfq_binom_cdf(int n, int k, double pr, int *status_or_null);
+
+/* --- `lofreq uniq` on the reads of a resident read set (the read-level road to the two tests above) ----------------------
+ * The reference runs one index query and one 1-bp mpileup per variant (lofreq_uniq.c:695-728).  Here: the reads of the
+ * variants' span in ONE read set (the other sample's, filtered by the caller as uniq's mpileup filters them: MAPQ >= 1, no
+ * orphans unless --use-orphan, the flag mask; no BAQ), and one sparse pileup for all variants.
+ *
+ * lfq_readset_pileup_sites: the pileup of a resident read set at a LIST of reference positions: column i = site i, in the order
+ * given (any order, duplicates allowed); a site no read covers is an EMPTY column (mpileup would not call back at all).
+ * tracks_out gets device tracks with ncols = n_sites: nt one byte per observation (LFQ_TRACKS_NT_PACKED is never set: the
+ * columns are few and scattered, and both uniq entry points read unpacked tracks), the observations of a column in pileup
+ * (read) order with the bytes lfq_readset_pileup_snv writes, ref_base from the contig, coverage_plp / num_bases as that function
+ * sets them, baq always there (255 = missing where the read set has no BAQ), sq when the read set has source qualities.
+ * coverage_plp_out_or_null / num_tails_out_or_null: [n_sites] host arrays; num_tails counts the entries that are the last
+ * aligned base of their read (plp.c:912-920).  The buffers are the context's own, grow only, and are valid until the next
+ * lfq_readset_pileup_sites or lfq_readset_uniq call on the context; they are NOT those of the region pileup:
+ * lfq_pileup_skip_snv_columns and tracks returned earlier by lfq_readset_pileup_snv are untouched.  The call returns when the
+ * tracks are complete.  Two kernels whatever the number of sites; per site 16 bytes come back between them and 21 go down.
+ * LFQ_ERR_INVALID, before anything is launched: a NULL ctx, rs or tracks_out (before a device is touched); n_sites < 0; NULL
+ * site_pos with n_sites > 0; a position outside [0, ref_len); reads that are not position-sorted (lfq_set_pileup_unsorted does
+ * not apply); a context cap (lfq_set_max_depth) under which lfq_readset_kept_reads drops at least one read -- the reference
+ * applies -d to the reads of each 1-bp query, not to the region's, and that rule is not approximated.  n_sites = 0: LFQ_OK, no
+ * launch, ncols = 0. */
+int lfq_readset_pileup_sites(lfq_ctx *ctx, lfq_readset *rs, const int64_t *site_pos, int64_t n_sites, int min_plp_bq,
+                             lfq_tracks *tracks_out, int32_t *coverage_plp_out_or_null, int32_t *num_tails_out_or_null);
+
+/* lfq_readset_uniq: uniq_snv (lofreq_uniq.c:222-394) for all variants at once, SNVs and indels, both modes.
+ *   is_indel = strlen(REF) > 1 || strlen(ALT) > 1 || the INDEL key (vcf.c:328-337).
+ *   coverage = coverage_plp, minus num_tails for an indel variant (:248-251); coverage < 1: no tag, no flag (:252-254), in BOTH
+ *      modes -- with --use-det-lim an indel variant whose reads all end at the site has a non-empty column and detectable = 0.
+ *   Default mode (use_det_lim = 0): alt_count = base_count of ALT[0] for an SNV (the nucleotide-count kernel of
+ *      lfq_uniq_binom_batch), for an indel variant the number of pileup entries whose indel is the variant's (:343-368): the
+ *      entry's position is the last of its M / = / X / D / N operation and an I or D follows (a P in between as htslib's
+ *      resolve_cigar2 takes it), whatever the base's quality and BI / BD (uniq's min_plp_idq is 0, :460); an insertion's key is
+ *      the inserted read letters (an ambiguity code is its own letter), a deletion's the contig letters pos + 1 .. pos + len
+ *      upper-cased, 'N' beyond ref_len (plp.c:1091-1094, 1135-1138); a match is bytewise equality with REF + 1 if strlen(REF) >
+ *      strlen(ALT), else ALT + 1; an empty key matches nothing.  Then pvalue = lfq_binom_cdf(coverage, alt_count, af) with the
+ *      AF reset of :262-268, and uq = PROB_TO_PHREDQUAL_SAFE(pvalue); uq = -1 and pvalue = -1.0 where the reference adds no tag.
+ *      detectable = 0.
+ *   --use-det-lim (use_det_lim != 0): lfq_uniq_detlim_batch on the device tracks; alt_count = 0, uq = -1, pvalue = -1.0.
+ *   Deletion keys and the reference's binary: `lofreq uniq` opens no FASTA, so its mpileup has no contig and the key of EVERY
+ *      deletion is 'N' repeated there (plp.c:1136); here the key comes from the read set's contig.  The two agree where the
+ *      contig holds N (or is all N, which the default mode reads for nothing else); INTEGRATION.md section 8.
+ * One sparse pileup (lfq_readset_pileup_sites with the variants' keys, the event match done in its count pass); no
+ * per-observation byte crosses the link in either direction.  The read-level filters are the caller's, as for every read set.
+ * LFQ_ERR_INVALID, before anything is launched: a NULL ctx, rs, vars or out (before a device is touched); n < 0; a NULL array of
+ * vars with n > 0 (indel_key_or_null excepted); offsets that decrease; a NaN in af; and everything lfq_readset_pileup_sites
+ * refuses.  n = 0: LFQ_OK, no launch.  More than one contig per call, VCF text and the per-query -d rule are not covered. */
+typedef struct lfq_uniq_variants {
+    int64_t n;
+    const int64_t *pos;               /* [n] var->pos, 0-based */
+    const int64_t *ref_off, *alt_off; /* [n + 1] into ref / alt */
+    const char *ref, *alt;            /* REF / ALT strings, concatenated, no NULs */
+    const uint8_t *indel_key_or_null; /* [n] vcf_var_has_info_key(var, "INDEL"); NULL = none has it */
+    const float *af;                  /* [n] strtof of AF, or --uni-freq */
+} lfq_uniq_variants;
+typedef struct lfq_uniq_result {      /* caller's arrays, [n] each, any may be NULL */
+    int32_t *coverage;    /* coverage_plp, minus num_tails for an indel variant (lofreq_uniq.c:248-251); 0 = uncovered */
+    int32_t *alt_count;   /* default mode: base_count of ALT[0], or the event count of an indel variant */
+    int32_t *uq;          /* default mode: the UQ= value; -1 where the reference adds no tag */
+    double *pvalue;       /* default mode: binom()'s value, -1.0 where none */
+    uint8_t *detectable;  /* --use-det-lim: 1 where the reference adds UNIQ */
+} lfq_uniq_result;
+int lfq_readset_uniq(lfq_ctx *ctx, lfq_readset *rs, const lfq_uniq_variants *vars, int use_det_lim, int min_plp_bq,
+                     lfq_uniq_result *out);
+/* the two kernels of the context's last lfq_readset_pileup_sites / lfq_readset_uniq call on the device's clock, the call's sites
+ * and the observations of its columns; n_launches = 0 (and 0 ms) where nothing was launched */
+typedef struct lfq_sites_times {
+    double count_ms, scatter_ms;
+    int64_t n_sites, n_obs;
+    int n_launches;
+} lfq_sites_times;
+int lfq_last_sites_times(lfq_ctx *ctx, lfq_sites_times *t);
 
 /* --- synthetic workload (bench / tests): fills device tracks per include/lofreq_synth.h --- */
 int lfq_synth_fill_device(lfq_ctx *ctx, uint64_t seed, uint32_t depth, uint32_t plant_period,

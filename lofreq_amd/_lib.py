@@ -93,6 +93,21 @@ class IndelqualTimes(C.Structure):
     _fields_ = [("ms_kernels", C.c_float), ("n_launches", C.c_int32), ("n_reads", C.c_int64), ("n_bases", C.c_int64)]
 
 
+class UniqVariants(C.Structure):
+    """lfq_uniq_variants"""
+    _fields_ = [("n", C.c_int64)] + [(n, C.c_void_p) for n in ("pos", "ref_off", "alt_off", "ref", "alt", "indel_key_or_null", "af")]
+
+
+class UniqResult(C.Structure):
+    """lfq_uniq_result: the caller's arrays"""
+    _fields_ = [(n, C.c_void_p) for n in ("coverage", "alt_count", "uq", "pvalue", "detectable")]
+
+
+class SitesTimes(C.Structure):
+    _fields_ = [("count_ms", C.c_double), ("scatter_ms", C.c_double), ("n_sites", C.c_int64), ("n_obs", C.c_int64),
+                ("n_launches", C.c_int)]
+
+
 class PileupReads(C.Structure):
     _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in (
         "pos", "cigar_off", "cigar", "seq_off", "seq", "qual", "baq", "mapq", "reverse", "ref")] + [("ref_len", C.c_int64),
@@ -159,6 +174,7 @@ EXPORTS = [
     "lfq_readset_pileup_snv", "lfq_readset_pileup_indels", "lfq_readset_fetch_tags",
     "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
     "lfq_readset_viterbi",
+    "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_indelqual_batch", "lfq_readset_indelqual", "lfq_readset_fetch_indelquals", "lfq_last_indelqual_times",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
@@ -292,6 +308,9 @@ def load():
     L.lfq_readset_pileup_snv.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.POINTER(Tracks), vp]
     L.lfq_readset_pileup_indels.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.POINTER(IndelColumnsC)), vp]
     L.lfq_readset_fetch_tags.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lfq_readset_pileup_sites.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.POINTER(Tracks), vp, vp]
+    L.lfq_readset_uniq.argtypes = [vp, vp, C.POINTER(UniqVariants), C.c_int, C.c_int, C.POINTER(UniqResult)]
+    L.lfq_last_sites_times.argtypes = [vp, C.POINTER(SitesTimes)]
     L.lfq_set_max_depth.argtypes = [vp, C.c_int64]
     L.lfq_readset_kept_reads.argtypes = [vp, vp, vp, C.POINTER(C.c_int64)]
     L.lfq_source_qual_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, C.c_int, vp, vp, vp]

@@ -482,6 +482,11 @@ void lfq_destroy(lfq_ctx *c)
         }
         if (c->h_pin2) (void)hipHostFree(c->h_pin2);
         if (c->d_detlim) (void)hipFree(c->d_detlim);
+        if (c->d_sites_in) (void)hipFree(c->d_sites_in);
+        if (c->d_sites_out) (void)hipFree(c->d_sites_out);
+        for (int i = 0; i < 4; i++) {
+            if (c->ev_sites_t[i]) (void)hipEventDestroy(c->ev_sites_t[i]);
+        }
         if (c->ev_baq_t[0]) (void)hipEventDestroy(c->ev_baq_t[0]);
         if (c->ev_baq_t[1]) (void)hipEventDestroy(c->ev_baq_t[1]);
         if (c->ev_idq_t[0]) (void)hipEventDestroy(c->ev_idq_t[0]);
@@ -1491,6 +1496,114 @@ int lfq_uniq_binom_batch(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_device,
         if (pvalue_or_null) {
             pvalue_or_null[i] = pv;
         }
+    }
+    return LFQ_OK;
+}
+
+/* uniq_snv (lofreq_uniq.c:222-394) for every variant of a list on the reads of a resident read set: one sparse pileup whose
+ * count pass also counts the entries carrying each indel variant's event, then the arithmetic of the two calls above */
+int lfq_readset_uniq(lfq_ctx *c, lfq_readset *rs, const lfq_uniq_variants *v, int use_det_lim, int min_plp_bq,
+                     lfq_uniq_result *out)
+{
+    if (!c || !rs || !v || !out || v->n < 0
+        || (v->n > 0 && (!v->pos || !v->ref_off || !v->alt_off || !v->ref || !v->alt || !v->af))) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = v->n;
+    if (n == 0) {
+        lfq_tracks none;
+        return lfq_readset_sites_impl(c, rs, nullptr, 0, min_plp_bq, nullptr, nullptr, nullptr, &none, nullptr, nullptr, nullptr, nullptr);
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (v->ref_off[i + 1] < v->ref_off[i] || v->alt_off[i + 1] < v->alt_off[i] || v->af[i] != v->af[i]) {
+            return LFQ_ERR_INVALID;
+        }
+    }
+    /* the keys find_del_sequence / find_ins_sequence are asked for (:343-368): REF + 1 of a deletion, else ALT + 1 */
+    std::vector<uint8_t> is_indel((size_t)n), key_del((size_t)n);
+    std::vector<int64_t> key_off((size_t)n + 1, 0);
+    std::vector<char> key_chars;
+    bool any_indel = false, any_snv = false;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t rl = v->ref_off[i + 1] - v->ref_off[i], al = v->alt_off[i + 1] - v->alt_off[i];
+        is_indel[(size_t)i] = (rl > 1 || al > 1 || (v->indel_key_or_null && v->indel_key_or_null[i])) ? 1 : 0;   /* vcf.c:328-337 */
+        key_del[(size_t)i] = 0;
+        if (is_indel[(size_t)i]) {
+            any_indel = true;
+            const bool del = rl > al;
+            key_del[(size_t)i] = del ? 1 : 0;
+            const char *s = del ? v->ref + v->ref_off[i] : v->alt + v->alt_off[i];
+            const int64_t l = del ? rl : al;
+            if (l > 1) {
+                key_chars.insert(key_chars.end(), s + 1, s + l);
+            }
+        } else {
+            any_snv = true;
+        }
+        key_off[(size_t)i + 1] = (int64_t)key_chars.size();
+    }
+    const bool keys = any_indel && !use_det_lim;        /* the event count is read in the default mode only */
+    key_chars.push_back('\0');
+    lfq_tracks T;
+    std::vector<int32_t> cov((size_t)n), nb((size_t)n), tails((size_t)n), ev((size_t)n, 0);
+    LFQ_TRY(lfq_readset_sites_impl(c, rs, v->pos, n, min_plp_bq, keys ? key_off.data() : nullptr, key_chars.data(),
+                                   key_del.data(), &T, cov.data(), nb.data(), tails.data(), keys ? ev.data() : nullptr));
+    for (int64_t i = 0; i < n; i++) {
+        cov[(size_t)i] -= is_indel[(size_t)i] ? tails[(size_t)i] : 0;                  /* :248-251 */
+        if (out->coverage) out->coverage[i] = cov[(size_t)i];
+        if (out->alt_count) out->alt_count[i] = 0;
+        if (out->uq) out->uq[i] = -1;
+        if (out->pvalue) out->pvalue[i] = -1.0;
+        if (out->detectable) out->detectable[i] = 0;
+    }
+    if (use_det_lim) {
+        std::vector<uint8_t> det((size_t)n);
+        LFQ_TRY(lfq_uniq_detlim_batch(c, &T, 1, v->af, det.data(), nullptr));
+        for (int64_t i = 0; i < n && out->detectable; i++) {
+            out->detectable[i] = (cov[(size_t)i] >= 1 && det[(size_t)i]) ? 1 : 0;      /* :252-254 comes first */
+        }
+        return LFQ_OK;
+    }
+    LfqPin<int32_t> h_nt(c, any_snv ? (size_t)n * 4 : 0);
+    LFQ_PIN_OK(h_nt);
+    if (any_snv) {
+        LfqTracksDev D;
+        memset(&D, 0, sizeof(D));
+        D.nt = T.nt;
+        D.bq = T.bq;
+        D.col_off = T.col_off;
+        D.ncols = n;
+        D.nt_packed = 0;
+        LFQ_TRY(grow(&c->d_counts, &c->counts_cap, n));             /* reused as int32[4] per column, as lfq_uniq_binom_batch does */
+        int32_t *d_nt = reinterpret_cast<int32_t *>(c->d_counts);
+        LFQ_TRY(lfq_launch_ntcount(D, d_nt, c->stream));
+        LFQ_TRY_HIP(hipMemcpyAsync(h_nt.data(), d_nt, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+        LFQ_TRY_HIP(hipStreamSynchronize(c->stream));
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (cov[(size_t)i] < 1) {
+            continue;                                               /* :252-254 */
+        }
+        int alt_count;
+        if (is_indel[(size_t)i]) {
+            alt_count = ev[(size_t)i];
+        } else {
+            const char ab = v->alt_off[i + 1] > v->alt_off[i] ? v->alt[v->alt_off[i]] : '\0';
+            const int code = (ab == 'A' || ab == 'a') ? 0 : (ab == 'C' || ab == 'c') ? 1 : (ab == 'G' || ab == 'g') ? 2
+                             : (ab == 'T' || ab == 't') ? 3 : 4;
+            const int32_t *cn = &h_nt[(size_t)i * 4];
+            /* bam_nt4_table sends every other letter to N: the observations in none of the four counts (see lfq_uniq_binom_batch) */
+            const int64_t n_col = nb[(size_t)i];
+            alt_count = code < 4 ? cn[code] : (int)(n_col - cn[0] - cn[1] - cn[2] - cn[3]);
+        }
+        if (out->alt_count) out->alt_count[i] = alt_count;
+        int st = 0;
+        const double pv = lfq_binom_cdf(cov[(size_t)i], alt_count, (double)lfq_uniq_reset_af(v->af[i]), &st);   /* :262-268, :381 */
+        if (st != 0) {
+            continue;                                               /* "binom() failed": no UQ tag */
+        }
+        if (out->uq) out->uq[i] = phred_safe(pv);                   /* :386 */
+        if (out->pvalue) out->pvalue[i] = pv;
     }
     return LFQ_OK;
 }

@@ -358,6 +358,12 @@ struct lfq_ctx {
     float *d_detlim;
     int64_t detlim_cap;
     int32_t *d_plp_nb;               /* num_bases of the tracks last handed out, and their column count */
+    /* lfq_readset_pileup_sites / lfq_readset_uniq: site list, windows, counts and keys; the tracks handed out (both grow-only, and
+     * not d_plp_in / d_plp_out: the region pileup's tracks stay as they are) */
+    uint8_t *d_sites_in, *d_sites_out;
+    int64_t sites_in_bytes, sites_out_bytes;
+    hipEvent_t ev_sites_t[4];        /* around the count pass, around the scatter pass (created on first use) */
+    lfq_sites_times sites_times;     /* sites, observations and launches of the last call (the ms: from the events, when asked for) */
     int64_t plp_ncols;
     /* BAQ scratch (lfq_baq_batch), kept between calls */
     double *d_baq_scr;
@@ -462,6 +468,11 @@ int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);
 int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr, lfq_col_counts *d_counts,
                           lfq_col_pvals *d_pvals, int64_t pvals_capacity, void *stream_or_null, bool indel_mode);
 int lfq_stage_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_device, lfq_tracks *dev_out);
+/* lfq_readset_pileup_sites (lfq_readset.hip), with the event match of lfq_readset_uniq: key_off null = no keys; ev_out gets the
+ * matching entries per site */
+int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos, int64_t n_sites, int min_plp_bq,
+                           const int64_t *key_off, const char *key_chars, const uint8_t *key_del, lfq_tracks *out,
+                           int32_t *cov_out, int32_t *nb_out, int32_t *tails_out, int32_t *ev_out);
 }
 
 #endif

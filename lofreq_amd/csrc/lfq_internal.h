@@ -346,6 +346,30 @@ struct LfqPlpIndelArgs {
 };
 int lfq_launch_plp_indel(const LfqPlpIndelArgs &a, int scatter, void *stream);
 int lfq_launch_plp_indel_columns(const LfqPlpIndelArgs &a, int scatter, void *stream);
+/* the pileup at a LIST of positions (lfq_readset_pileup_sites / lfq_readset_uniq): position-sorted reads only, one wavefront
+ * per site, column i = site i.  Count pass: counts + win; scatter pass: the kept bases to col_off[i] + rank */
+struct LfqSitesArgs {
+    int64_t n_reads;
+    const int32_t *pos, *pmax_end;        /* [n] see LfqPileupArgs */
+    const int64_t *cigar_off, *seq_off;
+    const uint32_t *cigar;
+    const uint8_t *seq, *qual, *baq;      /* baq: lb tag bytes or null */
+    const uint8_t *mapq, *reverse, *sq;   /* [n]; sq: source quality byte or null */
+    const uint8_t *ref;                   /* the contig (deletion keys) */
+    int64_t ref_len;
+    int64_t n_sites;
+    const int64_t *site_pos;              /* [n_sites] */
+    int32_t min_plp_bq;
+    /* event match (null key_off: none): the key of site i is key_chars[key_off[i] .. key_off[i + 1]), a deleted reference
+     * sequence where key_del[i] != 0, else an inserted one */
+    const int64_t *key_off;
+    const uint8_t *key_chars, *key_del;
+    int32_t *counts;                      /* [4][n_sites] coverage_plp | num_bases | num_tails | matching events */
+    int64_t *win;                         /* [n_sites][2] the window of reads the count pass found */
+    const uint64_t *col_off;              /* [n_sites + 1] scatter pass */
+    uint8_t *t_nt, *t_bq, *t_baq, *t_mq, *t_sq;
+};
+int lfq_launch_pileup_sites(const LfqSitesArgs &a, int scatter, void *stream);
 /* the kept reads of a -d cap as the pileup kernels take them (read_idx / pos / pmax_end of LfqPileupArgs): keep[r] != 0 for a
  * kept read; kept_idx / kept_pos / kept_pmax get one entry per kept read.  scratch: lfq_keep_compact_scratch(n) bytes, whose
  * first n int32 the caller fills with the reads' exclusive ends (computed on the host with the keep decision) */

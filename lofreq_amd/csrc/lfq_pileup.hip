@@ -1146,6 +1146,127 @@ int lfq_launch_plp_indel_columns(const LfqPlpIndelArgs &a, int scatter, void *st
 }
 
 
+/* ---- the pileup at a LIST of positions (lfq_readset_pileup_sites, lfq_readset_uniq) ----------------------------------------
+ * `lofreq uniq` looks at the other sample at the positions of a few thousand variants: a sparse gather over the sorted read
+ * list, where the tile kernels above would resolve 64 positions to use one.  One wavefront per site, the window walk of
+ * lfq_pileup_columns_kernel.  Count pass: the two wave-wide searches, then per site coverage_plp, num_bases, num_tails (is_tail
+ * of an entry that is not a deletion, plp.c:912-920) and -- with keys -- the entries whose indel IS the variant's
+ * (lofreq_uniq.c:343-368: find_ins_sequence / find_del_sequence on the key compile_plp_col builds, plp.c:1069-1168), all by
+ * ballots; the window is kept for the scatter pass, which writes the kept bases to col_off[site] + rank in read order with the
+ * bytes of lfq_pileup_columns_kernel<true>.  No atomics.  Both passes resolve an entry with lfq_plp_locate_indel, so that they
+ * agree on every kept base by construction.
+ * An entry carries its indel whatever its base quality (check_indel comes after base_skip), and uniq's min_plp_idq is 0: BI / BD
+ * are not read.  Latency-bound: window -> cigar_off -> CIGAR words -> seq_off -> quality byte are dependent loads. */
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void lfq_pileup_sites_kernel(LfqSitesArgs A)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.n_sites) {
+        return;
+    }
+    const int64_t p = A.site_pos[i];
+    int64_t lo, hi;
+    uint64_t base = 0;
+    uint32_t room = 0;
+    if (SCATTER) {
+        base = A.col_off[i];
+        room = (uint32_t)(A.col_off[i + 1] - base);
+        if (room == 0) {
+            return;
+        }
+        lo = A.win[2 * i];
+        hi = A.win[2 * i + 1];
+    } else {
+        lo = lfq_wave_first_above(A.pmax_end, 0, A.n_reads, p, lane);
+        hi = lfq_wave_first_above(A.pos, lo, A.n_reads, p, lane);
+    }
+    int64_t koff = 0;
+    int klen = 0;
+    bool kdel = false;
+    if (!SCATTER && A.key_off) {
+        koff = A.key_off[i];
+        klen = (int)(A.key_off[i + 1] - koff);
+        kdel = A.key_del[i] != 0;
+    }
+    uint32_t n_cov = 0, n_kept = 0, n_tail = 0, n_ev = 0;
+    for (int64_t r0 = lo; r0 < hi; r0 += 64) {
+        const int64_t r = r0 + lane;
+        int kind = 0, qpos = 0, indel = 0, bq = 0;
+        bool tail = false, ev = false;
+        int64_t s0 = 0;
+        if (r < hi) {
+            const int64_t co = A.cigar_off[r];
+            s0 = A.seq_off[r];
+            const int lq = (int)(A.seq_off[r + 1] - s0);
+            kind = lfq_plp_locate_indel(A.cigar + co, (int)(A.cigar_off[r + 1] - co), A.pos[r], p, lq, &qpos, &indel, &tail);
+            if (kind == 1 && qpos >= 0) {               /* (qpos < 0: a read without bases) */
+                bq = A.qual[s0 + qpos];
+            }
+            if (!SCATTER && klen > 0 && kind != 0 && indel == (kdel ? -klen : klen)) {
+                ev = true;
+                for (int j = 0; j < klen && ev; ++j) {
+                    uint8_t ch;
+                    if (kdel) {                         /* plp.c:1135-1138 */
+                        const int64_t g = p + 1 + j;
+                        ch = g < A.ref_len ? A.ref[g] : (uint8_t)'N';
+                        ch = (ch >= 'a' && ch <= 'z') ? (uint8_t)(ch - 32) : ch;
+                    } else {                            /* plp.c:1091-1094 */
+                        const int q = qpos + 1 + j;
+                        ch = (uint8_t)lfq_seq_letter(q < lq ? A.seq[s0 + q] : 4u);
+                    }
+                    ev = ch == A.key_chars[koff + j];
+                }
+            }
+        }
+        const bool kept = kind == 1 && qpos >= 0 && bq >= A.min_plp_bq;
+        const uint64_t mk = __ballot(kept);
+        if (!SCATTER) {
+            n_cov += (uint32_t)__popcll(__ballot(kind != 0));
+            n_tail += (uint32_t)__popcll(__ballot(kind == 1 && tail));
+            n_ev += (uint32_t)__popcll(__ballot(ev));
+        } else if (kept) {
+            const uint32_t rank = n_kept + (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));
+            if (rank < room) {
+                const uint64_t slot = base + rank;
+                const uint32_t code = A.seq[s0 + qpos];
+                A.t_nt[slot] = (uint8_t)((code > 4 ? 4u : code) | (A.reverse[r] ? 8u : 0u));
+                A.t_bq[slot] = (uint8_t)(bq > 93 ? 93 : bq);                                   /* plp.c:948-952 */
+                const uint32_t lb = A.baq ? A.baq[s0 + qpos] : 0u;
+                A.t_baq[slot] = A.baq ? (uint8_t)(lb >= 33 ? lb - 33 : 255) : (uint8_t)255;
+                A.t_mq[slot] = A.mapq[r];
+                if (A.t_sq) {
+                    A.t_sq[slot] = A.sq[r];
+                }
+            }
+        }
+        n_kept += (uint32_t)__popcll(mk);
+    }
+    if (!SCATTER && lane == 0) {
+        A.counts[i] = (int32_t)n_cov;
+        A.counts[A.n_sites + i] = (int32_t)n_kept;
+        A.counts[2 * A.n_sites + i] = (int32_t)n_tail;
+        A.counts[3 * A.n_sites + i] = (int32_t)n_ev;
+        A.win[2 * i] = lo;
+        A.win[2 * i + 1] = hi;
+    }
+}
+
+int lfq_launch_pileup_sites(const LfqSitesArgs &a, int scatter, void *stream)
+{
+    if (a.n_sites <= 0) {
+        return LFQ_OK;
+    }
+    const dim3 grid((unsigned)((a.n_sites + 3) / 4)), block(256);
+    if (scatter) {
+        hipLaunchKernelGGL(lfq_pileup_sites_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
+    } else {
+        hipLaunchKernelGGL(lfq_pileup_sites_kernel<false>, grid, block, 0, (hipStream_t)stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
+}
+
+
 /* ---- indel pseudo-columns on the device ----------------------------------------------------------------------
  * One wavefront per tested event: the column's reads without an event of that side (indel quality, MAPQ) followed
  * by the reads of all its events, the tested one's marked as the alt allele and carrying their alignment quality

@@ -1643,6 +1643,196 @@ int lfq_readset_pileup_snv(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, in
     return LFQ_OK;
 }
 
+/* ---- the pileup at a list of positions (`lofreq uniq` on a read set) ---------------------------------------------------
+ * Count pass -> the per-site counts come back once (16 bytes a site; the binomial test needs them on the host anyway) ->
+ * the column offsets, reference bases and the two count arrays of the tracks go down (21 bytes a site) -> scatter pass.  The
+ * buffers are the context's own pair for this call family. */
+int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos, int64_t n_sites, int min_plp_bq,
+                           const int64_t *key_off, const char *key_chars, const uint8_t *key_del, lfq_tracks *out,
+                           int32_t *cov_out, int32_t *nb_out, int32_t *tails_out, int32_t *ev_out)
+{
+    if (!c || !rs || rs->c != c || !out || n_sites < 0 || (n_sites > 0 && !site_pos)
+        || (rs->n > 0 && (!rs->seq || !rs->qual || !rs->mapq || !rs->reverse))) {
+        return LFQ_ERR_INVALID;
+    }
+    memset(out, 0, sizeof(*out));
+    memset(&c->sites_times, 0, sizeof(c->sites_times));
+    if (n_sites == 0) {
+        return LFQ_OK;
+    }
+    for (int64_t i = 0; i < n_sites; i++) {
+        if (site_pos[i] < 0 || site_pos[i] >= rs->ref_len) {
+            return LFQ_ERR_INVALID;
+        }
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    hipStream_t ps = c->stream;
+    LFQ_TRY(readset_upload_wait(rs, ps));
+    /* the window search needs position-sorted reads, and the reference's -d acts on the reads of each 1-bp query: a cap
+     * that drops a read of the region is not that rule */
+    const int32_t *pmax = rs->n > 0 ? readset_pmax(c, rs, ps) : nullptr;
+    if (rs->n > 0 && !pmax) {
+        return LFQ_ERR_INVALID;
+    }
+    LFQ_TRY(readset_keep(c, rs));
+    if (c->plp_max_depth != LFQ_NO_MAX_DEPTH && !rs->keep.empty()) {
+        return LFQ_ERR_INVALID;
+    }
+    c->sites_times.n_sites = n_sites;
+    for (int i = 0; i < 4; i++) {
+        if (!c->ev_sites_t[i]) {
+            LFQ_TRY_HIP(hipEventCreate(&c->ev_sites_t[i]));
+        }
+    }
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t n = n_sites, n_key = key_off ? key_off[n] - key_off[0] : 0;
+    /* what goes up in one copy: positions | key offsets | key sides | key letters; then the windows and the counts */
+    const int64_t o_pos = 0, o_koff = o_pos + al(n * 8), o_kdel = o_koff + al((n + 1) * 8), o_kch = o_kdel + al(n),
+                  o_win = o_kch + al(n_key + 1), o_cnt = o_win + al(n * 16), total = o_cnt + al(n * 16);
+    LFQ_TRY(lfq_order_after_batch(c, ps));                 /* the tracks of the previous call may still be a running batch's input */
+    LFQ_TRY(grow(&c->d_sites_in, &c->sites_in_bytes, total));
+    uint8_t *d = c->d_sites_in;
+    LfqPin<uint8_t> up(c, (size_t)o_win);
+    LFQ_PIN_OK(up);
+    memcpy(up.data() + o_pos, site_pos, (size_t)n * 8);
+    if (key_off) {
+        int64_t *ko = (int64_t *)(up.data() + o_koff);
+        for (int64_t i = 0; i <= n; i++) {
+            ko[i] = key_off[i] - key_off[0];
+        }
+        memcpy(up.data() + o_kdel, key_del, (size_t)n);
+        if (n_key > 0) {
+            memcpy(up.data() + o_kch, key_chars + key_off[0], (size_t)n_key);
+        }
+    }
+    LFQ_TRY_HIP(hipMemcpyAsync(d, up.data(), (size_t)o_win, hipMemcpyHostToDevice, ps));
+    LfqSitesArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_reads = rs->n;
+    A.pos = (const int32_t *)rs->d_pos;
+    A.pmax_end = pmax;
+    A.cigar_off = (const int64_t *)rs->d_coff;
+    A.seq_off = (const int64_t *)rs->d_soff;
+    A.cigar = (const uint32_t *)rs->d_cig;
+    A.seq = rs->d_seq;
+    A.qual = rs->d_qual;
+    A.baq = rs->has_lb ? rs->d_lb : nullptr;
+    A.mapq = rs->d_mapq;
+    A.reverse = rs->d_rev;
+    A.sq = rs->has_sqb ? rs->d_sqb : nullptr;
+    A.ref = rs->d_ref;
+    A.ref_len = rs->ref_len;
+    A.n_sites = n;
+    A.site_pos = (const int64_t *)(d + o_pos);
+    A.min_plp_bq = min_plp_bq;
+    if (key_off) {
+        A.key_off = (const int64_t *)(d + o_koff);
+        A.key_del = d + o_kdel;
+        A.key_chars = d + o_kch;
+    }
+    A.counts = (int32_t *)(d + o_cnt);
+    A.win = (int64_t *)(d + o_win);
+    LfqPin<int32_t> h_cnt(c, (size_t)n * 4);
+    LFQ_PIN_OK(h_cnt);
+    LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[0], ps));
+    LFQ_TRY(lfq_launch_pileup_sites(A, 0, ps));
+    LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[1], ps));
+    c->sites_times.n_launches = 1;
+    LFQ_TRY_HIP(hipMemcpyAsync(h_cnt.data(), A.counts, (size_t)n * 16, hipMemcpyDeviceToHost, ps));
+    LFQ_TRY_HIP(hipStreamSynchronize(ps));
+    const int32_t *h_cov = h_cnt.data(), *h_nb = h_cov + n, *h_tails = h_nb + n, *h_ev = h_tails + n;
+    /* the header of the tracks, assembled here and sent down in one copy: offsets | reference bases | coverage_plp | num_bases */
+    const int64_t t_off = 0, t_ref = t_off + al((n + 1) * 8), t_cov = t_ref + al(n + 16), t_nb = t_cov + al(n * 4 + 16),
+                  t_nt = t_nb + al(n * 4 + 16);
+    LfqPin<uint8_t> hdr(c, (size_t)t_nt);
+    LFQ_PIN_OK(hdr);
+    memset(hdr.data(), 0, (size_t)t_nt);
+    uint64_t *h_off = (uint64_t *)(hdr.data() + t_off);
+    int64_t n_obs = 0, max_obs = 0;
+    for (int64_t i = 0; i < n; i++) {
+        h_off[i] = (uint64_t)n_obs;
+        n_obs += h_nb[i];
+        max_obs = std::max<int64_t>(max_obs, h_nb[i]);
+        uint8_t rb = rs->ref ? (uint8_t)rs->ref[site_pos[i]] : (uint8_t)'N';     /* plp.c:818-823, as the region pileup */
+        if (!(rb == 'A' || rb == 'C' || rb == 'T' || rb == 'G' || rb == 'N')) {
+            rb = 'N';
+        }
+        hdr[(size_t)(t_ref + i)] = rb;
+    }
+    h_off[n] = (uint64_t)n_obs;
+    memcpy(hdr.data() + t_cov, h_cov, (size_t)n * 4);
+    memcpy(hdr.data() + t_nb, h_nb, (size_t)n * 4);
+    const int64_t trk = al(n_obs + 32);
+    const int64_t t_bq = t_nt + trk, t_baq = t_bq + trk, t_mq = t_baq + trk, t_sq = t_mq + trk,
+                  t_total = t_sq + (rs->has_sqb ? trk : 0);
+    LFQ_TRY(grow(&c->d_sites_out, &c->sites_out_bytes, t_total));
+    uint8_t *t = c->d_sites_out;
+    LFQ_TRY_HIP(hipMemcpyAsync(t, hdr.data(), (size_t)t_nt, hipMemcpyHostToDevice, ps));
+    for (int64_t o = t_nt; o < t_total; o += trk) {
+        LFQ_TRY_HIP(hipMemsetAsync(t + o + n_obs, 0, (size_t)(trk - n_obs), ps));        /* the 16-byte tails are read */
+    }
+    if (n_obs > 0) {
+        A.col_off = (const uint64_t *)(t + t_off);
+        A.t_nt = t + t_nt;
+        A.t_bq = t + t_bq;
+        A.t_baq = t + t_baq;
+        A.t_mq = t + t_mq;
+        A.t_sq = rs->has_sqb ? t + t_sq : nullptr;
+        LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[2], ps));
+        LFQ_TRY(lfq_launch_pileup_sites(A, 1, ps));
+        LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[3], ps));
+        c->sites_times.n_launches = 2;
+    }
+    c->sites_times.n_obs = n_obs;
+    LFQ_TRY_HIP(hipStreamSynchronize(ps));                 /* (the header's staging block goes back to the pool on return) */
+    for (int64_t i = 0; i < n; i++) {
+        if (cov_out) cov_out[i] = h_cov[i];
+        if (nb_out) nb_out[i] = h_nb[i];
+        if (tails_out) tails_out[i] = h_tails[i];
+        if (ev_out) ev_out[i] = h_ev[i];
+    }
+    out->nt = t + t_nt;
+    out->bq = t + t_bq;
+    out->baq = t + t_baq;
+    out->mq = t + t_mq;
+    out->sq = rs->has_sqb ? t + t_sq : nullptr;
+    out->col_off = (const uint64_t *)(t + t_off);
+    out->ref_base = t + t_ref;
+    out->coverage_plp = (const int32_t *)(t + t_cov);
+    out->num_bases = (const int32_t *)(t + t_nb);
+    out->ncols = n;
+    out->max_col_obs = max_obs;
+    out->flags = 0;
+    return LFQ_OK;
+}
+
+int lfq_readset_pileup_sites(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos, int64_t n_sites, int min_plp_bq,
+                             lfq_tracks *out, int32_t *coverage_plp_out, int32_t *num_tails_out)
+{
+    return lfq_readset_sites_impl(c, rs, site_pos, n_sites, min_plp_bq, nullptr, nullptr, nullptr, out, coverage_plp_out,
+                                  nullptr, num_tails_out, nullptr);
+}
+
+int lfq_last_sites_times(lfq_ctx *c, lfq_sites_times *t)
+{
+    if (!c || !t) {
+        return LFQ_ERR_INVALID;
+    }
+    *t = c->sites_times;
+    if (t->n_launches > 0) {
+        LFQ_TRY_HIP(hipSetDevice(c->device));
+        LFQ_TRY_HIP(hipEventSynchronize(c->ev_sites_t[t->n_launches > 1 ? 3 : 1]));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c->ev_sites_t[0], c->ev_sites_t[1]) == hipSuccess) {
+            t->count_ms = ms;
+        }
+        if (t->n_launches > 1 && hipEventElapsedTime(&ms, c->ev_sites_t[2], c->ev_sites_t[3]) == hipSuccess) {
+            t->scatter_ms = ms;
+        }
+    }
+    return LFQ_OK;
+}
+
 /* compile_plp_col's indel fields for the reads of a region (plp.c:1019-1192): the sparse part (which read carries
  * which insertion / deletion where: straight from the CIGARs) is assembled here, the dense part (counts over all
  * pileup entries and the quality arrays of the reads WITHOUT an event at the event columns) by lfq_plp_indel_kernel */

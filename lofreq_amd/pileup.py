@@ -366,3 +366,57 @@ class ReadSet:
             _lib.check(self.L.lfq_readset_pileup_indels(self.caller.h, self.h, int(begin), int(end), int(min_plp_idq),
                                                         C.byref(out), col_pos.ctypes.data), "lfq_readset_pileup_indels")
         return _indel_columns_from_c(out, col_pos, self.caller)
+
+    def pileup_sites(self, pos, min_plp_bq=3):
+        """lfq_readset_pileup_sites: the pileup at a LIST of positions, column i = pos[i] (any order, duplicates allowed; a
+        position no read covers is an empty column).  -> (DeviceTracks with unpacked nt, valid until the context's next
+        pileup_sites / uniq call; coverage_plp; num_tails)"""
+        pos = np.ascontiguousarray(pos, np.int64)
+        n = len(pos)
+        cov = np.zeros(max(n, 1), np.int32)
+        tails = np.zeros(max(n, 1), np.int32)
+        t = _lib.Tracks()
+        _lib.check(self.L.lfq_readset_pileup_sites(self.caller.h, self.h, pos.ctypes.data, n, int(min_plp_bq), C.byref(t),
+                                                   cov.ctypes.data, tails.ctypes.data), "lfq_readset_pileup_sites")
+        return DeviceTracks(t, pos.copy()), cov[:n], tails[:n]
+
+    def uniq(self, pos, ref, alt, af, indel_key=None, use_det_lim=False, min_plp_bq=3):
+        """lfq_readset_uniq (`lofreq uniq` for a list of variants on this read set, the OTHER sample's reads filtered as
+        uniq's mpileup filters them).  pos: 0-based positions; ref / alt: the REF / ALT strings; af: the AF values (or
+        --uni-freq); indel_key: which variants carry the INDEL key.  -> dict of arrays: coverage, alt_count, uq (-1 = no
+        UQ tag), pvalue (-1.0 = none) and detectable (the UNIQ flag of --use-det-lim)"""
+        n = len(pos)
+        pos = np.ascontiguousarray(pos, np.int64)
+        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+        refs, alts = [enc(x) for x in ref], [enc(x) for x in alt]
+        assert len(refs) == n and len(alts) == n and len(af) == n
+        ref_off = np.zeros(n + 1, np.int64)
+        alt_off = np.zeros(n + 1, np.int64)
+        ref_off[1:] = np.cumsum([len(x) for x in refs])
+        alt_off[1:] = np.cumsum([len(x) for x in alts])
+        ref_b, alt_b = b"".join(refs) + b"\0", b"".join(alts) + b"\0"
+        af = np.ascontiguousarray(af, np.float32)
+        v = _lib.UniqVariants()
+        v.n = n
+        v.pos, v.ref_off, v.alt_off = pos.ctypes.data, ref_off.ctypes.data, alt_off.ctypes.data
+        v.ref, v.alt = C.cast(C.c_char_p(ref_b), C.c_void_p), C.cast(C.c_char_p(alt_b), C.c_void_p)
+        v.af = af.ctypes.data
+        if indel_key is not None:
+            indel_key = np.ascontiguousarray(np.asarray(indel_key, bool), np.uint8)
+            assert len(indel_key) == n
+            v.indel_key_or_null = indel_key.ctypes.data
+        res = {"coverage": np.zeros(max(n, 1), np.int32), "alt_count": np.zeros(max(n, 1), np.int32),
+               "uq": np.zeros(max(n, 1), np.int32), "pvalue": np.zeros(max(n, 1), np.float64),
+               "detectable": np.zeros(max(n, 1), np.uint8)}
+        o = _lib.UniqResult()
+        for k, a in res.items():
+            setattr(o, k, a.ctypes.data)
+        _lib.check(self.L.lfq_readset_uniq(self.caller.h, self.h, C.byref(v), 1 if use_det_lim else 0, int(min_plp_bq),
+                                           C.byref(o)), "lfq_readset_uniq")
+        return {k: a[:n] for k, a in res.items()}
+
+    def last_sites_times(self):
+        """lfq_last_sites_times of the caller's context -> _lib.SitesTimes"""
+        t = _lib.SitesTimes()
+        _lib.check(self.L.lfq_last_sites_times(self.caller.h, C.byref(t)), "lfq_last_sites_times")
+        return t

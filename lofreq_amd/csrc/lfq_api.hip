@@ -5,6 +5,7 @@
  * There is deliberately no CPU fallback in this file: every compute entry point needs a HIP
  * device and fails with LFQ_ERR_NO_DEVICE / LFQ_ERR_HIP otherwise.
  */
+#include "lfq_bound.h"
 #include "lfq_ctx.h"
 
 namespace {
@@ -666,6 +667,19 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         LFQ_TRY_HIP(hipStreamSynchronize(st));
         max_depth = c->h_counters[LFQ_GC_MAXDEPTH];
     }
+    /* the screen kernel's bound gate (lfq_bound.h), where the lean count kernel supplies its statistic and under the conditions
+     * of the screen's LB form (lfq_launch_dp_quad): a counted row has bq in [max(min_bq, min_alt_bq), LFQ_BOUND_QLO] and keeps
+     * that quality, so its error probability is at least the smallest table entry over that range */
+    {
+        static const LfqLuts h_luts = [] {
+            LfqLuts h;
+            fill_luts(&h);
+            return h;
+        }();
+        const bool lb = !P.general && P.def_alt_bq == 0 && P.def_alt_jp < 0.0;
+        P.bound_p_lo = (lb && !indel_mode && kn.bound_gate && lfq_count_is_lean(T, P, max_depth))
+                           ? lfq_bound_p_lo(h_luts.bq, P.min_alt_bq4, LFQ_BOUND_QLO) : 0.0;
+    }
     const int64_t per_block = 3 * max_depth + 72;
     int n_big_blocks = c->n_cu;                         /* 8-wave workgroups: one per CU beside the light kernel */
     const int64_t budget = (int64_t)1 << 29;            /* 4 GiB of doubles */
@@ -755,7 +769,9 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
          * chain short (0.69 ms at C3); a context that queues its batches without a gate runs the chain beside the next batch's
          * count kernel, where its length is hidden (1.7 ms with one wavefront per CU against a period of 2.8) and every resident
          * screen wavefront costs the count kernel a slot -- C3 2.82-2.84 -> 2.77-2.79 ms per step with one, C2 0.523-0.528 ->
-         * 0.505-0.512 with one or two; shallow batches keep two (their chain is the longer part of a shorter period). */
+         * 0.505-0.512 with one or two; shallow batches keep two (their chain is the longer part of a shorter period).  With the
+         * bound gate (lfq_bound.h) dropping ~99 % of C3's light columns at claim time, one against four was measured again: four
+         * shorten the light chain 1.03 -> 0.56 ms and the step is 2.71 ms against 2.65 with one (profiles/NOTES.md). */
         const int screen_auto = (c->batch_gate == LFQ_GATE_NONE && !indel_mode) ? (tr->max_col_obs >= 4096 ? 1 : 2) : 4;
         const int light_waves_per_cu = kn.light_kernel == 0 ? screen_auto : 10;
         const int n_light_waves = (int)std::min<int64_t>((int64_t)c->n_cu * light_waves_per_cu, std::max<int64_t>(seg_cols / 8, 4));

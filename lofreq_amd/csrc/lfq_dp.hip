@@ -28,6 +28,7 @@
  */
 #include <atomic>
 
+#include "lfq_bound.h"
 #include "lfq_device.h"
 
 #define LFQ_LN2_HI 6.93147180369123816490e-01
@@ -1139,15 +1140,27 @@ __device__ __forceinline__ void lfq_screen_row(double (&v)[KREG], double p, doub
  * (snpcaller.c:334) only ever add -- read from two of the five tracks and evaluated with one FMA.  P(X >= K) is
  * monotone in every p, so a tail computed from lower bounds that exceeds the pruning threshold proves that the exact
  * one does: the column is pruned a row or two later than it could be (the dropped terms are ~1 % of the error mass of
- * a typical column), never wrongly.  Everything the screen does not prune is redone exactly by the retry kernel. */
-template <int KREG, bool LB>
+ * a typical column), never wrongly.  Everything the screen does not prune is redone exactly by the retry kernel.
+ * GATE: the instantiation for batches whose count kernel left the bound gate's statistic in the entries (P.bound_p_lo > 0);
+ * the other one is the kernel without a trace of it. */
+template <int KREG, bool LB, bool GATE>
 __global__ __launch_bounds__(256) void lfq_dp_screen_kernel(LfqTracksDev T, LfqParams P,
                                                             const LfqLuts *__restrict__ g_luts, LfqWork W,
                                                             uint8_t *__restrict__ retry, int max_rounds)
 {
     constexpr int MAXK = KREG - 1;
+    static_assert(MAXK <= LFQ_BOUND_MAXK, "the bound gate's table");
+    static_assert(LB || !GATE, "the bound needs the LB conditions");
     __shared__ LfqLuts s_luts;
+    __shared__ LfqBoundTab s_bound;                 /* (GATE only: an unused LDS variable is not allocated) */
     lfq_luts_to_lds(&s_luts, g_luts);
+    if constexpr (GATE) {                           /* the gate's two small tables, an entry per thread */
+        if (threadIdx.x < LFQ_BOUND_CODES) {
+            s_bound.qm[threadIdx.x] = lfq_bound_qm(P.bound_p_lo, threadIdx.x);
+        } else if (threadIdx.x >= 64 && threadIdx.x < 64 + LFQ_BOUND_NRK) {
+            s_bound.rk[threadIdx.x - 64] = lfq_bound_rk(P.bound_p_lo, (int)threadIdx.x - 64);
+        }
+    }
     __syncthreads();
     const int lane = lfq_lane();
     const int n_work = W.counters[LFQ_CNT_LIGHT];
@@ -1205,15 +1218,21 @@ __global__ __launch_bounds__(256) void lfq_dp_screen_kernel(LfqTracksDev T, LfqP
                     retry[idx] = 1;                 /* needs more cells than this variant keeps in registers */
                     n_retry++;
                 } else {
-                    active = true;
-                    off0 = ((uint64_t)a.y << 32) | a.x;
-                    n_obs = (int)a.z;
                     int64_t bonf = P.bonf_base;
                     if (P.bonf_dynamic) {           /* lfq_col_setup */
                         bonf = ((P.bonf_reset_first && P.bonf_base == 1) ? 0 : P.bonf_base)
                                + (int64_t)P.bonf_step * (int)b.x;
                     }
                     bonf_d = (double)bonf;
+                    /* the bound gate: the column's n_lo kept rows of probability >= p_lo alone put its tail above the pruning
+                     * threshold, so the reference prunes it and nothing comes of it -- dropped before a byte of it is read
+                     * (neither rows nor cells to account for, no retry): the lane stays free and claims again */
+                    active = true;
+                    if constexpr (GATE) {
+                        active = !(b.w != 0u && lfq_bound_tail(&s_bound, b.w & (LFQ_BOUND_CODES - 1u), K) * bonf_d > sig_s);
+                    }
+                    off0 = ((uint64_t)a.y << 32) | a.x;
+                    n_obs = (int)a.z;
                     med = (int)(int16_t)(b.z & 0xffffu);
                     ref_code = (int)((b.z >> 16) & 0xffu);
                     rel = -(int)(off0 & 15u);       /* window start relative to the column start */
@@ -2976,11 +2995,14 @@ int lfq_launch_dp_quad(const LfqTracksDev &t, const LfqParams &p, const LfqLuts 
         const bool lb = !p.general && p.def_alt_bq == 0 && p.def_alt_jp < 0.0;
 #define LFQ_LAUNCH_SCREEN(KR)                                                                                        \
     do {                                                                                                             \
-        if (lb) {                                                                                                    \
-            hipLaunchKernelGGL((lfq_dp_screen_kernel<KR, true>), grid, block, 0, st, t, p, d_luts, w, d_retry,       \
+        if (lb && p.bound_p_lo > 0.0) {                                                                              \
+            hipLaunchKernelGGL((lfq_dp_screen_kernel<KR, true, true>), grid, block, 0, st, t, p, d_luts, w, d_retry, \
+                               kn.screen_rounds);                                                                    \
+        } else if (lb) {                                                                                             \
+            hipLaunchKernelGGL((lfq_dp_screen_kernel<KR, true, false>), grid, block, 0, st, t, p, d_luts, w, d_retry, \
                                kn.screen_rounds);                                                                    \
         } else {                                                                                                     \
-            hipLaunchKernelGGL((lfq_dp_screen_kernel<KR, false>), grid, block, 0, st, t, p, d_luts, w, d_retry,      \
+            hipLaunchKernelGGL((lfq_dp_screen_kernel<KR, false, false>), grid, block, 0, st, t, p, d_luts, w, d_retry, \
                                kn.screen_rounds);                                                                    \
         }                                                                                                            \
     } while (0)

@@ -105,6 +105,7 @@ const LfqKnobs &lfq_knobs(void)
         x.indel_host_pack = LFQ_TUNE_HAS("LFQ_INDEL_HOST_PACK");
         x.pileup_atomic = LFQ_TUNE_HAS("LFQ_PILEUP_ATOMIC");
         x.baq_lds = LFQ_TUNE_I("LFQ_BAQ_LDS", 1) != 0;
+        x.bound_gate = LFQ_TUNE_I("LFQ_BOUND_GATE", 1) != 0;
         (void)geti;
         (void)has;
         return x;

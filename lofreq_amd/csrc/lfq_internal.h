@@ -50,6 +50,7 @@ struct LfqParams {
     int32_t sparse_counts;    /* 1: the shared-wavefront count kernel writes the dense entry of a column only if it is tested (nothing
                                * on the device reads the others: lfq_set_dense_counts) */
     int32_t pad_;
+    double bound_p_lo;        /* the screen kernel's bound gate (lfq_bound.h): smallest bq-table entry a counted row can have; 0 = gate off */
 };
 
 struct LfqTracksDev {
@@ -73,8 +74,12 @@ struct LfqEntry {
     int16_t median_ref_bq;
     uint8_t ref_code;         /* 0..3 */
     uint8_t pad_;
-    int32_t pad2_;
+    int32_t pad2_;            /* light class: lfq_bound_code(n_lo) of the column (lfq_bound.h), 0 = no statistic */
 };
+
+/* the class byte the count kernels write per column: bit 0 tested, bit 1 mid, bit 2 big; bits 3..7 the bound gate's
+ * statistic (lfq_count_column_lean only) */
+#define LFQ_FLAG_NLO_SHIFT 3
 
 /* ---- row-split ("long") columns ------------------------------------------------------------------
  * The rows of a column are independent Bernoulli trials, so the count distribution of the whole column is
@@ -231,6 +236,7 @@ struct LfqKnobs {
     int baq_lds;               /* LFQ_BAQ_LDS (1) */
     long baq_scratch_mb;       /* LFQ_BAQ_SCRATCH_MB: -1 = from free HBM */
     int private_stream;        /* LFQ_PRIVATE_STREAM (0): lfq_create gives every context a launch stream of its own (lfq_set_private_stream) */
+    int bound_gate;            /* LFQ_BOUND_GATE (1): 0 = every light column runs the screen's DP (A/B of the bound gate, lfq_bound.h) */
 };
 const LfqKnobs &lfq_knobs(void);
 /* CPUs this process may actually use: the affinity mask and the cgroup's cpu.max quota, not the machine's core count
@@ -466,6 +472,7 @@ bool lfq_count_is_shallow(const LfqTracksDev &t, const LfqParams &p, int64_t max
 int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqParams &p, const LfqLuts *d_luts,
                      lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, bool shallow_half_cu = false);
 /* (shallow_half_cu: the shared-wavefront count kernel keeps two workgroups per CU resident instead of as many as fit) */
+bool lfq_count_is_lean(const LfqTracksDev &t, const LfqParams &p, int64_t max_col_obs);
 int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const uint8_t *d_flags,
                     const lfq_col_counts *d_counts, const LfqWork &w, void *stream, bool relist = false);
 /* -t / --approx-threshold (snpcaller.c:1128-1142): clears the flag byte of the listed columns the Poisson gate gives up;

@@ -30,6 +30,7 @@
 
 #include <algorithm>
 
+#include "lfq_bound.h"
 #include "lfq_device.h"
 #include "lofreq_synth.h"
 
@@ -175,6 +176,43 @@ __device__ __forceinline__ void lfq_count_nib8_lean(uint32_t (&ge)[4], uint32_t 
         lfq_bcnt_acc(ga[2], p2 & g2);
         lfq_bcnt_acc(ga[3], p3 & g2);
     }
+}
+
+/* lfq_count_nib8_lean for the chunks the bound gate's statistic is taken from (lfq_bound.h): besides the planes it counts the
+ * observations that are kept rows whatever their allele (p0, under the larger threshold with two) and have
+ * bq <= LFQ_BOUND_QLO = 31 -- byte + 96 has bit 7 set exactly when byte >= 32, brought to the nibble domain like the gate.
+ * The count rides in bits 26.. of ge[3] (LFQ_NLO_PACK) -- at most 32 per lane, this runs on the first trip of a lane's loop
+ * only -- until the column's sums are taken: a vector register of its own would be the kernel's 33rd.  Seven instructions
+ * more per 8 observations. */
+#define LFQ_NLO_PACK 26
+template <bool SAME_THR>
+__device__ __forceinline__ void lfq_count_nib8_lean_lo(uint32_t (&ge)[4], uint32_t (&ga)[4], uint32_t ntw, uint32_t bqa,
+                                                       uint32_t bqb, uint32_t vm, uint32_t kge, uint32_t kga)
+{
+    static_assert(LFQ_BOUND_QLO == 31, "the bit test below");
+    const uint32_t hi = __builtin_amdgcn_bitop3_b32(0x80808080u, bqb + 0x60606060u, (bqa + 0x60606060u) >> 4, 0xCA);    /* bit 3 of a nibble: bq >= 32 */
+    const uint32_t s0 = ntw << 3, s1 = ntw << 2, s2 = ntw << 1;
+    const uint32_t a = bqa + kge, b = bqb + kge;
+    const uint32_t g = __builtin_amdgcn_bitop3_b32(0x80808080u, b, a >> 4, 0xCA);
+    const uint32_t p0 = __builtin_amdgcn_bitop3_b32(g, s2, vm, 0x20);
+    uint32_t lo = p0 & ~hi;
+    if (!SAME_THR) {
+        const uint32_t a2 = bqa + kga, b2 = bqb + kga;
+        const uint32_t g2 = __builtin_amdgcn_bitop3_b32(0x80808080u, b2, a2 >> 4, 0xCA);
+        lo &= g2;
+        lfq_bcnt_acc(ga[0], p0 & g2);
+        lfq_bcnt_acc(ga[1], p0 & s0 & g2);
+        lfq_bcnt_acc(ga[2], p0 & s1 & g2);
+        lfq_bcnt_acc(ga[3], p0 & s0 & s1 & g2);
+    }
+    ge[3] += (uint32_t)__builtin_popcount(lo) << LFQ_NLO_PACK;
+    const uint32_t p1 = p0 & s0;
+    const uint32_t p2 = p0 & s1;
+    const uint32_t p3 = __builtin_amdgcn_bitop3_b32(p0, s0, s1, 0x80);
+    lfq_bcnt_acc(ge[0], p0);
+    lfq_bcnt_acc(ge[1], p1);
+    lfq_bcnt_acc(ge[2], p2);
+    lfq_bcnt_acc(ge[3], p3);
 }
 
 template <bool SAME_THR, bool PACKED, bool STRAND = true>
@@ -1106,6 +1144,8 @@ __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq
     const bool gated = (ref_code < 0) || ((int64_t)nb * 2 < (int64_t)cov) || (nb < T.min_cov);
 
     uint32_t ge[4] = {0u, 0u, 0u, 0u}, ga[4] = {0u, 0u, 0u, 0u};
+    /* (the bound gate's statistic, lfq_bound.h -- kept rows of bq <= 31 among the interior chunks of the loop's first trip:
+     * whole chunks, up to LFQ_BOUND_SUBSET observations, none for a column whose loop does not run -- rides in ge[3]) */
 #ifdef LFQ_COUNT_STAMP
     uint64_t st1 = st0, st2 = st0;
 #endif
@@ -1122,6 +1162,21 @@ __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq
         st1 = wall_clock64() + (uint64_t)(n_ch & 0);
 #endif
         int i = 1 + lane;
+        if (i + (UNROLL - 1) * LFQ_WAVE < n_in) {                             /* the first trip, peeled: it also counts n_lo */
+            uint2 nv[UNROLL];
+            uint4 bv[UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                nv[u] = nt8[i + u * LFQ_WAVE];
+                bv[u] = bq16[i + u * LFQ_WAVE];
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                lfq_count_nib8_lean_lo<SAME_THR>(ge, ga, nv[u].x, bv[u].x, bv[u].y, 0x88888888u, kge, kga);
+                lfq_count_nib8_lean_lo<SAME_THR>(ge, ga, nv[u].y, bv[u].z, bv[u].w, 0x88888888u, kge, kga);
+            }
+            i += UNROLL * LFQ_WAVE;
+        }
         for (; i + (UNROLL - 1) * LFQ_WAVE < n_in; i += UNROLL * LFQ_WAVE) {  /* UNROLL chunks' loads in flight per lane */
             uint2 nv[UNROLL];
             uint4 bv[UNROLL];
@@ -1171,6 +1226,10 @@ __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq
 #ifdef LFQ_COUNT_STAMP
     st2 = wall_clock64() + (uint64_t)((ge[0] + ge[1] + ge[2] + ge[3]) & 0u);
 #endif
+    /* n_lo leaves ge[3] (a lane that did not take the first trip has 0 there; the plane below it stays under 2^LFQ_NLO_PACK:
+     * a lane sees at most n_obs / 64 + 32 < 2^26 observations of a column of less than 2^31) */
+    const uint32_t n_lo = lfq_wave_sum_lane63_u32(ge[3] >> LFQ_NLO_PACK);
+    ge[3] &= (1u << LFQ_NLO_PACK) - 1u;
     /* the column's sums end up in lane 63, which writes the record */
     uint32_t n_ge[4], n_ga[4];
 #pragma unroll
@@ -1217,6 +1276,9 @@ __device__ __forceinline__ void lfq_count_column_lean(const LfqCountArgs &T, lfq
             const int suspicious = max(12, r.n_err_probs / 512 + 8);
             flag = (uint8_t)((r.tested ? 1 : 0)
                              | ((kmax >= LFQ_BIG_K) ? 4 : (kmax >= LFQ_MID_K || kmax >= suspicious) ? 2 : 0));
+            /* n_lo, rounded down, in the five bits above the class (the scan hands it to the screen kernel; the other count
+             * kernels leave them 0, which switches the gate off for their columns) */
+            flag |= (uint8_t)(r.tested ? lfq_bound_code(n_lo) << LFQ_FLAG_NLO_SHIFT : 0u);
         }
 #ifdef LFQ_COUNT_STAMP
         {
@@ -1531,7 +1593,7 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_apply_kernel(LfqTra
             e.median_ref_bq = (int16_t)cn->median_ref_bq;
             e.ref_code = (uint8_t)((rb == 'A') ? 0 : (rb == 'C') ? 1 : (rb == 'G') ? 2 : 3);
             e.pad_ = 0;
-            e.pad2_ = 0;
+            e.pad2_ = (f[i] & 6u) ? 0 : (int32_t)(f[i] >> LFQ_FLAG_NLO_SHIFT);     /* light: the bound gate's n_lo code */
             W.entries[pos] = e;
         }
         if (!RELIST) {
@@ -1668,6 +1730,13 @@ bool lfq_count_is_shallow(const LfqTracksDev &t, const LfqParams &p, int64_t max
     return !p.general && !p.detlim_af && max_col_obs > 0 && max_col_obs < lfq_knobs().count_multi_below && t.nt_packed;
 }
 
+/* ... lfq_count_lean_kernel (the only one that counts the bound gate's statistic, lfq_bound.h) */
+bool lfq_count_is_lean(const LfqTracksDev &t, const LfqParams &p, int64_t max_col_obs)
+{
+    return !p.general && !p.detlim_af && !(max_col_obs > 0 && max_col_obs < lfq_knobs().count_multi_below) && t.nt_packed
+           && p.lazy_strand;
+}
+
 int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqParams &p, const LfqLuts *d_luts,
                      lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, bool shallow_half_cu)
 {
@@ -1742,7 +1811,7 @@ int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqPar
         const int variant = (t.nt_packed ? 4 : 0) | (strand ? 2 : 0) | (same_thr ? 1 : 0);
         const unsigned blocks = (unsigned)((c1 - c0 + LFQ_COUNT_WG_WAVES - 1) / LFQ_COUNT_WG_WAVES);
         const dim3 wg(64 * LFQ_COUNT_WG_WAVES);
-        if (t.nt_packed && !strand) {
+        if (lfq_count_is_lean(t, p, max_col_obs)) {
             /* lazy record counts on the packed layout: the decision counts only */
             if (same_thr) hipLaunchKernelGGL((lfq_count_lean_kernel<true>), dim3(blocks), wg, 0, (hipStream_t)stream, ca, d_counts, d_flags, c0, c1);
             else hipLaunchKernelGGL((lfq_count_lean_kernel<false>), dim3(blocks), wg, 0, (hipStream_t)stream, ca, d_counts, d_flags, c0, c1);

@@ -43,6 +43,7 @@ extern "C" {
 /* 8: lfq_viterbi_batch, lfq_last_viterbi_times. */
 /* 9: lfq_indelqual_batch, lfq_readset_indelqual, lfq_readset_fetch_indelquals, lfq_last_indelqual_times. */
 /* (10 still: lfq_readset_pileup_sites, lfq_readset_uniq, lfq_last_sites_times are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_readset_plp_summary, lfq_format_plp_summary, lfq_last_summary_times are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -861,6 +862,59 @@ typedef struct lfq_sites_times {
     int n_launches;
 } lfq_sites_times;
 int lfq_last_sites_times(lfq_ctx *ctx, lfq_sites_times *t);
+
+/* --- `lofreq plpsummary` / --plp-summary-only: the header line of plp_summary on a read set (lofreq_call.c:438-459) ---------
+ * lfq_readset_plp_summary: for every covered position of [region_begin, region_end), in order and numbered as the columns of
+ * lfq_readset_pileup_snv / lfq_readset_pileup_indels, what plp_summary prints in its first line:
+ *   fw / rv      fw_counts / rv_counts in A, C, G, T, N order: the entries that are not deleted / skipped and have
+ *                bq >= min_plp_bq, by seq_nt16_int code (every code above 4 is N) and strand (plp.c:929-941, 1007-1011);
+ *   num_heads / num_tails   entries at the first / last aligned position of their read that are not deleted / skipped, BEFORE
+ *                the min_plp_bq filter (plp.c:912-920); num_tails equals lfq_indel_columns.num_tails;
+ *   the consensus (plp.c:1231-1268): cons_kind 0 = a base, cons_nt = bam_nt4_rev_table[argmax_d(base_counts)] with
+ *                base_counts[nt4] += 1.0 - pow(10, -bq / 10.0), bq capped at 93 (:949-953), an increment of 0.0 replaced by
+ *                DBL_MIN (:1003-1005), summed in pileup order, the first maximum winning (utils.c:87-98: N never wins a tie, a
+ *                column without a kept base gets 'A'); cons_kind 1 / 2 = an insertion / deletion: per side the FIRST event in table
+ *                order whose cons_quals (the sum of its reads' indel qualities) is strictly greatest, if that sum is strictly
+ *                greater than the side's non-event quality sum; an insertion before a deletion.  Its key is
+ *                cons_key_chars[cons_key_off[col] .. cons_key_off[col + 1]) (empty for kind 0; cons_nt is filled in either way).
+ *                cons_kind != 0 exactly where lfq_indel_columns.cons_indel is set;
+ *   num_ins / num_dels / hrun / coverage_plp / ref_base   those of lfq_readset_pileup_indels for the same region and
+ *                min_plp_idq, which this call RUNS: afterwards the context's current lfq_indel_columns are this region's, exactly
+ *                as after lfq_readset_pileup_indels (an IndelColumns obtained earlier is superseded).
+ * One kernel, one wavefront per column; a double sum depends on the order of its terms, so a column whose two largest sums are
+ * closer than the rounding of two summation orders can explain is summed again in pileup order, add by add (lfq_summary_times.
+ * n_ordered counts them).  A -d cap (lfq_set_max_depth) removes reads as in the other pileups.  The arrays are host memory owned
+ * by the context, grow only, valid until the next lfq_readset_plp_summary call on it; the SNV tracks of lfq_readset_pileup_snv
+ * and the buffers of lfq_readset_pileup_sites are untouched.
+ * LFQ_ERR_INVALID, before anything is launched: a NULL ctx, rs or out (before a device is touched); region_end < region_begin; a
+ * region outside [0, ref_len]; min_plp_bq < 0; reads that are not position-sorted (lfq_set_pileup_unsorted does not apply).  An
+ * empty region, an empty read set or a region no read covers: LFQ_OK, ncols = 0, no summary launch.
+ * The indented quality lines of plp_summary (lofreq_call.c:460-597) are not produced: the tracks and event tables carry them. */
+typedef struct lfq_plp_summary {
+    int64_t ncols;
+    const int64_t *col_pos;            /* [ncols] 0-based positions */
+    const uint8_t *ref_base;           /* [ncols] plp.c:818-823 */
+    const int32_t *fw, *rv;            /* [ncols][5] A, C, G, T, N */
+    const int32_t *num_heads, *num_tails, *num_ins, *num_dels, *hrun, *coverage_plp;   /* [ncols] */
+    const uint8_t *cons_kind;          /* [ncols] 0 base, 1 '+', 2 '-' */
+    const uint8_t *cons_nt;            /* [ncols] 'A' 'C' 'G' 'T' 'N' */
+    const int64_t *cons_key_off;       /* [ncols + 1] */
+    const char *cons_key_chars;
+} lfq_plp_summary;
+int lfq_readset_plp_summary(lfq_ctx *ctx, lfq_readset *rs, int64_t region_begin, int64_t region_end, int min_plp_bq,
+                            int min_plp_idq, const lfq_plp_summary **out);
+/* "chrom\tpos\tref\tcons\tA:fw/rv\tC:..\tG:..\tT:..\tN:..\theads:%d\ttails:%d\tins:%d\tdels:%d\thrun:%d\n" of column col
+ * (lofreq_call.c:445-459).  Returns the length of the line (without the NUL) when buflen holds line and NUL, else
+ * LFQ_ERR_CAPACITY; LFQ_ERR_INVALID for a NULL argument or a column outside [0, ncols). */
+int lfq_format_plp_summary(char *buf, int buflen, const char *chrom, const lfq_plp_summary *summary, int64_t col);
+/* the kernel of the context's last lfq_readset_plp_summary call on the device's clock, its columns and how many of them took
+ * the ordered path; n_launches = 0 (and 0 ms) where nothing was launched */
+typedef struct lfq_summary_times {
+    double kernel_ms;
+    int64_t n_cols, n_ordered;
+    int n_launches;
+} lfq_summary_times;
+int lfq_last_summary_times(lfq_ctx *ctx, lfq_summary_times *t);
 
 /* --- synthetic workload (bench / tests): fills device tracks per include/lofreq_synth.h --- */
 int lfq_synth_fill_device(lfq_ctx *ctx, uint64_t seed, uint32_t depth, uint32_t plant_period,

@@ -73,6 +73,8 @@ struct lfq_region {
     int max_depth_set;              /* lfq_region_set_max_depth was called: close takes the cap off the context again */
     lfq_indelqual_conf idq;         /* lfq_region_set_indelqual; mode 0 = off (the default) */
     int vit_on, vit_def_qual;       /* lfq_region_set_viterbi; off by default */
+    lfq_region_emit_fn emit_summary; /* lfq_region_set_summary; NULL = off (the default) */
+    void *summary_user;
     /* outputs, grown on demand */
     int64_t *col_pos_i, pos_cap;
     lfq_snv_record *srec;
@@ -182,6 +184,16 @@ int lfq_region_set_viterbi(lfq_region *r, int on, int def_qual)
     }
     r->vit_on = on != 0;
     r->vit_def_qual = def_qual;
+    return LFQ_OK;
+}
+
+int lfq_region_set_summary(lfq_region *r, lfq_region_emit_fn emit_summary_line, void *user)
+{
+    if (!r || r->open || r->buf[0].started || r->buf[1].started) {
+        return LFQ_ERR_INVALID;
+    }
+    r->emit_summary = emit_summary_line;
+    r->summary_user = user;
     return LFQ_OK;
 }
 
@@ -411,6 +423,27 @@ static int region_finish(lfq_region *r, reg_buf *b)
         return LFQ_OK;
     }
     rc = grow_out(r, b->end - b->beg + 1);
+    if (rc == LFQ_OK && r->emit_summary) {
+        /* plp_summary's header lines, before the region's calls (the indel pileup below is then this region's second) */
+        const lfq_plp_summary *sm = NULL;
+        const int cap = (int)strlen(b->target) + 1536;      /* a consensus key is below MAX_INDELSIZE = 256 (utils.h:38) */
+        char *big = (char *)malloc((size_t)cap);
+        int64_t c;
+        if (!big) {
+            rc = LFQ_ERR_NOMEM;
+        } else {
+            rc = lfq_readset_plp_summary(r->ctx, b->rs, b->beg, b->end, r->o.min_plp_bq, r->o.min_plp_idq, &sm);
+        }
+        for (c = 0; rc == LFQ_OK && c < sm->ncols; c++) {
+            const int len = lfq_format_plp_summary(big, cap, b->target, sm, c);
+            if (len < 0) {
+                rc = len;
+            } else {
+                r->emit_summary(r->summary_user, big);
+            }
+        }
+        free(big);
+    }
     /* the consensus-indel gate of call_vars (:928-931) needs the indel fields even when no indel is called -- but
      * without BI / BD no event can win the consensus (its quality sum is 0, plp.c:1236-1270) */
     if (rc == LFQ_OK && (r->o.call_indels || b->any_bi || b->any_bd || r->idq.mode)) {

@@ -77,6 +77,13 @@ int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_nu
  * LFQ_ERR_INVALID, as is a read with a quality above 93 that would be realigned (from lfq_region_end).  Same calling rule as
  * lfq_region_set_indelqual: after lfq_region_open, before the first lfq_region_begin.  Not a field of lfq_region_opts. */
 int lfq_region_set_viterbi(lfq_region *r, int on, int def_qual);
+/* `lofreq call --plp-summary-only` / `lofreq plpsummary` beside the calls (opt-in; default off): with a callback, every region
+ * also emits the header line of plp_summary (lofreq_call.c:445-459) of each of its columns, in column order, BEFORE the region's
+ * VCF lines -- one lfq_readset_plp_summary call per region, which runs the indel pileup of the region whether or not indels are
+ * called.  The VCF lines and conf's counters are the same with and without it.  NULL switches it off again: such a run makes the
+ * launches it made before this function existed.  Same calling rule as lfq_region_set_max_depth: after lfq_region_open, before
+ * the first lfq_region_begin.  Not a field of lfq_region_opts. */
+int lfq_region_set_summary(lfq_region *r, lfq_region_emit_fn emit_summary_line_or_null, void *user);
 /* `ref`: the contig, upper-cased (plp.c:652), valid until the NEXT lfq_region_end / lfq_region_close has returned */
 int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, int64_t ref_len, int64_t beg0, int64_t end0);
 /* one BAM record that passed the flag filters of plp.c:608-632, in file order (position-sorted).  The fields are

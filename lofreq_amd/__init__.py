@@ -14,7 +14,8 @@ from .caller import (PileupBatch, SnvCaller, VarcallConf, filter_records, finali
 from .baq import baq_batch, encode_seq
 from .viterbi import viterbi_batch
 from .indelqual import indelqual_batch
-from .pileup import DeviceTracks, ReadSet, pileup_indel_columns, pileup_snv_tracks, skip_snv_columns
+from .pileup import (DeviceTracks, PlpSummary, ReadSet, format_plp_summary, pileup_indel_columns, pileup_snv_tracks,
+                     skip_snv_columns)
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
 
@@ -24,4 +25,5 @@ __all__ = [
     "filter_records", "finalize_pvals", "format_vcf", "format_vcf_record", "pvalue_from_log", "snvqual_thresh",
     "write_vcf_header", "LFQ_USE_IDAQ", "INDEL_RECORD_DTYPE", "IndelColumns", "call_indels", "format_indel_record", "filter_indel_records", "baq_batch", "viterbi_batch", "indelqual_batch", "encode_seq", "DeviceTracks", "pileup_snv_tracks",
     "source_qual_batch", "pileup_indel_columns", "skip_snv_columns", "ReadSet", "binom_cdf", "uniq_mtc",
+    "PlpSummary", "format_plp_summary",
 ]

@@ -108,6 +108,17 @@ class SitesTimes(C.Structure):
                 ("n_launches", C.c_int)]
 
 
+class PlpSummaryC(C.Structure):
+    """lfq_plp_summary: host arrays owned by the context"""
+    _fields_ = [("ncols", C.c_int64)] + [(n, C.c_void_p) for n in (
+        "col_pos", "ref_base", "fw", "rv", "num_heads", "num_tails", "num_ins", "num_dels", "hrun", "coverage_plp",
+        "cons_kind", "cons_nt", "cons_key_off", "cons_key_chars")]
+
+
+class SummaryTimes(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("n_cols", C.c_int64), ("n_ordered", C.c_int64), ("n_launches", C.c_int)]
+
+
 class PileupReads(C.Structure):
     _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in (
         "pos", "cigar_off", "cigar", "seq_off", "seq", "qual", "baq", "mapq", "reverse", "ref")] + [("ref_len", C.c_int64),
@@ -175,6 +186,7 @@ EXPORTS = [
     "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
     "lfq_readset_viterbi",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
+    "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
     "lfq_indelqual_batch", "lfq_readset_indelqual", "lfq_readset_fetch_indelquals", "lfq_last_indelqual_times",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
@@ -311,6 +323,9 @@ def load():
     L.lfq_readset_pileup_sites.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.POINTER(Tracks), vp, vp]
     L.lfq_readset_uniq.argtypes = [vp, vp, C.POINTER(UniqVariants), C.c_int, C.c_int, C.POINTER(UniqResult)]
     L.lfq_last_sites_times.argtypes = [vp, C.POINTER(SitesTimes)]
+    L.lfq_readset_plp_summary.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.POINTER(PlpSummaryC))]
+    L.lfq_format_plp_summary.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.POINTER(PlpSummaryC), C.c_int64]
+    L.lfq_last_summary_times.argtypes = [vp, C.POINTER(SummaryTimes)]
     L.lfq_set_max_depth.argtypes = [vp, C.c_int64]
     L.lfq_readset_kept_reads.argtypes = [vp, vp, vp, C.POINTER(C.c_int64)]
     L.lfq_source_qual_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, C.c_int, vp, vp, vp]

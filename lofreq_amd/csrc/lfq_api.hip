@@ -488,6 +488,11 @@ void lfq_destroy(lfq_ctx *c)
         for (int i = 0; i < 4; i++) {
             if (c->ev_sites_t[i]) (void)hipEventDestroy(c->ev_sites_t[i]);
         }
+        if (c->d_sum) (void)hipFree(c->d_sum);
+        if (c->h_sum) (void)hipHostFree(c->h_sum);
+        delete c->plp_sum;
+        if (c->ev_sum_t[0]) (void)hipEventDestroy(c->ev_sum_t[0]);
+        if (c->ev_sum_t[1]) (void)hipEventDestroy(c->ev_sum_t[1]);
         if (c->ev_baq_t[0]) (void)hipEventDestroy(c->ev_baq_t[0]);
         if (c->ev_baq_t[1]) (void)hipEventDestroy(c->ev_baq_t[1]);
         if (c->ev_idq_t[0]) (void)hipEventDestroy(c->ev_idq_t[0]);

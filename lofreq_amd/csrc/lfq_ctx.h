@@ -234,6 +234,7 @@ struct LfqIndelColsOwned {
     lfq_indel_columns cols;
     LfqVec<uint8_t> ref_base, cons_indel;
     LfqVec<int32_t> cov, tails, non_indels, n_ins, n_dels, hrun;
+    std::vector<int32_t> ne_qsum[2];     /* per column: ins_nonevent_qual / del_nonevent_qual (plp.c:810) where the column-major kernel summed them */
     struct Side {
         LfqVec<int32_t> non_fw, non_rv, ev_fw, ev_rv;
         LfqVec<int64_t> ne_off, ev_off, key_off, rd_off;
@@ -245,6 +246,7 @@ struct LfqIndelColsOwned {
         memset(&cols, 0, sizeof(cols));
         ref_base.clear(); cons_indel.clear();
         cov.clear(); tails.clear(); non_indels.clear(); n_ins.clear(); n_dels.clear(); hrun.clear();
+        ne_qsum[0].clear(); ne_qsum[1].clear();
         for (Side &s : side) {
             s.non_fw.clear(); s.non_rv.clear(); s.ev_fw.clear(); s.ev_rv.clear();
             s.ne_off.clear(); s.ev_off.clear(); s.key_off.clear(); s.rd_off.clear();
@@ -252,6 +254,15 @@ struct LfqIndelColsOwned {
             s.key_chars.clear();
         }
     }
+};
+
+/* what lfq_readset_plp_summary hands out (host arrays, valid until the next summary call on the context) */
+struct LfqSummaryOwned {
+    lfq_plp_summary sum;
+    std::vector<int64_t> col_pos, key_off;
+    std::vector<uint8_t> ref_base, cons_kind;
+    std::vector<int32_t> n_ins, n_dels, hrun, cov;
+    std::vector<char> key_chars;
 };
 
 #define LFQ_PIN_SLOTS 40
@@ -365,6 +376,14 @@ struct lfq_ctx {
     hipEvent_t ev_sites_t[4];        /* around the count pass, around the scatter pass (created on first use) */
     lfq_sites_times sites_times;     /* sites, observations and launches of the last call (the ms: from the events, when asked for) */
     int64_t plp_ncols;
+    /* lfq_readset_plp_summary: column list, increment table and the kernel's output (grow-only); the host arrays handed out */
+    uint8_t *d_sum;
+    int64_t sum_bytes;
+    uint8_t *h_sum;                  /* pinned: what the kernel wrote (fw | rv | heads | tails | consensus letter | path), handed out as it lies */
+    int64_t h_sum_bytes;
+    struct LfqSummaryOwned *plp_sum;
+    hipEvent_t ev_sum_t[2];          /* around the summary kernel (created on first use) */
+    lfq_summary_times sum_times;     /* columns, ordered columns and launches of the last call (the ms: from the events, when asked for) */
     /* BAQ scratch (lfq_baq_batch), kept between calls */
     double *d_baq_scr;
     int32_t *d_baq_expect;

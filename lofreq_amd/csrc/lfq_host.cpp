@@ -773,6 +773,39 @@ int lfq_format_indel_record(char *buf, int buflen, const char *chrom, int64_t po
                     ref_fw, ref_rv, alt_fw, alt_rv, hrun);
 }
 
+/* the header line of plp_summary for one column (lofreq_call.c:445-459), byte for byte */
+int lfq_format_plp_summary(char *buf, int buflen, const char *chrom, const lfq_plp_summary *s, int64_t col)
+{
+    if (!buf || buflen < 0 || !chrom || !s || col < 0 || col >= s->ncols) {
+        return LFQ_ERR_INVALID;
+    }
+    char cons[1024];                                        /* MAX_INDELSIZE is 256 (utils.h:38) */
+    const int64_t k0 = s->cons_key_off[col], k1 = s->cons_key_off[col + 1];
+    if (s->cons_kind[col] == 0) {
+        cons[0] = (char)s->cons_nt[col];
+        cons[1] = '\0';
+    } else {
+        if (k1 - k0 > (int64_t)sizeof(cons) - 2) {
+            return LFQ_ERR_CAPACITY;
+        }
+        cons[0] = s->cons_kind[col] == 1 ? '+' : '-';
+        memcpy(cons + 1, s->cons_key_chars + k0, (size_t)(k1 - k0));
+        cons[1 + (k1 - k0)] = '\0';
+    }
+    const int32_t *fw = s->fw + col * 5, *rv = s->rv + col * 5;
+    const int n = snprintf(buf, (size_t)buflen,
+                           "%s\t%d\t%c\t%s\tA:%lu/%lu\tC:%lu/%lu\tG:%lu/%lu\tT:%lu/%lu\tN:%lu/%lu\theads:%d\ttails:%d\tins:%d\tdels:%d\thrun:%d\n",
+                           chrom, (int)(s->col_pos[col] + 1), (char)s->ref_base[col], cons,
+                           (unsigned long)fw[0], (unsigned long)rv[0], (unsigned long)fw[1], (unsigned long)rv[1],
+                           (unsigned long)fw[2], (unsigned long)rv[2], (unsigned long)fw[3], (unsigned long)rv[3],
+                           (unsigned long)fw[4], (unsigned long)rv[4], s->num_heads[col], s->num_tails[col], s->num_ins[col],
+                           s->num_dels[col], s->hrun[col]);
+    if (n < 0) {
+        return LFQ_ERR_INVALID;
+    }
+    return n < buflen ? n : LFQ_ERR_CAPACITY;
+}
+
 /* many records at once; returns the number of bytes the full text needs (written if it fits) */
 int64_t lfq_format_vcf(char *buf, int64_t buflen, const char *chrom, const int64_t *pos0_or_null,
                        const lfq_snv_record *recs, int64_t n, const uint8_t *keep_or_null,

@@ -376,6 +376,23 @@ struct LfqSitesArgs {
     uint8_t *t_nt, *t_bq, *t_baq, *t_mq, *t_sq;
 };
 int lfq_launch_pileup_sites(const LfqSitesArgs &a, int scatter, void *stream);
+/* the header line of plp_summary (lfq_readset_plp_summary): position-sorted reads only, one wavefront per column */
+struct LfqSummaryArgs {
+    int64_t n_reads;
+    const int32_t *pos, *pmax_end, *read_idx;   /* see LfqPileupArgs (read_idx: the kept reads of a -d cap, or null) */
+    const int64_t *cigar_off, *seq_off;
+    const uint32_t *cigar;
+    const uint8_t *seq, *qual, *reverse;
+    int64_t n_cols;
+    const int64_t *col_pos;               /* [n_cols] the covered positions of the region */
+    int32_t min_plp_bq;
+    const double *incr;                   /* [94] 1 - 10^(-q / 10) from the host's pow, 0.0 replaced by DBL_MIN (plp.c:999-1005) */
+    int32_t *fw, *rv;                     /* [n_cols][5] fw_counts / rv_counts */
+    int32_t *heads, *tails;               /* [n_cols] num_heads / num_tails */
+    uint8_t *cons_nt;                     /* [n_cols] bam_nt4_rev_table[argmax_d(base_counts)] */
+    uint8_t *ordered;                     /* [n_cols] 1 where the sums were formed in pileup order */
+};
+int lfq_launch_plp_summary(const LfqSummaryArgs &a, void *stream);
 /* the kept reads of a -d cap as the pileup kernels take them (read_idx / pos / pmax_end of LfqPileupArgs): keep[r] != 0 for a
  * kept read; kept_idx / kept_pos / kept_pmax get one entry per kept read.  scratch: lfq_keep_compact_scratch(n) bytes, whose
  * first n int32 the caller fills with the reads' exclusive ends (computed on the host with the keep decision) */

@@ -1267,6 +1267,192 @@ int lfq_launch_pileup_sites(const LfqSitesArgs &a, int scatter, void *stream)
 }
 
 
+/* ---- the header line of plp_summary (lfq_readset_plp_summary; lofreq_call.c:445-459) ------------------------------------------
+ * What compile_plp_col keeps per column beside the quality arrays: fw_counts / rv_counts of the five nucleotides (plp.c:929-941,
+ * 1007-1011), num_heads / num_tails (:912-920, counted BEFORE the min_plp_bq filter, deleted / skipped entries never) and the
+ * consensus base, argmax_d over base_counts[nt4] += 1 - 10^(-bq / 10) with bq capped at 93 and an increment of 0.0 replaced by
+ * DBL_MIN (:949-953, 999-1007, 1255-1260; utils.c:87-98: the first maximum wins).  One wavefront per COLUMN (the covered positions
+ * of the region, which the indel pileup of the same call has found), the window walk of lfq_pileup_columns_kernel, the ten counts
+ * by ballots: no atomics, no LDS.
+ *
+ * The reference adds the increments one by one in pileup order, and a double sum depends on that order in its last bit.  Here
+ * every lane adds up its own reads and the wavefront reduces the 64 partial sums: another order.  For a sum of n non-negative
+ * terms, recursive summation in ANY order is off the exact sum S by at most (n - 1) u S (1 + O(n u)), u = 2^-53 (Higham, Accuracy
+ * and Stability of Numerical Algorithms, eq. 4.4).  With a >= b the two largest reduced sums and n the number of kept bases, the
+ * reference's two sums therefore stand in the same order as a and b whenever a - b > 2 (n - 1) u (A + B) for the exact sums A, B;
+ * the kernel asks for a - b > 4 n u (a + b), which covers that (n for n - 1, the reduced sums for the exact ones and the rounding
+ * of the bound itself are factors 1 + O(n u), n u < 2^-22, against a factor 2 of room).  A smaller third sum c trails a by at
+ * least as much, against a smaller bound.  A column that misses the gap takes the ORDERED path: the window is walked again, the
+ * lanes fetch their reads as before, and the five sums are formed add by add in pileup order -- the increments are handed from
+ * lane to lane in lane order, every lane doing the same additions -- then argmax_d.  ordered[col] says which path decided.
+ * Latency-bound like the sites kernel: window -> cigar_off -> CIGAR words -> seq_off -> quality byte -> increment. */
+__device__ __forceinline__ int lfq_plp_locate_tail(const uint32_t *cg, int n_cigar, int64_t x, int64_t p, int *qpos, bool *tail)
+{
+    int y = 0, kind = 0;                         /* -> 1: base at *qpos, 2: deleted / skipped, 0: no overlap */
+    for (int k = 0; k < n_cigar; ++k) {
+        const int op = cg[k] & 0xf, l = cg[k] >> 4;
+        const bool m = op == 0 || op == 7 || op == 8, d = op == 2 || op == 3;
+        if ((m || d) && kind == 0 && p >= x && p < x + l) {
+            kind = m ? 1 : 2;
+            *qpos = m ? y + (int)(p - x) : y;
+        }
+        if (m) {
+            x += l; y += l;
+        } else if (d) {
+            x += l;
+        } else if (op == 1 || op == 4) {
+            y += l;
+        }
+    }
+    *tail = (p == x - 1);                        /* x is now bam_endpos */
+    return kind;
+}
+
+__device__ __forceinline__ double lfq_wave_sum_f64(double x)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        x += __shfl_xor(x, s, 64);
+    }
+    return __shfl(x, 0, 64);
+}
+
+/* one lane's entry of the column: kind, the base's nt4 code, capped quality, strand; head / tail of its read */
+struct LfqSumEntry {
+    int kind, code, bq, rev;
+    bool head, tail;
+};
+
+__device__ __forceinline__ LfqSumEntry lfq_summary_entry(const LfqSummaryArgs &A, int64_t r, int64_t hi, int64_t p)
+{
+    LfqSumEntry e;
+    e.kind = e.code = e.bq = e.rev = 0;
+    e.head = e.tail = false;
+    if (r < hi) {
+        const int64_t rr = lfq_plp_read(A.read_idx, r);
+        const int64_t co = A.cigar_off[rr], s0 = A.seq_off[rr];
+        const int lq = (int)(A.seq_off[rr + 1] - s0);
+        const int64_t x = A.pos[r];
+        int qpos = 0;
+        e.kind = lfq_plp_locate_tail(A.cigar + co, (int)(A.cigar_off[rr + 1] - co), x, p, &qpos, &e.tail);
+        if (e.kind == 1 && qpos < lq) {
+            const uint32_t code = A.seq[s0 + qpos];
+            e.code = (int)(code > 4 ? 4u : code);                                              /* seq_nt16_int: every other code is N */
+            e.bq = A.qual[s0 + qpos];
+            e.rev = A.reverse[rr] ? 1 : 0;
+            e.head = p == x;
+        } else if (e.kind == 1) {
+            e.kind = 0;                                                                        /* (a CIGAR longer than its read) */
+        }
+    }
+    return e;
+}
+
+__global__ __launch_bounds__(256) void lfq_plp_summary_kernel(LfqSummaryArgs A)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.n_cols) {
+        return;
+    }
+    const int64_t p = A.col_pos[i];
+    const int64_t lo = lfq_wave_first_above(A.pmax_end, 0, A.n_reads, p, lane);
+    const int64_t hi = lfq_wave_first_above(A.pos, lo, A.n_reads, p, lane);
+    uint32_t fw0 = 0, fw1 = 0, fw2 = 0, fw3 = 0, fw4 = 0, rv0 = 0, rv1 = 0, rv2 = 0, rv3 = 0, rv4 = 0, n_head = 0, n_tail = 0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;            /* this lane's share of base_counts */
+    for (int64_t r0 = lo; r0 < hi; r0 += 64) {
+        const LfqSumEntry e = lfq_summary_entry(A, r0 + lane, hi, p);
+        const bool base = e.kind == 1, kept = base && e.bq >= A.min_plp_bq;
+        n_head += (uint32_t)__popcll(__ballot(base && e.head));                                /* plp.c:912-920 */
+        n_tail += (uint32_t)__popcll(__ballot(base && e.tail));
+        const uint64_t mf = __ballot(kept && !e.rev), mr = __ballot(kept && e.rev);
+        const uint64_t c0 = __ballot(e.code == 0), c1 = __ballot(e.code == 1), c2 = __ballot(e.code == 2),
+                       c3 = __ballot(e.code == 3), c4 = __ballot(e.code == 4);
+        fw0 += (uint32_t)__popcll(mf & c0); rv0 += (uint32_t)__popcll(mr & c0);
+        fw1 += (uint32_t)__popcll(mf & c1); rv1 += (uint32_t)__popcll(mr & c1);
+        fw2 += (uint32_t)__popcll(mf & c2); rv2 += (uint32_t)__popcll(mr & c2);
+        fw3 += (uint32_t)__popcll(mf & c3); rv3 += (uint32_t)__popcll(mr & c3);
+        fw4 += (uint32_t)__popcll(mf & c4); rv4 += (uint32_t)__popcll(mr & c4);
+        const double inc = kept ? A.incr[e.bq > 93 ? 93 : e.bq] : 0.0;                         /* plp.c:949-953, 999-1005 */
+        s0 += e.code == 0 ? inc : 0.0;
+        s1 += e.code == 1 ? inc : 0.0;
+        s2 += e.code == 2 ? inc : 0.0;
+        s3 += e.code == 3 ? inc : 0.0;
+        s4 += e.code == 4 ? inc : 0.0;
+    }
+    const uint32_t n_kept = fw0 + fw1 + fw2 + fw3 + fw4 + rv0 + rv1 + rv2 + rv3 + rv4;
+    int best = 0, ordered = 0;
+    if (n_kept > 0) {                                   /* (no kept base: all sums 0.0, argmax_d gives index 0) */
+        s0 = lfq_wave_sum_f64(s0);
+        s1 = lfq_wave_sum_f64(s1);
+        s2 = lfq_wave_sum_f64(s2);
+        s3 = lfq_wave_sum_f64(s3);
+        s4 = lfq_wave_sum_f64(s4);
+        double a = s0, b = -1.0;                        /* the largest sum (first of equals) and the largest of the rest */
+        if (s1 > a) { b = a; a = s1; best = 1; } else if (s1 > b) { b = s1; }
+        if (s2 > a) { b = a; a = s2; best = 2; } else if (s2 > b) { b = s2; }
+        if (s3 > a) { b = a; a = s3; best = 3; } else if (s3 > b) { b = s3; }
+        if (s4 > a) { b = a; a = s4; best = 4; } else if (s4 > b) { b = s4; }
+        const double bound = 4.0 * (double)n_kept * 0x1p-53 * (a + b);
+        if (!(a - b > bound)) {
+            /* the ordered path: base_counts add by add in pileup order (wave-uniform: every lane does the same additions) */
+            ordered = 1;
+            s0 = s1 = s2 = s3 = s4 = 0.0;
+            for (int64_t r0 = lo; r0 < hi; r0 += 64) {
+                const LfqSumEntry e = lfq_summary_entry(A, r0 + lane, hi, p);
+                const bool kept = e.kind == 1 && e.bq >= A.min_plp_bq;
+                const double inc = kept ? A.incr[e.bq > 93 ? 93 : e.bq] : 0.0;
+                uint64_t m = __ballot(kept);
+                while (m) {
+                    const int l = (int)__builtin_ctzll(m);
+                    m &= m - 1;
+                    const double v = __shfl(inc, l, 64);
+                    const int cd = __shfl(e.code, l, 64);
+                    s0 = cd == 0 ? s0 + v : s0;
+                    s1 = cd == 1 ? s1 + v : s1;
+                    s2 = cd == 2 ? s2 + v : s2;
+                    s3 = cd == 3 ? s3 + v : s3;
+                    s4 = cd == 4 ? s4 + v : s4;
+                }
+            }
+            best = 0;                                   /* argmax_d, utils.c:87-98 */
+            a = s0;
+            if (s1 > a) { a = s1; best = 1; }
+            if (s2 > a) { a = s2; best = 2; }
+            if (s3 > a) { a = s3; best = 3; }
+            if (s4 > a) { a = s4; best = 4; }
+        }
+    }
+    uint32_t v = fw0;                                   /* lanes 0..4: fw, 5..9: rv, 10: heads, 11: tails */
+    v = lane == 1 ? fw1 : v; v = lane == 2 ? fw2 : v; v = lane == 3 ? fw3 : v; v = lane == 4 ? fw4 : v;
+    v = lane == 5 ? rv0 : v; v = lane == 6 ? rv1 : v; v = lane == 7 ? rv2 : v; v = lane == 8 ? rv3 : v; v = lane == 9 ? rv4 : v;
+    v = lane == 10 ? n_head : v; v = lane == 11 ? n_tail : v;
+    if (lane < 5) {
+        A.fw[i * 5 + lane] = (int32_t)v;
+    } else if (lane < 10) {
+        A.rv[i * 5 + lane - 5] = (int32_t)v;
+    } else if (lane == 10) {
+        A.heads[i] = (int32_t)v;
+    } else if (lane == 11) {
+        A.tails[i] = (int32_t)v;
+    }
+    if (lane == 0) {
+        A.cons_nt[i] = (uint8_t)(best == 0 ? 'A' : best == 1 ? 'C' : best == 2 ? 'G' : best == 3 ? 'T' : 'N');     /* bam_nt4_rev_table */
+        A.ordered[i] = (uint8_t)ordered;
+    }
+}
+
+int lfq_launch_plp_summary(const LfqSummaryArgs &a, void *stream)
+{
+    if (a.n_cols <= 0) {
+        return LFQ_OK;
+    }
+    const dim3 grid((unsigned)((a.n_cols + 3) / 4)), block(256);
+    hipLaunchKernelGGL(lfq_plp_summary_kernel, grid, block, 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
+}
+
+
 /* ---- indel pseudo-columns on the device ----------------------------------------------------------------------
  * One wavefront per tested event: the column's reads without an event of that side (indel quality, MAPQ) followed
  * by the reads of all its events, the tested one's marked as the alt allele and carrying their alignment quality

@@ -2535,6 +2535,8 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
     }
     /* 6. publish */
     lfq_indel_columns &C = O.cols;
+    O.ne_qsum[0].swap(qsum[0]);             /* kept for lfq_readset_plp_summary (the key of a consensus indel) */
+    O.ne_qsum[1].swap(qsum[1]);
     C.cons_indel = O.cons_indel.data();
     C.ncols = (int64_t)O.cov.size();
     C.ref_base = O.ref_base.data();
@@ -2563,6 +2565,239 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
         T.rd_aq = S.rd_aq.data();
         T.rd_mq = S.rd_mq.data();
         T.rd_sq = S.rd_sq.data();
+    }
+    return LFQ_OK;
+}
+
+/* ---- plp_summary's header line (lofreq_call.c:445-459) for the columns of a region -------------------------------------------
+ * The indel side (coverage_plp, num_tails, num_ins, num_dels, hrun, the event tables and the non-event quality sums) is the
+ * indel pileup's of the same read set and region, run here; lfq_plp_summary_kernel adds the strand-resolved base counts,
+ * num_heads and the consensus base on the columns it found; the key of a consensus indel is picked from the event tables here
+ * (plp.c:1231-1268: the first event of a side whose quality sum is strictly greatest, against the side's non-event sum; an
+ * insertion before a deletion). */
+static const double *summary_incr_table()
+{
+    static double tab[94];
+    static const bool done = [] {
+        for (int q = 0; q < 94; q++) {
+            double v = 1.0 - pow(10.0, -1.0 * q / 10.0);       /* 1.0 - PHREDQUAL_TO_PROB(bq), plp.c:999 */
+            if (v == 0.0) {
+                v = DBL_MIN;                                    /* plp.c:1003-1005 */
+            }
+            tab[q] = v;
+        }
+        return true;
+    }();
+    (void)done;
+    return tab;
+}
+
+int lfq_readset_plp_summary(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, int64_t region_end, int min_plp_bq,
+                            int min_plp_idq, const lfq_plp_summary **out)
+{
+    if (!c || !rs || rs->c != c || !out || region_end < region_begin || region_begin < 0 || region_end > rs->ref_len
+        || min_plp_bq < 0 || (rs->n > 0 && (!rs->seq || !rs->qual || !rs->mapq || !rs->reverse))) {
+        return LFQ_ERR_INVALID;
+    }
+    if (!c->plp_sum) {
+        c->plp_sum = new LfqSummaryOwned();
+    }
+    LfqSummaryOwned &S = *c->plp_sum;
+    memset(&S.sum, 0, sizeof(S.sum));
+    memset(&c->sum_times, 0, sizeof(c->sum_times));
+    S.col_pos.clear();
+    S.key_chars.clear();
+    S.key_off.assign(1, 0);
+    S.ref_base.clear();
+    S.cons_kind.clear();
+    for (auto *v : {&S.n_ins, &S.n_dels, &S.hrun, &S.cov}) {
+        v->clear();
+    }
+    auto publish = [&S, out]() {
+        lfq_plp_summary &P = S.sum;
+        P.ncols = (int64_t)S.col_pos.size();
+        P.col_pos = S.col_pos.data();
+        P.ref_base = S.ref_base.data();
+        P.fw = P.rv = P.num_heads = P.num_tails = nullptr;      /* (ncols > 0: set to the pinned block by the caller) */
+        P.num_ins = S.n_ins.data();
+        P.num_dels = S.n_dels.data();
+        P.hrun = S.hrun.data();
+        P.coverage_plp = S.cov.data();
+        P.cons_kind = S.cons_kind.data();
+        P.cons_nt = nullptr;
+        P.cons_key_off = S.key_off.data();
+        S.key_chars.push_back('\0');
+        P.cons_key_chars = S.key_chars.data();
+        *out = &P;
+        return LFQ_OK;
+    };
+    const int64_t width = region_end - region_begin;
+    if (rs->n == 0 || width == 0) {
+        return publish();
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    hipStream_t ps = c->stream;
+    LFQ_TRY(readset_upload_wait(rs, ps));
+    const int32_t *pmax = readset_pmax(c, rs, ps);
+    if (!pmax) {
+        return LFQ_ERR_INVALID;             /* the window search needs position-sorted reads (lfq_set_pileup_unsorted does not apply) */
+    }
+    /* the indel side: the context's current lfq_indel_columns are this region's from here on */
+    const lfq_indel_columns *ic = nullptr;
+    S.col_pos.resize((size_t)width);
+    const int rc_ind = lfq_readset_pileup_indels(c, rs, region_begin, region_end, min_plp_idq, &ic, S.col_pos.data());
+    if (rc_ind != LFQ_OK) {
+        S.col_pos.clear();
+        return rc_ind;
+    }
+    const int64_t ncols = ic->ncols;
+    S.col_pos.resize((size_t)ncols);
+    if (ncols == 0) {
+        return publish();
+    }
+    const LfqIndelColsOwned &O = *c->plp_indel;
+    if (O.ne_qsum[0].size() != (size_t)ncols || O.ne_qsum[1].size() != (size_t)ncols) {
+        return LFQ_ERR_INVALID;             /* (cannot happen: sorted reads go to the kernel that sums the qualities) */
+    }
+    for (int i = 0; i < 2; i++) {
+        if (!c->ev_sum_t[i]) {
+            LFQ_TRY_HIP(hipEventCreate(&c->ev_sum_t[i]));
+        }
+    }
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    /* what goes up in one copy: column positions | increment table; what the kernel writes and one copy brings back into pinned
+     * memory, where the struct points at it: fw | rv | heads | tails | consensus letter | path */
+    const int64_t o_pos = 0, o_incr = o_pos + al(ncols * 8), o_cnt = o_incr + al(94 * 8), o_rv = o_cnt + al(ncols * 20),
+                  o_heads = o_rv + al(ncols * 20), o_tails = o_heads + al(ncols * 4), o_cons = o_tails + al(ncols * 4),
+                  o_ord = o_cons + al(ncols), total = o_ord + al(ncols);
+    LFQ_TRY(grow(&c->d_sum, &c->sum_bytes, total));
+    uint8_t *d = c->d_sum;
+    if (total - o_cnt > c->h_sum_bytes) {
+        if (c->h_sum) (void)hipHostFree(c->h_sum);
+        c->h_sum = nullptr;
+        c->h_sum_bytes = 0;
+        if (hipHostMalloc((void **)&c->h_sum, (size_t)(total - o_cnt), hipHostMallocDefault) != hipSuccess) {
+            return LFQ_ERR_NOMEM;
+        }
+        c->h_sum_bytes = total - o_cnt;
+    }
+    const uint8_t *h = c->h_sum - o_cnt;                    /* h + o_x: where the device's d + o_x lands */
+    /* -d cap: the decision both pileups share (before the first copy is queued: nothing below returns with one in flight) */
+    const int32_t *k_idx, *k_pos, *k_pmax;
+    LFQ_TRY(readset_keep_device(c, rs, ps, &k_idx, &k_pos, &k_pmax));
+    LfqPin<uint8_t> up(c, (size_t)o_cnt);
+    LFQ_PIN_OK(up);
+    memcpy(up.data() + o_pos, S.col_pos.data(), (size_t)ncols * 8);
+    memcpy(up.data() + o_incr, summary_incr_table(), 94 * 8);
+    int rc = hipMemcpyAsync(d, up.data(), (size_t)o_cnt, hipMemcpyHostToDevice, ps) == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
+    LfqSummaryArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_reads = rs->n;
+    A.pos = (const int32_t *)rs->d_pos;
+    A.pmax_end = pmax;
+    A.cigar_off = (const int64_t *)rs->d_coff;
+    A.seq_off = (const int64_t *)rs->d_soff;
+    A.cigar = (const uint32_t *)rs->d_cig;
+    A.seq = rs->d_seq;
+    A.qual = rs->d_qual;
+    A.reverse = rs->d_rev;
+    A.n_cols = ncols;
+    A.col_pos = (const int64_t *)(d + o_pos);
+    A.min_plp_bq = min_plp_bq;
+    A.incr = (const double *)(d + o_incr);
+    A.fw = (int32_t *)(d + o_cnt);
+    A.rv = (int32_t *)(d + o_rv);
+    A.heads = (int32_t *)(d + o_heads);
+    A.tails = (int32_t *)(d + o_tails);
+    A.cons_nt = d + o_cons;
+    A.ordered = d + o_ord;
+    if (k_idx) {                            /* -d cap: the kept reads only */
+        A.n_reads = rs->n_kept;
+        A.read_idx = k_idx;
+        A.pos = k_pos;
+        A.pmax_end = k_pmax;
+    }
+    if (rc == LFQ_OK && hipEventRecord(c->ev_sum_t[0], ps) != hipSuccess) {
+        rc = LFQ_ERR_HIP;
+    }
+    if (rc == LFQ_OK) {
+        rc = lfq_launch_plp_summary(A, ps);
+    }
+    if (rc == LFQ_OK && (hipEventRecord(c->ev_sum_t[1], ps) != hipSuccess
+                         || hipMemcpyAsync(c->h_sum, d + o_cnt, (size_t)(total - o_cnt), hipMemcpyDeviceToHost, ps) != hipSuccess)) {
+        rc = LFQ_ERR_HIP;
+    }
+    if (rc == LFQ_OK) {
+        c->sum_times.n_launches = 1;
+        c->sum_times.n_cols = ncols;
+    }
+    /* the indel side's share of the struct and the consensus indels, while the kernel runs */
+    S.cons_kind.assign((size_t)ncols, 0);
+    S.key_off.resize((size_t)ncols + 1);
+    S.ref_base.assign(ic->ref_base, ic->ref_base + ncols);
+    S.n_ins.assign(ic->num_ins, ic->num_ins + ncols);
+    S.n_dels.assign(ic->num_dels, ic->num_dels + ncols);
+    S.hrun.assign(ic->hrun, ic->hrun + ncols);
+    S.cov.assign(ic->coverage_plp, ic->coverage_plp + ncols);
+    for (int64_t col = 0; col < ncols; col++) {
+        /* consensus indel, plp.c:1231-1268 */
+        int64_t best_ev[2] = {-1, -1};
+        for (int sd = 0; sd < 2; sd++) {
+            const lfq_indel_side &T = ic->side[sd];
+            int64_t best = 0;
+            for (int64_t e = T.ev_off[col]; e < T.ev_off[col + 1]; e++) {
+                int64_t sum = 0;                                    /* cons_quals, utils.c:569, 629 */
+                for (int64_t i = T.rd_off[e]; i < T.rd_off[e + 1]; i++) {
+                    sum += T.rd_q[i];
+                }
+                if (sum > best) {
+                    best = sum;
+                    best_ev[sd] = e;
+                }
+            }
+            if (best_ev[sd] >= 0 && !(best > (int64_t)O.ne_qsum[sd][(size_t)col])) {
+                best_ev[sd] = -1;
+            }
+        }
+        const int sd = best_ev[0] >= 0 ? 0 : (best_ev[1] >= 0 ? 1 : -1);
+        if (sd >= 0) {
+            const lfq_indel_side &T = ic->side[sd];
+            S.cons_kind[(size_t)col] = (uint8_t)(sd + 1);
+            S.key_chars.insert(S.key_chars.end(), T.key_chars + T.key_off[best_ev[sd]], T.key_chars + T.key_off[best_ev[sd] + 1]);
+        }
+        S.key_off[(size_t)col + 1] = (int64_t)S.key_chars.size();
+    }
+    if (hipStreamSynchronize(ps) != hipSuccess) {       /* on every path: `up` goes back to the pool on return */
+        rc = LFQ_ERR_HIP;
+    }
+    LFQ_TRY(rc);
+    int64_t n_ordered = 0;
+    for (int64_t col = 0; col < ncols; col++) {
+        n_ordered += (h + o_ord)[col];
+    }
+    c->sum_times.n_ordered = n_ordered;
+    publish();
+    S.sum.fw = (const int32_t *)(h + o_cnt);
+    S.sum.rv = (const int32_t *)(h + o_rv);
+    S.sum.num_heads = (const int32_t *)(h + o_heads);
+    S.sum.num_tails = (const int32_t *)(h + o_tails);
+    S.sum.cons_nt = h + o_cons;
+    return LFQ_OK;
+}
+
+int lfq_last_summary_times(lfq_ctx *c, lfq_summary_times *t)
+{
+    if (!c || !t) {
+        return LFQ_ERR_INVALID;
+    }
+    *t = c->sum_times;
+    if (t->n_launches > 0) {
+        LFQ_TRY_HIP(hipSetDevice(c->device));
+        LFQ_TRY_HIP(hipEventSynchronize(c->ev_sum_t[1]));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c->ev_sum_t[0], c->ev_sum_t[1]) == hipSuccess) {
+            t->kernel_ms = ms;
+        }
     }
     return LFQ_OK;
 }

@@ -204,6 +204,62 @@ def skip_snv_columns(caller, skip):
                "lfq_pileup_skip_snv_columns")
 
 
+class PlpSummary:
+    """The header fields of `lofreq plpsummary` for the columns of a region (`lfq_plp_summary`, copied): col_pos, ref_base, fw /
+    rv ([ncols, 5]: A, C, G, T, N), num_heads, num_tails, num_ins, num_dels, hrun, coverage_plp, cons_kind (0 base, 1 '+', 2
+    '-') as numpy arrays and cons, the list of the columns' consensus strings as plp_summary prints them"""
+
+    def __init__(self, ptr):
+        cs = ptr.contents
+        n = self.ncols = int(cs.ncols)
+
+        def arr(p, count, dt):
+            if count == 0 or not p:
+                return np.zeros(0, dt)
+            return np.frombuffer(C.string_at(p, count * np.dtype(dt).itemsize), dtype=dt).copy()
+
+        self.col_pos = arr(cs.col_pos, n, np.int64)
+        self.ref_base = arr(cs.ref_base, n, np.uint8)
+        self.fw = arr(cs.fw, n * 5, np.int32).reshape(n, 5)
+        self.rv = arr(cs.rv, n * 5, np.int32).reshape(n, 5)
+        for name in ("num_heads", "num_tails", "num_ins", "num_dels", "hrun", "coverage_plp"):
+            setattr(self, name, arr(getattr(cs, name), n, np.int32))
+        self.cons_kind = arr(cs.cons_kind, n, np.uint8)
+        self.cons_nt = arr(cs.cons_nt, n, np.uint8)
+        self.cons_key_off = arr(cs.cons_key_off, n + 1, np.int64) if n else np.zeros(1, np.int64)
+        self.cons_key_chars = arr(cs.cons_key_chars, int(self.cons_key_off[-1]) + 1, np.uint8)
+        keys = self.cons_key_chars.tobytes()
+        self.cons = [(chr(self.cons_nt[i]) if self.cons_kind[i] == 0 else
+                      "+-"[self.cons_kind[i] - 1] + keys[self.cons_key_off[i]:self.cons_key_off[i + 1]].decode())
+                     for i in range(n)]
+
+    def _as_c(self):
+        """an lfq_plp_summary over this object's arrays (kept alive by the returned tuple)"""
+        keep = [np.ascontiguousarray(a) for a in (self.col_pos, self.ref_base, self.fw, self.rv, self.num_heads, self.num_tails,
+                                                  self.num_ins, self.num_dels, self.hrun, self.coverage_plp, self.cons_kind,
+                                                  self.cons_nt, self.cons_key_off, self.cons_key_chars)]
+        cs = _lib.PlpSummaryC()
+        cs.ncols = self.ncols
+        for (name, _), a in zip(_lib.PlpSummaryC._fields_[1:], keep):
+            setattr(cs, name, a.ctypes.data)
+        return cs, keep
+
+
+def format_plp_summary(chrom, summary):
+    """`lfq_format_plp_summary` for every column of a PlpSummary -> list of the header lines of plp_summary (lofreq_call.c:
+    445-459), each with its newline"""
+    L = _lib.load()
+    cs, _keep = summary._as_c()
+    chrom = chrom if isinstance(chrom, bytes) else str(chrom).encode()
+    buf = C.create_string_buffer(len(chrom) + 2048)
+    lines = []
+    for col in range(summary.ncols):
+        n = L.lfq_format_plp_summary(buf, len(buf), chrom, C.byref(cs), col)
+        _lib.check(min(n, 0), "lfq_format_plp_summary")
+        lines.append(buf.raw[:n].decode())
+    return lines
+
+
 class ReadSet:
     """The reads of one contig region resident on the device (`lfq_readset`): upload once, then BAQ / IDAQ, source
     quality, both pileups and the calls without the per-base arrays leaving HBM.
@@ -414,6 +470,23 @@ class ReadSet:
         _lib.check(self.L.lfq_readset_uniq(self.caller.h, self.h, C.byref(v), 1 if use_det_lim else 0, int(min_plp_bq),
                                            C.byref(o)), "lfq_readset_uniq")
         return {k: a[:n] for k, a in res.items()}
+
+    def plp_summary(self, begin, end, min_plp_bq=3, min_plp_idq=0, max_depth=None):
+        """lfq_readset_plp_summary: the header fields of `lofreq plpsummary` for the covered positions of [begin, end), numbered as
+        the columns of pileup_snv / pileup_indels -> PlpSummary.  Runs the indel pileup of the region: an IndelColumns obtained
+        earlier from this caller is superseded (call_indels then packs it from its host copy), as after pileup_indels"""
+        out = C.POINTER(_lib.PlpSummaryC)()
+        with _MaxDepth(self.caller, max_depth):
+            _lib.check(self.L.lfq_readset_plp_summary(self.caller.h, self.h, int(begin), int(end), int(min_plp_bq),
+                                                      int(min_plp_idq), C.byref(out)), "lfq_readset_plp_summary")
+        self.caller._indel_gen = getattr(self.caller, "_indel_gen", 0) + 1
+        return PlpSummary(out)
+
+    def last_summary_times(self):
+        """lfq_last_summary_times of the caller's context -> _lib.SummaryTimes"""
+        t = _lib.SummaryTimes()
+        _lib.check(self.L.lfq_last_summary_times(self.caller.h, C.byref(t)), "lfq_last_summary_times")
+        return t
 
     def last_sites_times(self):
         """lfq_last_sites_times of the caller's context -> _lib.SitesTimes"""

@@ -44,6 +44,7 @@ extern "C" {
 /* 9: lfq_indelqual_batch, lfq_readset_indelqual, lfq_readset_fetch_indelquals, lfq_last_indelqual_times. */
 /* (10 still: lfq_readset_pileup_sites, lfq_readset_uniq, lfq_last_sites_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_readset_plp_summary, lfq_format_plp_summary, lfq_last_summary_times are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_plp_quals_from_tracks, lfq_format_plp_quals, lfq_format_plp_indel_quals, lfq_set_indel_arrays_all_columns, lfq_last_plp_quals_times are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -889,7 +890,8 @@ int lfq_last_sites_times(lfq_ctx *ctx, lfq_sites_times *t);
  * LFQ_ERR_INVALID, before anything is launched: a NULL ctx, rs or out (before a device is touched); region_end < region_begin; a
  * region outside [0, ref_len]; min_plp_bq < 0; reads that are not position-sorted (lfq_set_pileup_unsorted does not apply).  An
  * empty region, an empty read set or a region no read covers: LFQ_OK, ncols = 0, no summary launch.
- * The indented quality lines of plp_summary (lofreq_call.c:460-597) are not produced: the tracks and event tables carry them. */
+ * The indented quality lines of plp_summary (lofreq_call.c:460-598) come from lfq_plp_quals_from_tracks + lfq_format_plp_quals (the
+ * nucleotide lines) and lfq_format_plp_indel_quals (the indel lines and the closing empty line), below. */
 typedef struct lfq_plp_summary {
     int64_t ncols;
     const int64_t *col_pos;            /* [ncols] 0-based positions */
@@ -915,6 +917,55 @@ typedef struct lfq_summary_times {
     int n_launches;
 } lfq_summary_times;
 int lfq_last_summary_times(lfq_ctx *ctx, lfq_summary_times *t);
+
+/* --- the quality lines of plp_summary (lofreq_call.c:460-598) ---------------------------------------------------------------
+ * lfq_plp_quals_from_tracks: the bq / baq / mq / sq bytes of the columns [col_begin, col_end) of SNV tracks, per column stably
+ * partitioned by nucleotide code in A, C, G, T, N order (a code above 4 counts as N) -- base_quals[nt4], baq_quals[nt4],
+ * map_quals[nt4], source_quals[nt4] of plp_col_t (plp.c:954-975) -- with pileup order kept inside each group, and the five
+ * group sizes of every column as offsets.  One kernel (lfq_plp_group_kernel), one wavefront per column.
+ * tracks_on_device != 0: the tracks lfq_readset_pileup_snv / lfq_pileup_snv_tracks / lfq_readset_pileup_sites returned; the
+ * kernel is queued behind their scatter pass on the context's stream.  Otherwise host tracks, whose columns of the range are
+ * uploaded into the context's buffers.  The column range lets a caller page through a region: the output is as large as the
+ * tracks of the range.  The results are pinned host memory owned by the context, grow only, valid until the next call of this
+ * function on it; the SNV tracks, the buffers of lfq_readset_pileup_sites and the arrays of lfq_readset_plp_summary are
+ * untouched.
+ * Observations are in the reference's order only where the tracks are: that holds for position-sorted reads (the column-major
+ * kernels), and is NOT promised for tracks made under lfq_set_pileup_unsorted.
+ * LFQ_ERR_INVALID, before anything is launched: a NULL ctx, tracks or out (before a device is touched); a range outside
+ * [0, tracks->ncols] or col_end < col_begin; LFQ_TRACKS_NT_PACKED tracks (lfq_set_pileup_nt_packed(ctx, 0) gives byte tracks).
+ * An empty range or a range without observations: LFQ_OK, no launch (lfq_plp_quals_times.n_launches = 0). */
+typedef struct lfq_plp_quals {
+    int64_t ncols, col_begin;          /* columns [col_begin, col_begin + ncols) of the tracks */
+    const int64_t *nt_off;             /* [5 * ncols + 1]: group (column i, nt k) = [nt_off[5i + k], nt_off[5i + k + 1]) */
+    const uint8_t *bq, *baq, *mq, *sq; /* grouped bytes, track encoding unchanged; baq / sq NULL when the tracks have none */
+} lfq_plp_quals;
+int lfq_plp_quals_from_tracks(lfq_ctx *ctx, const lfq_tracks *tracks, int tracks_on_device,
+                              int64_t col_begin, int64_t col_end, const lfq_plp_quals **out);
+/* lofreq_call.c:460-489 for column col (a column index of the TRACKS, inside the struct's range): for every nucleotide with a
+ * non-empty group, in A C G T N order, the lines "  %c\tBQ =\t", BAQ, MQ and, with LFQ_USE_SQ in flag, SQ, each followed by
+ * " %d" per value and "\n".  BQ: the byte.  BAQ: -1 for every value unless LFQ_USE_BAQ is in flag (:478), else the byte with
+ * 255 -> -1.  MQ: the byte as it is (255 prints 255).  SQ: 255 -> -1, 254 -> 49314 (the one value above 253 source_qual returns,
+ * plp.c:521).  LFQ_USE_BAQ without a baq array or LFQ_USE_SQ without an sq array: LFQ_ERR_INVALID (the reference would read an
+ * empty array).  Returns the length written (without the NUL); buf == NULL && buflen == 0: the length needed (lines grow with
+ * the depth); LFQ_ERR_CAPACITY when text and NUL do not fit; LFQ_ERR_INVALID for a NULL struct or a column outside its range.
+ * Pure host code. */
+int lfq_format_plp_quals(char *buf, int64_t buflen, const lfq_plp_quals *q, int64_t col, int flag);
+/* on = 1: from then on lfq_readset_pileup_indels / lfq_pileup_indel_columns (and the indel pileup lfq_readset_plp_summary runs)
+ * give ne_off / ne_q / ne_mq -- ins_quals / ins_map_quals, del_quals / del_map_quals -- for EVERY column, not only for those
+ * with an event: what plp_summary's "+0" / "-0" lines print.  Costs 8 bytes per observation and region (two int16 per side) on
+ * the device and, with lfq_set_indel_arrays_on_host(ctx, 1) -- which lfq_format_plp_indel_quals needs --, in the copy back.
+ * lfq_call_indels_batch reads the arrays at event columns only (through ne_off): same records.  Default 0: every byte as before. */
+int lfq_set_indel_arrays_all_columns(lfq_ctx *ctx, int on);
+/* lofreq_call.c:491-598 for column col: "  +0\tIDQ =\t" / "  +0\tMQ =\t" over the reads without an insertion, every insertion
+ * event in table order ("  +KEY\tIQ =\t", MQ, AQ, SQ), the same for "-0" and the deletion events (IDQ, MQ, AQ, SQ), and the
+ * closing empty line.  Values are the int16 entries as they are (-1 = missing); rd_sq saturates at 32767, which prints as 49314.
+ * Return rules of lfq_format_plp_quals.  LFQ_ERR_INVALID also when ne_q / ne_mq are NULL (device-only arrays), or when the column
+ * has non-event reads by its counts but an empty ne_off range (lfq_set_indel_arrays_all_columns off). */
+int lfq_format_plp_indel_quals(char *buf, int64_t buflen, const lfq_indel_columns *cols, int64_t col);
+/* the kernel of the context's last lfq_plp_quals_from_tracks call on the device's clock, its columns and observations;
+ * n_launches = 0 (and 0 ms) where nothing was launched */
+typedef struct lfq_plp_quals_times { double kernel_ms; int64_t n_cols, n_obs; int n_launches; } lfq_plp_quals_times;
+int lfq_last_plp_quals_times(lfq_ctx *ctx, lfq_plp_quals_times *t);
 
 /* --- synthetic workload (bench / tests): fills device tracks per include/lofreq_synth.h --- */
 int lfq_synth_fill_device(lfq_ctx *ctx, uint64_t seed, uint32_t depth, uint32_t plant_period,

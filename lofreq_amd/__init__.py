@@ -14,7 +14,8 @@ from .caller import (PileupBatch, SnvCaller, VarcallConf, filter_records, finali
 from .baq import baq_batch, encode_seq
 from .viterbi import viterbi_batch
 from .indelqual import indelqual_batch
-from .pileup import (DeviceTracks, PlpSummary, ReadSet, format_plp_summary, pileup_indel_columns, pileup_snv_tracks,
+from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_indel_quals, format_plp_quals,
+                     format_plp_summary, last_plp_quals_times, pileup_indel_columns, pileup_snv_tracks, plp_quals,
                      skip_snv_columns)
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
@@ -26,4 +27,5 @@ __all__ = [
     "write_vcf_header", "LFQ_USE_IDAQ", "INDEL_RECORD_DTYPE", "IndelColumns", "call_indels", "format_indel_record", "filter_indel_records", "baq_batch", "viterbi_batch", "indelqual_batch", "encode_seq", "DeviceTracks", "pileup_snv_tracks",
     "source_qual_batch", "pileup_indel_columns", "skip_snv_columns", "ReadSet", "binom_cdf", "uniq_mtc",
     "PlpSummary", "format_plp_summary",
+    "PlpQuals", "plp_quals", "format_plp_quals", "format_plp_indel_quals", "last_plp_quals_times",
 ]

@@ -119,6 +119,15 @@ class SummaryTimes(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("n_cols", C.c_int64), ("n_ordered", C.c_int64), ("n_launches", C.c_int)]
 
 
+class PlpQualsC(C.Structure):
+    """lfq_plp_quals: pinned host arrays owned by the context"""
+    _fields_ = [("ncols", C.c_int64), ("col_begin", C.c_int64)] + [(n, C.c_void_p) for n in ("nt_off", "bq", "baq", "mq", "sq")]
+
+
+class PlpQualsTimes(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("n_cols", C.c_int64), ("n_obs", C.c_int64), ("n_launches", C.c_int)]
+
+
 class PileupReads(C.Structure):
     _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in (
         "pos", "cigar_off", "cigar", "seq_off", "seq", "qual", "baq", "mapq", "reverse", "ref")] + [("ref_len", C.c_int64),
@@ -187,6 +196,8 @@ EXPORTS = [
     "lfq_readset_viterbi",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
+    "lfq_plp_quals_from_tracks", "lfq_format_plp_quals", "lfq_set_indel_arrays_all_columns", "lfq_format_plp_indel_quals",
+    "lfq_last_plp_quals_times",
     "lfq_indelqual_batch", "lfq_readset_indelqual", "lfq_readset_fetch_indelquals", "lfq_last_indelqual_times",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
@@ -326,6 +337,11 @@ def load():
     L.lfq_readset_plp_summary.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.POINTER(PlpSummaryC))]
     L.lfq_format_plp_summary.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.POINTER(PlpSummaryC), C.c_int64]
     L.lfq_last_summary_times.argtypes = [vp, C.POINTER(SummaryTimes)]
+    L.lfq_plp_quals_from_tracks.argtypes = [vp, C.POINTER(Tracks), C.c_int, C.c_int64, C.c_int64, C.POINTER(C.POINTER(PlpQualsC))]
+    L.lfq_format_plp_quals.argtypes = [C.c_char_p, C.c_int64, C.POINTER(PlpQualsC), C.c_int64, C.c_int]
+    L.lfq_set_indel_arrays_all_columns.argtypes = [vp, C.c_int]
+    L.lfq_format_plp_indel_quals.argtypes = [C.c_char_p, C.c_int64, C.POINTER(IndelColumnsC), C.c_int64]
+    L.lfq_last_plp_quals_times.argtypes = [vp, C.POINTER(PlpQualsTimes)]
     L.lfq_set_max_depth.argtypes = [vp, C.c_int64]
     L.lfq_readset_kept_reads.argtypes = [vp, vp, vp, C.POINTER(C.c_int64)]
     L.lfq_source_qual_batch.argtypes = [vp, C.POINTER(BaqReads), C.c_int, C.c_int, vp, vp, vp]

@@ -202,6 +202,11 @@ class SnvCaller:
         """lfq_set_indel_arrays_on_host: off = the quality arrays of the indel columns stay on the device only"""
         _lib.check(self.L.lfq_set_indel_arrays_on_host(self.h, 1 if on else 0), "lfq_set_indel_arrays_on_host")
 
+    def set_indel_arrays_all_columns(self, on):
+        """lfq_set_indel_arrays_all_columns: on = the indel pileups give ne_off / ne_q / ne_mq for every column, not only for
+        those with an event (8 bytes per observation and region); what format_plp_indel_quals needs"""
+        _lib.check(self.L.lfq_set_indel_arrays_all_columns(self.h, 1 if on else 0), "lfq_set_indel_arrays_all_columns")
+
     def call_snvs_submit(self, batch, conf):
         """first half of call_snvs: launch the kernels of the batch and return (one batch in flight per context)"""
         t = batch._tracks()

@@ -493,6 +493,10 @@ void lfq_destroy(lfq_ctx *c)
         delete c->plp_sum;
         if (c->ev_sum_t[0]) (void)hipEventDestroy(c->ev_sum_t[0]);
         if (c->ev_sum_t[1]) (void)hipEventDestroy(c->ev_sum_t[1]);
+        if (c->d_pq) (void)hipFree(c->d_pq);
+        if (c->h_pq) (void)hipHostFree(c->h_pq);
+        if (c->ev_pq_t[0]) (void)hipEventDestroy(c->ev_pq_t[0]);
+        if (c->ev_pq_t[1]) (void)hipEventDestroy(c->ev_pq_t[1]);
         if (c->ev_baq_t[0]) (void)hipEventDestroy(c->ev_baq_t[0]);
         if (c->ev_baq_t[1]) (void)hipEventDestroy(c->ev_baq_t[1]);
         if (c->ev_idq_t[0]) (void)hipEventDestroy(c->ev_idq_t[0]);
@@ -934,6 +938,15 @@ int lfq_set_indel_arrays_on_host(lfq_ctx *c, int on)
         return LFQ_ERR_INVALID;
     }
     c->indel_host_arrays = on ? 1 : 0;
+    return LFQ_OK;
+}
+
+int lfq_set_indel_arrays_all_columns(lfq_ctx *c, int on)
+{
+    if (!c) {
+        return LFQ_ERR_INVALID;
+    }
+    c->indel_all_columns = on ? 1 : 0;
     return LFQ_OK;
 }
 

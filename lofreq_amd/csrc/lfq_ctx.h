@@ -384,6 +384,15 @@ struct lfq_ctx {
     struct LfqSummaryOwned *plp_sum;
     hipEvent_t ev_sum_t[2];          /* around the summary kernel (created on first use) */
     lfq_summary_times sum_times;     /* columns, ordered columns and launches of the last call (the ms: from the events, when asked for) */
+    /* lfq_plp_quals_from_tracks: the uploaded slice of host tracks | the kernel's output (grow-only); its pinned copy, handed out */
+    uint8_t *d_pq;
+    int64_t pq_bytes;
+    uint8_t *h_pq;                   /* pinned: nt_off | bq | baq | mq | sq as the kernel wrote them */
+    int64_t h_pq_bytes;
+    lfq_plp_quals plp_quals;         /* the struct handed out */
+    hipEvent_t ev_pq_t[2];           /* around the group kernel (created on first use) */
+    lfq_plp_quals_times pq_times;    /* columns, observations and launches of the last call (the ms: from the events, when asked for) */
+    int indel_all_columns;           /* lfq_set_indel_arrays_all_columns */
     /* BAQ scratch (lfq_baq_batch), kept between calls */
     double *d_baq_scr;
     int32_t *d_baq_expect;

@@ -806,6 +806,142 @@ int lfq_format_plp_summary(char *buf, int buflen, const char *chrom, const lfq_p
     return n < buflen ? n : LFQ_ERR_CAPACITY;
 }
 
+/* ---- the quality lines of plp_summary (lofreq_call.c:460-598) --------------------------------------------------------------------
+ * Lines grow with the depth: the text is produced by one routine that counts, and writes where there is room. */
+namespace {
+struct PlpText {
+    char *buf;
+    int64_t cap, len;           /* cap: bytes that may be written (0 with a NULL buffer); len: bytes the text has so far */
+    void put(const char *s, size_t n)
+    {
+        if (buf && len + (int64_t)n <= cap) {
+            memcpy(buf + len, s, n);
+        }
+        len += (int64_t)n;
+    }
+    void str(const char *s) { put(s, strlen(s)); }
+    void num(int v)                                         /* " %d" */
+    {
+        char t[16];
+        const int n = snprintf(t, sizeof(t), " %d", v);
+        put(t, (size_t)n);
+    }
+    int finish()
+    {
+        if (len > INT_MAX) {
+            return LFQ_ERR_CAPACITY;
+        }
+        if (!buf) {
+            return (int)len;                                /* the length query */
+        }
+        if (len > cap) {
+            return LFQ_ERR_CAPACITY;
+        }
+        buf[len] = '\0';
+        return (int)len;
+    }
+};
+}  // namespace
+
+int lfq_format_plp_quals(char *buf, int64_t buflen, const lfq_plp_quals *q, int64_t col, int flag)
+{
+    if (!q || col < q->col_begin || col >= q->col_begin + q->ncols || !q->nt_off || buflen < 0 || (!buf && buflen != 0)) {
+        return LFQ_ERR_INVALID;
+    }
+    const bool use_baq = (flag & LFQ_USE_BAQ) != 0, use_sq = (flag & LFQ_USE_SQ) != 0;
+    if (!q->bq || !q->mq || (use_baq && !q->baq) || (use_sq && !q->sq)) {
+        return LFQ_ERR_INVALID;
+    }
+    PlpText T = {buf, buf ? buflen - 1 : 0, 0};             /* one byte kept for the NUL */
+    if (buf && buflen == 0) {
+        return LFQ_ERR_CAPACITY;
+    }
+    static const char *title[] = {"BQ", "BAQ", "MQ", "SQ"};
+    const int64_t *off = q->nt_off + 5 * (col - q->col_begin);
+    for (int i = 0; i < 5; i++) {
+        if (off[i + 1] == off[i]) {
+            continue;                                       /* :466 */
+        }
+        for (int x = 0; x < (use_sq ? 4 : 3); x++) {
+            char head[16];
+            const int n = snprintf(head, sizeof(head), "  %c\t%s =\t", "ACGTN"[i], title[x]);
+            T.put(head, (size_t)n);
+            for (int64_t j = off[i]; j < off[i + 1]; j++) {
+                int v = -1;
+                if (x == 0) {
+                    v = q->bq[j];
+                } else if (x == 1 && use_baq) {             /* :478 */
+                    v = q->baq[j] == LFQ_Q_MISSING ? -1 : q->baq[j];
+                } else if (x == 2) {
+                    v = q->mq[j];
+                } else if (x == 3) {
+                    v = q->sq[j] == LFQ_Q_MISSING ? -1 : (q->sq[j] == 254 ? 49314 : q->sq[j]);
+                }
+                T.num(v);
+            }
+            T.str("\n");
+        }
+    }
+    return T.finish();
+}
+
+int lfq_format_plp_indel_quals(char *buf, int64_t buflen, const lfq_indel_columns *b, int64_t col)
+{
+    if (!b || col < 0 || col >= b->ncols || buflen < 0 || (!buf && buflen != 0)) {
+        return LFQ_ERR_INVALID;
+    }
+    for (int sd = 0; sd < 2; sd++) {
+        const lfq_indel_side &S = b->side[sd];
+        if (!S.ne_off || !S.ne_q || !S.ne_mq || !S.ev_off || !S.key_off || !S.key_chars || !S.rd_off || !S.rd_q || !S.rd_mq
+            || !S.rd_aq || !S.rd_sq || !S.non_fw || !S.non_rv) {
+            return LFQ_ERR_INVALID;                         /* (ne_q / ne_mq NULL: device-only arrays) */
+        }
+        if (S.ne_off[col + 1] == S.ne_off[col] && S.non_fw[col] + S.non_rv[col] > 0) {
+            return LFQ_ERR_INVALID;                         /* lfq_set_indel_arrays_all_columns is off */
+        }
+    }
+    if (buf && buflen == 0) {
+        return LFQ_ERR_CAPACITY;
+    }
+    PlpText T = {buf, buf ? buflen - 1 : 0, 0};
+    for (int sd = 0; sd < 2; sd++) {
+        const lfq_indel_side &S = b->side[sd];
+        const char t = sd == 0 ? '+' : '-';
+        char head[8];
+        snprintf(head, sizeof(head), "  %c", t);
+        T.str(head);
+        T.str("0\tIDQ =\t");
+        for (int64_t i = S.ne_off[col]; i < S.ne_off[col + 1]; i++) {
+            T.num(S.ne_q[i]);
+        }
+        T.str("\n");
+        T.str(head);
+        T.str("0\tMQ =\t");
+        for (int64_t i = S.ne_off[col]; i < S.ne_off[col + 1]; i++) {
+            T.num(S.ne_mq[i]);
+        }
+        T.str("\n");
+        static const char *title[2][4] = {{"IQ", "MQ", "AQ", "SQ"}, {"IDQ", "MQ", "AQ", "SQ"}};
+        for (int64_t e = S.ev_off[col]; e < S.ev_off[col + 1]; e++) {
+            const int16_t *arr[4] = {S.rd_q, S.rd_mq, S.rd_aq, S.rd_sq};
+            for (int x = 0; x < 4; x++) {
+                T.str(head);
+                T.put(S.key_chars + S.key_off[e], (size_t)(S.key_off[e + 1] - S.key_off[e]));
+                T.str("\t");
+                T.str(title[sd][x]);
+                T.str(" =\t");
+                for (int64_t i = S.rd_off[e]; i < S.rd_off[e + 1]; i++) {
+                    const int v = arr[x][i];
+                    T.num(x == 3 && v == 32767 ? 49314 : v);
+                }
+                T.str("\n");
+            }
+        }
+    }
+    T.str("\n");                                            /* :598 */
+    return T.finish();
+}
+
 /* many records at once; returns the number of bytes the full text needs (written if it fits) */
 int64_t lfq_format_vcf(char *buf, int64_t buflen, const char *chrom, const int64_t *pos0_or_null,
                        const lfq_snv_record *recs, int64_t n, const uint8_t *keep_or_null,

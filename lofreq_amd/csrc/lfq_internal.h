@@ -393,6 +393,16 @@ struct LfqSummaryArgs {
     uint8_t *ordered;                     /* [n_cols] 1 where the sums were formed in pileup order */
 };
 int lfq_launch_plp_summary(const LfqSummaryArgs &a, void *stream);
+/* the quality lines of plp_summary (lfq_plp_quals_from_tracks): the bytes of byte-nt tracks grouped by nucleotide per column */
+struct LfqPlpGroupArgs {
+    const uint8_t *nt, *bq, *baq, *mq, *sq;   /* the tracks (baq / sq may be null); observation i lies at [i - in_shift] */
+    const uint64_t *col_off;                  /* [n_cols + 1] the range's entries of the tracks' col_off */
+    int64_t n_cols;
+    uint64_t in_shift;                        /* 0 for resident tracks, col_off[0] for an uploaded slice */
+    uint8_t *o_bq, *o_baq, *o_mq, *o_sq;      /* [col_off[n_cols] - col_off[0]] grouped bytes (o_baq / o_sq null with baq / sq) */
+    int64_t *nt_off;                          /* [5 * n_cols + 1] group offsets, relative to col_off[0] */
+};
+int lfq_launch_plp_group(const LfqPlpGroupArgs &a, void *stream);
 /* the kept reads of a -d cap as the pileup kernels take them (read_idx / pos / pmax_end of LfqPileupArgs): keep[r] != 0 for a
  * kept read; kept_idx / kept_pos / kept_pmax get one entry per kept read.  scratch: lfq_keep_compact_scratch(n) bytes, whose
  * first n int32 the caller fills with the reads' exclusive ends (computed on the host with the keep decision) */

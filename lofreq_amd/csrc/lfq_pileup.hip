@@ -1453,6 +1453,99 @@ int lfq_launch_plp_summary(const LfqSummaryArgs &a, void *stream)
 }
 
 
+/* ---- the quality lines of plp_summary (lfq_plp_quals_from_tracks; lofreq_call.c:460-489) --------------------------------------
+ * compile_plp_col files every kept base under its nucleotide: base_quals[nt4], baq_quals[nt4], map_quals[nt4], source_quals[nt4]
+ * (plp.c:954-975).  The SNV tracks hold the same bytes in pileup order with the nucleotide in bits 0-2 of nt; this kernel is
+ * the stable partition of every column by that code (A, C, G, T, N; a code above 4 counts as N).  One wavefront per COLUMN, four
+ * columns a workgroup, lanes = observations, 64 a round.  Pass 1: five ballots a round give the group sizes, hence the five
+ * start offsets.  Pass 2: rank = start[code] + seen[code] + popcount(mask[code] & lanes_below); each lane stores its 3 to 4
+ * bytes at rank.  The first round stays in registers between the passes, so a column of at most 64 observations loads nothing
+ * twice.  No atomics, no LDS, no scratch.  A lane's stores are single bytes, in at most five contiguous runs per instruction;
+ * loads are one byte a lane, contiguous over the wavefront.  Bounds: rank < the column's size because the five sizes sum to it. */
+__device__ __forceinline__ uint32_t lfq_group_code(const uint8_t *nt, uint64_t i)
+{
+    const uint32_t code = nt[i] & 7u;
+    return code > 4u ? 4u : code;
+}
+
+__global__ __launch_bounds__(256) void lfq_plp_group_kernel(LfqPlpGroupArgs A)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= A.n_cols) {
+        return;
+    }
+    const uint64_t base = A.col_off[0], b = A.col_off[c], e = A.col_off[c + 1];
+    const uint64_t below = (1ull << lane) - 1ull;
+    /* pass 1: the group sizes */
+    const bool act0 = b + (uint64_t)lane < e;
+    const uint32_t code0 = act0 ? lfq_group_code(A.nt, b + (uint64_t)lane - A.in_shift) : 7u;
+    const uint64_t f0 = __ballot(code0 == 0u), f1 = __ballot(code0 == 1u), f2 = __ballot(code0 == 2u),
+                   f3 = __ballot(code0 == 3u), f4 = __ballot(code0 == 4u);
+    uint32_t n0 = (uint32_t)__popcll(f0), n1 = (uint32_t)__popcll(f1), n2 = (uint32_t)__popcll(f2),
+             n3 = (uint32_t)__popcll(f3), n4 = (uint32_t)__popcll(f4);
+    for (uint64_t r0 = b + 64; r0 < e; r0 += 64) {
+        const uint64_t i = r0 + (uint64_t)lane;
+        const uint32_t code = i < e ? lfq_group_code(A.nt, i - A.in_shift) : 7u;
+        n0 += (uint32_t)__popcll(__ballot(code == 0u));
+        n1 += (uint32_t)__popcll(__ballot(code == 1u));
+        n2 += (uint32_t)__popcll(__ballot(code == 2u));
+        n3 += (uint32_t)__popcll(__ballot(code == 3u));
+        n4 += (uint32_t)__popcll(__ballot(code == 4u));
+    }
+    uint32_t s0 = 0, s1 = n0, s2 = n0 + n1, s3 = n0 + n1 + n2, s4 = n0 + n1 + n2 + n3;     /* where the next of each group goes */
+    {
+        uint32_t v = s0;                            /* lanes 0..4: the group starts; lane 5 of the last column: the end */
+        v = lane == 1 ? s1 : v; v = lane == 2 ? s2 : v; v = lane == 3 ? s3 : v; v = lane == 4 ? s4 : v;
+        v = lane == 5 ? s4 + n4 : v;
+        if (lane < 5 || (lane == 5 && c == A.n_cols - 1)) {
+            A.nt_off[c * 5 + lane] = (int64_t)(b - base) + (int64_t)v;
+        }
+    }
+    /* pass 2: every observation to its rank */
+    const uint64_t out0 = b - base;
+    uint64_t m0 = f0, m1 = f1, m2 = f2, m3 = f3, m4 = f4;
+    uint32_t code = code0;
+    for (uint64_t r0 = b; r0 < e; r0 += 64) {
+        const uint64_t i = r0 + (uint64_t)lane;
+        if (r0 != b) {
+            code = i < e ? lfq_group_code(A.nt, i - A.in_shift) : 7u;
+            m0 = __ballot(code == 0u); m1 = __ballot(code == 1u); m2 = __ballot(code == 2u);
+            m3 = __ballot(code == 3u); m4 = __ballot(code == 4u);
+        }
+        if (code < 5u) {
+            uint64_t m = m0;
+            uint32_t s = s0;
+            m = code == 1u ? m1 : m; s = code == 1u ? s1 : s;
+            m = code == 2u ? m2 : m; s = code == 2u ? s2 : s;
+            m = code == 3u ? m3 : m; s = code == 3u ? s3 : s;
+            m = code == 4u ? m4 : m; s = code == 4u ? s4 : s;
+            const uint64_t src = i - A.in_shift, dst = out0 + s + (uint32_t)__popcll(m & below);
+            A.o_bq[dst] = A.bq[src];
+            A.o_mq[dst] = A.mq[src];
+            if (A.baq) {
+                A.o_baq[dst] = A.baq[src];
+            }
+            if (A.sq) {
+                A.o_sq[dst] = A.sq[src];
+            }
+        }
+        s0 += (uint32_t)__popcll(m0); s1 += (uint32_t)__popcll(m1); s2 += (uint32_t)__popcll(m2);
+        s3 += (uint32_t)__popcll(m3); s4 += (uint32_t)__popcll(m4);
+    }
+}
+
+int lfq_launch_plp_group(const LfqPlpGroupArgs &a, void *stream)
+{
+    if (a.n_cols <= 0) {
+        return LFQ_OK;
+    }
+    const dim3 grid((unsigned)((a.n_cols + 3) / 4)), block(256);
+    hipLaunchKernelGGL(lfq_plp_group_kernel, grid, block, 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
+}
+
+
 /* ---- indel pseudo-columns on the device ----------------------------------------------------------------------
  * One wavefront per tested event: the column's reads without an event of that side (indel quality, MAPQ) followed
  * by the reads of all its events, the tested one's marked as the alt allele and carrying their alignment quality

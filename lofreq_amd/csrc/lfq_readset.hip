@@ -2305,6 +2305,9 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
             for (const Ev &e : evs) {
                 has_ev[(size_t)(e.pos - region_begin)] = 1;
             }
+            if (c->indel_all_columns) {             /* lfq_set_indel_arrays_all_columns: the arrays of every column */
+                std::fill(has_ev.begin(), has_ev.end(), (uint8_t)1);
+            }
             /* two passes over the positions, both split over a few threads: count the covered positions and the
              * non-event reads at event positions per part, then every part fills its slice of the column arrays */
             int64_t part_cov[LFQ_HOST_PARTS + 1] = {0}, part_ne[2][LFQ_HOST_PARTS + 1] = {{0}, {0}};
@@ -2796,6 +2799,173 @@ int lfq_last_summary_times(lfq_ctx *c, lfq_summary_times *t)
         LFQ_TRY_HIP(hipEventSynchronize(c->ev_sum_t[1]));
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, c->ev_sum_t[0], c->ev_sum_t[1]) == hipSuccess) {
+            t->kernel_ms = ms;
+        }
+    }
+    return LFQ_OK;
+}
+
+/* ---- the nucleotide lines of plp_summary (lofreq_call.c:460-489): the tracks' bytes grouped per column --------------------------
+ * One buffer on the device, [uploaded slice of host tracks |] nt_off | bq | baq | mq | sq, whose output part one copy brings into
+ * pinned memory, where the struct points at it. */
+int lfq_plp_quals_from_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_device, int64_t col_begin, int64_t col_end,
+                              const lfq_plp_quals **out)
+{
+    if (!c || !tr || !out) {
+        return LFQ_ERR_INVALID;
+    }
+    if (col_begin < 0 || col_end < col_begin || col_end > tr->ncols || (tr->flags & LFQ_TRACKS_NT_PACKED)) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t ncols = col_end - col_begin;
+    if (ncols > 0 && (!tr->col_off || !tr->nt || !tr->bq || !tr->mq)) {
+        return LFQ_ERR_INVALID;
+    }
+    lfq_plp_quals &Q = c->plp_quals;
+    memset(&Q, 0, sizeof(Q));
+    memset(&c->pq_times, 0, sizeof(c->pq_times));
+    Q.ncols = ncols;
+    Q.col_begin = col_begin;
+    c->pq_times.n_cols = ncols;
+    *out = &Q;
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto pinned = [c](int64_t need) {
+        if (need > c->h_pq_bytes) {
+            if (c->h_pq) (void)hipHostFree(c->h_pq);
+            c->h_pq = nullptr;
+            c->h_pq_bytes = 0;
+            if (hipHostMalloc((void **)&c->h_pq, (size_t)need, hipHostMallocDefault) != hipSuccess) {
+                return LFQ_ERR_NOMEM;
+            }
+            c->h_pq_bytes = need;
+        }
+        return LFQ_OK;
+    };
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    hipStream_t ps = c->stream;
+    /* the range's first and last offset: how large the output is */
+    uint64_t ends[2] = {0, 0};
+    if (ncols > 0 && tracks_on_device) {
+        LfqPin<uint64_t> e2(c, 2);
+        LFQ_PIN_OK(e2);
+        int rc = LFQ_OK;
+        if (hipMemcpyAsync(e2.data(), tr->col_off + col_begin, 8, hipMemcpyDeviceToHost, ps) != hipSuccess
+            || hipMemcpyAsync(e2.data() + 1, tr->col_off + col_end, 8, hipMemcpyDeviceToHost, ps) != hipSuccess) {
+            rc = LFQ_ERR_HIP;
+        }
+        if (hipStreamSynchronize(ps) != hipSuccess) {
+            rc = LFQ_ERR_HIP;
+        }
+        LFQ_TRY(rc);
+        ends[0] = e2[0];
+        ends[1] = e2[1];
+    } else if (ncols > 0) {
+        ends[0] = tr->col_off[col_begin];
+        ends[1] = tr->col_off[col_end];
+    }
+    if (ends[1] < ends[0]) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n_obs = (int64_t)(ends[1] - ends[0]);
+    c->pq_times.n_obs = n_obs;
+    const int64_t n_off = 5 * ncols + 1;
+    const bool has_baq = tr->baq != nullptr, has_sq = tr->sq != nullptr;
+    /* output: nt_off | bq | baq | mq | sq */
+    const int64_t r_off = 0, r_bq = r_off + al(n_off * 8), r_baq = r_bq + al(n_obs), r_mq = r_baq + (has_baq ? al(n_obs) : 0),
+                  r_sq = r_mq + al(n_obs), r_total = r_sq + (has_sq ? al(n_obs) : 0);
+    LFQ_TRY(pinned(r_total));
+    uint8_t *h = c->h_pq;
+    int64_t *h_off = (int64_t *)(h + r_off);
+    Q.nt_off = h_off;
+    Q.bq = h + r_bq;
+    Q.baq = has_baq ? h + r_baq : nullptr;
+    Q.mq = h + r_mq;
+    Q.sq = has_sq ? h + r_sq : nullptr;
+    if (n_obs == 0) {                       /* an empty range, or one without observations: nothing to launch */
+        for (int64_t i = 0; i < n_off; i++) {
+            h_off[i] = 0;
+        }
+        return LFQ_OK;
+    }
+    /* host tracks: col_off | nt | bq | baq | mq | sq of the range go up in front of the output */
+    const int64_t u_off = 0, u_nt = u_off + al((ncols + 1) * 8), u_bq = u_nt + al(n_obs), u_baq = u_bq + al(n_obs),
+                  u_mq = u_baq + (has_baq ? al(n_obs) : 0), u_sq = u_mq + al(n_obs), u_total = u_sq + (has_sq ? al(n_obs) : 0);
+    const int64_t o_out = tracks_on_device ? 0 : u_total;
+    LFQ_TRY(grow(&c->d_pq, &c->pq_bytes, o_out + r_total));
+    uint8_t *d = c->d_pq;
+    for (int i = 0; i < 2; i++) {
+        if (!c->ev_pq_t[i]) {
+            LFQ_TRY_HIP(hipEventCreate(&c->ev_pq_t[i]));
+        }
+    }
+    LfqPlpGroupArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_cols = ncols;
+    int rc = LFQ_OK;
+    if (tracks_on_device) {
+        A.nt = tr->nt;
+        A.bq = tr->bq;
+        A.baq = tr->baq;
+        A.mq = tr->mq;
+        A.sq = tr->sq;
+        A.col_off = tr->col_off + col_begin;
+        A.in_shift = 0;
+    } else {
+        auto up = [&](int64_t off, const void *src, int64_t bytes) {
+            if (rc == LFQ_OK && src && bytes > 0
+                && hipMemcpyAsync(d + off, src, (size_t)bytes, hipMemcpyHostToDevice, ps) != hipSuccess) {
+                rc = LFQ_ERR_HIP;
+            }
+        };
+        up(u_off, tr->col_off + col_begin, (ncols + 1) * 8);
+        up(u_nt, tr->nt + ends[0], n_obs);
+        up(u_bq, tr->bq + ends[0], n_obs);
+        up(u_baq, has_baq ? tr->baq + ends[0] : nullptr, n_obs);
+        up(u_mq, tr->mq + ends[0], n_obs);
+        up(u_sq, has_sq ? tr->sq + ends[0] : nullptr, n_obs);
+        A.nt = d + u_nt;
+        A.bq = d + u_bq;
+        A.baq = has_baq ? d + u_baq : nullptr;
+        A.mq = d + u_mq;
+        A.sq = has_sq ? d + u_sq : nullptr;
+        A.col_off = (const uint64_t *)(d + u_off);
+        A.in_shift = ends[0];
+    }
+    A.nt_off = (int64_t *)(d + o_out + r_off);
+    A.o_bq = d + o_out + r_bq;
+    A.o_baq = has_baq ? d + o_out + r_baq : nullptr;
+    A.o_mq = d + o_out + r_mq;
+    A.o_sq = has_sq ? d + o_out + r_sq : nullptr;
+    if (rc == LFQ_OK && hipEventRecord(c->ev_pq_t[0], ps) != hipSuccess) {
+        rc = LFQ_ERR_HIP;
+    }
+    if (rc == LFQ_OK) {
+        rc = lfq_launch_plp_group(A, ps);
+    }
+    if (rc == LFQ_OK && (hipEventRecord(c->ev_pq_t[1], ps) != hipSuccess
+                         || hipMemcpyAsync(h, d + o_out, (size_t)r_total, hipMemcpyDeviceToHost, ps) != hipSuccess)) {
+        rc = LFQ_ERR_HIP;
+    }
+    if (rc == LFQ_OK) {
+        c->pq_times.n_launches = 1;
+    }
+    if (hipStreamSynchronize(ps) != hipSuccess) {       /* on every path: the caller's host tracks may still be a copy's source */
+        rc = LFQ_ERR_HIP;
+    }
+    return rc;
+}
+
+int lfq_last_plp_quals_times(lfq_ctx *c, lfq_plp_quals_times *t)
+{
+    if (!c || !t) {
+        return LFQ_ERR_INVALID;
+    }
+    *t = c->pq_times;
+    if (t->n_launches > 0) {
+        LFQ_TRY_HIP(hipSetDevice(c->device));
+        LFQ_TRY_HIP(hipEventSynchronize(c->ev_pq_t[1]));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c->ev_pq_t[0], c->ev_pq_t[1]) == hipSuccess) {
             t->kernel_ms = ms;
         }
     }

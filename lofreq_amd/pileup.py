@@ -260,6 +260,104 @@ def format_plp_summary(chrom, summary):
     return lines
 
 
+class PlpQuals:
+    """The grouped quality bytes of `lfq_plp_quals_from_tracks` for the columns [col_begin, col_begin + ncols) of SNV tracks
+    (copied): nt_off ([5 * ncols + 1]; group (column i, nucleotide k of A, C, G, T, N) = [nt_off[5i + k], nt_off[5i + k + 1])),
+    bq, mq and, where the tracks have them, baq and sq (else None), in the tracks' encoding"""
+
+    def __init__(self, ptr=None):
+        self.ncols, self.col_begin = 0, 0
+        self.nt_off = np.zeros(1, np.int64)
+        self.bq = self.mq = np.zeros(0, np.uint8)
+        self.baq = self.sq = None
+        if ptr is None:
+            return
+        cs = ptr.contents
+        self.ncols, self.col_begin = int(cs.ncols), int(cs.col_begin)
+        self.nt_off = np.frombuffer(C.string_at(cs.nt_off, (5 * self.ncols + 1) * 8), dtype=np.int64).copy()
+        n = int(self.nt_off[-1])
+
+        def arr(p):
+            if not p:
+                return None
+            return np.frombuffer(C.string_at(p, n), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+
+        self.bq, self.baq, self.mq, self.sq = arr(cs.bq), arr(cs.baq), arr(cs.mq), arr(cs.sq)
+
+    def _as_c(self):
+        """an lfq_plp_quals over this object's arrays (kept alive by the returned tuple)"""
+        cs = _lib.PlpQualsC()
+        cs.ncols, cs.col_begin = self.ncols, self.col_begin
+        keep = []
+        for name in ("nt_off", "bq", "baq", "mq", "sq"):
+            a = getattr(self, name)
+            if a is not None:
+                a = np.ascontiguousarray(a, np.int64 if name == "nt_off" else np.uint8)
+                if len(a) == 0:
+                    a = np.zeros(1, a.dtype)            # (an empty group list is still "present")
+                keep.append(a)
+                setattr(cs, name, a.ctypes.data)
+        return cs, keep
+
+
+def plp_quals(caller, tracks, col_begin=0, col_end=None):
+    """`lfq_plp_quals_from_tracks`: the bq / baq / mq / sq bytes of the columns [col_begin, col_end) of SNV tracks grouped by
+    nucleotide.  tracks: DeviceTracks with byte nt (SnvCaller.set_pileup_nt_packed(False), or those of pileup_sites), or a host
+    PileupBatch / anything with _tracks() and on_device.  -> PlpQuals"""
+    t = tracks._tracks()
+    if col_end is None:
+        col_end = int(t.ncols)
+    out = C.POINTER(_lib.PlpQualsC)()
+    _lib.check(_lib.load().lfq_plp_quals_from_tracks(caller.h, C.byref(t), 1 if tracks.on_device else 0, int(col_begin),
+                                                     int(col_end), C.byref(out)), "lfq_plp_quals_from_tracks")
+    return PlpQuals(out)
+
+
+def last_plp_quals_times(caller):
+    """lfq_last_plp_quals_times of the caller's context -> _lib.PlpQualsTimes"""
+    t = _lib.PlpQualsTimes()
+    _lib.check(_lib.load().lfq_last_plp_quals_times(caller.h, C.byref(t)), "lfq_last_plp_quals_times")
+    return t
+
+
+def _format_grown(call, what):
+    """a formatter whose text grows with the depth: ask for the length, then write"""
+    n = call(None, 0)
+    _lib.check(min(n, 0), what)
+    buf = C.create_string_buffer(n + 1)
+    m = call(buf, n + 1)
+    _lib.check(min(m, 0), what)
+    return buf.raw[:m].decode()
+
+
+def format_plp_quals(quals, flag, cols=None):
+    """`lfq_format_plp_quals` (lofreq_call.c:460-489): the nucleotide quality lines of the columns `cols` (indices of the
+    tracks; default: every column of the PlpQuals) -> list of strings, one per column ('' for a column without a kept base).
+    flag: LFQ_USE_BAQ / LFQ_USE_SQ decide the BAQ values and the SQ line as varcall_conf_t.flag does"""
+    L = _lib.load()
+    cs, _keep = quals._as_c()
+    if cols is None:
+        cols = range(quals.col_begin, quals.col_begin + quals.ncols)
+    return [_format_grown(lambda b, n, col=col: L.lfq_format_plp_quals(b, n, C.byref(cs), int(col), int(flag)),
+                          "lfq_format_plp_quals") for col in cols]
+
+
+def format_plp_indel_quals(indel_cols, cols=None):
+    """`lfq_format_plp_indel_quals` (lofreq_call.c:491-598): the indel quality lines and the closing empty line of the columns
+    `cols` (default: all) of an IndelColumns made with SnvCaller.set_indel_arrays_all_columns(True) -> list of strings"""
+    L = _lib.load()
+    cs = indel_cols.c_struct()
+    for sd in range(2):
+        S = indel_cols.sides[sd]
+        if len(S["ne_q"]) < int(S["ne_off"][-1]) or len(S["ne_mq"]) < int(S["ne_off"][-1]):
+            cs.side[sd].ne_q = None                     # device-only arrays (set_indel_arrays_on_host(False))
+            cs.side[sd].ne_mq = None
+    if cols is None:
+        cols = range(indel_cols.ncols)
+    return [_format_grown(lambda b, n, col=col: L.lfq_format_plp_indel_quals(b, n, C.byref(cs), int(col)),
+                          "lfq_format_plp_indel_quals") for col in cols]
+
+
 class ReadSet:
     """The reads of one contig region resident on the device (`lfq_readset`): upload once, then BAQ / IDAQ, source
     quality, both pileups and the calls without the per-base arrays leaving HBM.
@@ -481,6 +579,31 @@ class ReadSet:
                                                       int(min_plp_idq), C.byref(out)), "lfq_readset_plp_summary")
         self.caller._indel_gen = getattr(self.caller, "_indel_gen", 0) + 1
         return PlpSummary(out)
+
+    def plpsummary_text(self, chrom, begin, end, flag, min_plp_bq=3, min_plp_idq=0, max_depth=None):
+        """The text of `lofreq plpsummary` for the covered positions of [begin, end): one string per column -- header line
+        (lfq_format_plp_summary), nucleotide quality lines (lfq_plp_quals_from_tracks + lfq_format_plp_quals), indel quality
+        lines and the closing empty line (lfq_format_plp_indel_quals).  flag: LFQ_USE_BAQ / LFQ_USE_SQ as varcall_conf_t.flag.
+        Runs plp_summary, pileup_snv with byte nt and pileup_indels with the arrays of every column (the context offers no way
+        to the lfq_indel_columns the summary call left behind, so the indel pileup runs a second time); the caller's nt layout
+        and all-columns switch are set for the duration of the call and put back to their defaults (packed, off)"""
+        c = self.caller
+        s = self.plp_summary(begin, end, min_plp_bq=min_plp_bq, min_plp_idq=min_plp_idq, max_depth=max_depth)
+        heads = format_plp_summary(chrom, s)
+        c.set_pileup_nt_packed(False)
+        c.set_indel_arrays_all_columns(True)
+        try:
+            t = self.pileup_snv(begin, end, min_plp_bq=min_plp_bq, max_depth=max_depth)
+            q = plp_quals(c, t, 0, t.ncols)
+            cols, col_pos = self.pileup_indels(begin, end, min_plp_idq=min_plp_idq, max_depth=max_depth)
+        finally:
+            c.set_pileup_nt_packed(True)
+            c.set_indel_arrays_all_columns(False)
+        if not (t.ncols == cols.ncols == s.ncols and t.col_pos.tolist() == col_pos.tolist() == s.col_pos.tolist()):
+            raise RuntimeError("plpsummary_text: the three pileups disagree on the columns")
+        nts = format_plp_quals(q, flag)
+        ind = format_plp_indel_quals(cols)
+        return [h + a + b for h, a, b in zip(heads, nts, ind)]
 
     def last_summary_times(self):
         """lfq_last_summary_times of the caller's context -> _lib.SummaryTimes"""

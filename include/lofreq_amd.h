@@ -45,6 +45,7 @@ extern "C" {
 /* (10 still: lfq_readset_pileup_sites, lfq_readset_uniq, lfq_last_sites_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_readset_plp_summary, lfq_format_plp_summary, lfq_last_summary_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_plp_quals_from_tracks, lfq_format_plp_quals, lfq_format_plp_indel_quals, lfq_set_indel_arrays_all_columns, lfq_last_plp_quals_times are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_readset_create_from_bam, lfq_readset_fetch_bases, lfq_last_bam_decode_times are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -559,6 +560,57 @@ int lfq_readset_fetch_indelquals(lfq_ctx *ctx, lfq_readset *rs, uint8_t *bi_out,
  * in its stable-sorted order.  The call blocks until *out is complete. */
 int lfq_readset_viterbi(lfq_ctx *ctx, lfq_readset *rs, int def_qual, lfq_readset **out,
                         const lfq_viterbi_result **result_or_null, const int64_t **order_or_null);
+
+/* The read set of BAM records AS THEY LIE IN MEMORY: decoding them -- 4-bit bases -> base codes, qualities, the BI / BD strings
+ * among the aux fields -- is done on the device, and the record bytes cross the link once instead of four unpacked per-base arrays.
+ * *out equals in every observable way the read set lfq_readset_create builds from the arrays a per-base host loop would make:
+ *   base code   0..4 = A C G T N, 5..15 = the other letters, from the nibble through the table {5,0,1,6,2,7,8,9,3,10,11,12,13,14,15,4}
+ *               ("=ACMGRSVTWYHKDBN"; high nibble first);
+ *   qualities   copied as they are, 0xff included;
+ *   BI / BD     from the FIRST aux field with that tag, and only if its type is Z, its string has at least l_qseq bytes before the
+ *               NUL and the NUL lies inside the record; otherwise the read has no such tag (tag_flags bit 0 / 1 clear, bytes '!').
+ *               The read set has a BI (BD) array exactly when at least one read has the tag.  lb / ai / ad / sq tags are not read;
+ *   reverse     flag >> 4 & 1; mapq as given.
+ * Ownership: *out owns host copies of everything its host-side steps read (positions, offsets, CIGARs, mapq, strand, flags, and the
+ * per-base arrays, which come back from the device into pinned memory); after the call it depends neither on recs->data nor on the
+ * descriptor arrays.  Only `ref` is borrowed.  Every step of a read set runs on it, lfq_readset_viterbi included.
+ * The host reads per read only (descriptor checks, prefix sums, the CIGAR words); `data` goes down in one copy -- from the caller's
+ * memory if that is pinned (lfq_host_alloc), through a pinned staging copy otherwise.  The call blocks until *out is complete.
+ * LFQ_ERR_INVALID, before a device is touched: a NULL ctx, recs or out; n_reads < 0; a NULL array with n_reads > 0; decreasing
+ * data_off; l_qseq < 0; a record shorter than l_qname + 4 n_cigar + (l_qseq + 1) / 2 + l_qseq.  LFQ_ERR_INVALID from the decode
+ * (*out = NULL, the context stays usable): an aux field of an unknown type or B subtype (A c C s S i I f Z H B are known), a field
+ * that runs past its record, a Z / H field without a NUL inside the record.  No device read leaves [data_off[r], data_off[r + 1])
+ * by more than the aligned dword around its first / last byte, inside the library's own buffer.
+ * n_reads == 0: LFQ_OK, an empty read set, nothing launched. */
+typedef struct lfq_bam_records {
+    int64_t n_reads;
+    const uint8_t *data;      /* bam1_t.data of every read, concatenated: qname | cigar (uint32 LE) | seq, 4-bit, two bases per byte,
+                                 high nibble first | qual | aux.  = the bytes of an on-disk BAM record from read_name on.  No alignment
+                                 required, neither of data nor of any record. */
+    const int64_t *data_off;  /* [n + 1] */
+    const int32_t *pos;       /* [n] core.pos */
+    const uint16_t *flag;     /* [n] core.flag; only bit 16 (reverse) is read */
+    const uint8_t *mapq;      /* [n] core.qual, already capped by the caller (-M) */
+    const uint16_t *l_qname;  /* [n] core.l_qname: NUL and htslib's padding included */
+    const uint32_t *n_cigar;  /* [n] */
+    const int32_t *l_qseq;    /* [n] */
+    const char *ref;          /* the contig, borrowed: must outlive the read set, as for lfq_readset_create */
+    int64_t ref_len;
+} lfq_bam_records;
+int lfq_readset_create_from_bam(lfq_ctx *ctx, const lfq_bam_records *recs, lfq_readset **out);
+/* copies of a read set's resident per-base inputs, read back from the device: base codes, qualities, BI / BD bytes ('!' throughout
+ * for an array the read set does not have) in the seq_off layout, and per read bit 0 / 1 = has BI / BD.  NULL = not wanted.  Any
+ * read set; LFQ_ERR_INVALID for BI / BD / flags after lfq_readset_indelqual (lfq_readset_fetch_indelquals has those). */
+int lfq_readset_fetch_bases(lfq_ctx *ctx, lfq_readset *rs, uint8_t *seq_out, uint8_t *qual_out, uint8_t *bi_out, uint8_t *bd_out,
+                            uint8_t *tag_flags_out);
+/* the context's last lfq_readset_create_from_bam on the device's clock: the copy of the records (and descriptors) down, the two
+ * kernels (aux pass + base pass), the per-base arrays back into the read set's pinned host copies */
+typedef struct lfq_bam_decode_times {
+    double upload_ms, kernels_ms, download_ms;
+    int64_t n_reads, n_bases, n_data_bytes;
+    int n_launches;
+} lfq_bam_decode_times;
+int lfq_last_bam_decode_times(lfq_ctx *ctx, lfq_bam_decode_times *t);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

@@ -45,6 +45,10 @@ static int rv_reserve(rvec *v, int64_t more)
  * must stay as they are until region k is finished -- which happens while region k + 1 is being filled */
 typedef struct {
     rvec pos, cig_off, cig, seq_off, seq, qual, mapq, rev, bi, bd, flags;
+    /* lfq_region_add_record: the records as they lie in bam1_t.data (pinned: they go down by DMA) and their descriptors; pos,
+     * mapq and flags above are shared with the array road */
+    rvec rec, rec_off, rec_flag, rec_lqname, rec_ncig, rec_lqseq;
+    int fed_by;                     /* 0: no read yet, 1: lfq_region_add_read, 2: lfq_region_add_record */
     int64_t n, nb;
     int any_bi, any_bd;
     char *target;
@@ -105,11 +109,18 @@ static void buf_init(reg_buf *b)
      * 2 M-read region, in front of everything else on the upload stream) */
     b->seq.pinned = b->qual.pinned = b->bi.pinned = b->bd.pinned = 1;
     b->pos.pinned = b->cig_off.pinned = b->cig.pinned = b->seq_off.pinned = b->mapq.pinned = b->rev.pinned = b->flags.pinned = 1;
+    b->rec.elt = 1;
+    b->rec.pinned = 1;
+    b->rec_off.elt = sizeof(int64_t);
+    b->rec_flag.elt = b->rec_lqname.elt = sizeof(uint16_t);
+    b->rec_ncig.elt = sizeof(uint32_t);
+    b->rec_lqseq.elt = sizeof(int32_t);
 }
 
 static void buf_free(reg_buf *b)
 {
-    rvec *all[] = {&b->pos, &b->cig_off, &b->cig, &b->seq_off, &b->seq, &b->qual, &b->mapq, &b->rev, &b->bi, &b->bd, &b->flags};
+    rvec *all[] = {&b->pos, &b->cig_off, &b->cig, &b->seq_off, &b->seq, &b->qual, &b->mapq, &b->rev, &b->bi, &b->bd, &b->flags,
+                   &b->rec, &b->rec_off, &b->rec_flag, &b->rec_lqname, &b->rec_ncig, &b->rec_lqseq};
     size_t i;
     for (i = 0; i < sizeof(all) / sizeof(all[0]); i++) {
         if (all[i]->pinned) {
@@ -209,6 +220,8 @@ int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, in
     }
     b->pos.n = b->cig.n = b->seq.n = b->qual.n = b->mapq.n = b->rev.n = b->bi.n = b->bd.n = b->flags.n = 0;
     b->cig_off.n = b->seq_off.n = 0;
+    b->rec.n = b->rec_off.n = b->rec_flag.n = b->rec_lqname.n = b->rec_ncig.n = b->rec_lqseq.n = 0;
+    b->fed_by = 0;
     b->n = b->nb = 0;
     b->any_bi = b->any_bd = 0;
     free(b->target);
@@ -254,6 +267,10 @@ int lfq_region_add_read(lfq_region *r, int32_t pos, int flag, int mapq, int n_ci
         return 0;                               /* nothing the pileup could place */
     }
     b = &r->buf[r->cur];
+    if (b->fed_by == 2) {
+        return LFQ_ERR_INVALID;                 /* a region is fed by one of the two functions only */
+    }
+    b->fed_by = 1;
     if (rv_reserve(&b->pos, 1) || rv_reserve(&b->cig_off, 1) || rv_reserve(&b->seq_off, 1) || rv_reserve(&b->cig, n_cigar)
         || rv_reserve(&b->seq, l_qseq + 16) || rv_reserve(&b->qual, l_qseq + 16) || rv_reserve(&b->bi, l_qseq + 16)
         || rv_reserve(&b->bd, l_qseq + 16) || rv_reserve(&b->mapq, 1) || rv_reserve(&b->rev, 1) || rv_reserve(&b->flags, 1)) {
@@ -294,6 +311,87 @@ int lfq_region_add_read(lfq_region *r, int32_t pos, int flag, int mapq, int n_ci
     return 1;
 }
 
+int lfq_region_add_record(lfq_region *r, int32_t pos, int flag, int mapq, int l_qname, int n_cigar, int l_qseq,
+                          const uint8_t *data, int l_data)
+{
+    reg_buf *b;
+    if (!r || !r->open || l_qname < 0 || n_cigar < 0 || l_qseq < 0 || l_data < 0 || (l_data > 0 && !data)
+        || (int64_t)l_data < (int64_t)l_qname + 4 * (int64_t)n_cigar + ((int64_t)l_qseq + 1) / 2 + l_qseq) {
+        return LFQ_ERR_INVALID;
+    }
+    /* plp.c:706-720 */
+    if (mapq > r->o.max_mq) {
+        mapq = r->o.max_mq;
+    } else if (mapq < r->o.min_mq) {
+        return 0;
+    } else if (r->o.no_orphan && (flag & 1) && !(flag & 2)) {      /* BAM_FPAIRED without BAM_FPROPER_PAIR */
+        return 0;
+    }
+    if (n_cigar == 0 || l_qseq == 0) {
+        return 0;                               /* nothing the pileup could place */
+    }
+    b = &r->buf[r->cur];
+    if (b->fed_by == 1) {
+        return LFQ_ERR_INVALID;                 /* a region is fed by one of the two functions only */
+    }
+    b->fed_by = 2;
+    if (rv_reserve(&b->pos, 1) || rv_reserve(&b->mapq, 1) || rv_reserve(&b->flags, 1) || rv_reserve(&b->rec, (int64_t)l_data + 16)
+        || rv_reserve(&b->rec_off, 2) || rv_reserve(&b->rec_flag, 1) || rv_reserve(&b->rec_lqname, 1) || rv_reserve(&b->rec_ncig, 1)
+        || rv_reserve(&b->rec_lqseq, 1)) {
+        return LFQ_ERR_NOMEM;
+    }
+    /* the record as it lies: bases, qualities and aux fields are decoded on the device (lfq_readset_create_from_bam) */
+    memcpy((uint8_t *)b->rec.p + b->rec.n, data, (size_t)l_data);
+    ((int64_t *)b->rec_off.p)[b->n] = b->rec.n;
+    b->rec.n += l_data;
+    ((int64_t *)b->rec_off.p)[b->n + 1] = b->rec.n;
+    ((int32_t *)b->pos.p)[b->n] = pos;
+    ((uint8_t *)b->mapq.p)[b->n] = (uint8_t)mapq;
+    ((uint16_t *)b->rec_flag.p)[b->n] = (uint16_t)flag;
+    ((uint16_t *)b->rec_lqname.p)[b->n] = (uint16_t)l_qname;
+    ((uint32_t *)b->rec_ncig.p)[b->n] = (uint32_t)n_cigar;
+    ((int32_t *)b->rec_lqseq.p)[b->n] = l_qseq;
+    b->nb += l_qseq;
+    b->n += 1;
+    b->pos.n = b->mapq.n = b->flags.n = b->rec_flag.n = b->rec_lqname.n = b->rec_ncig.n = b->rec_lqseq.n = b->n;
+    b->rec_off.n = b->n + 1;
+    return 1;
+}
+
+/* the read set of a region fed by lfq_region_add_record: decoded on the device; which tags its reads came with is what the
+ * decode found */
+static int region_readset_from_records(lfq_region *r, reg_buf *b)
+{
+    lfq_bam_records rc_;
+    int64_t i;
+    int rc;
+    memset(&rc_, 0, sizeof(rc_));
+    rc_.n_reads = b->n;
+    rc_.data = (const uint8_t *)b->rec.p;
+    rc_.data_off = (const int64_t *)b->rec_off.p;
+    rc_.pos = (const int32_t *)b->pos.p;
+    rc_.flag = (const uint16_t *)b->rec_flag.p;
+    rc_.mapq = (const uint8_t *)b->mapq.p;
+    rc_.l_qname = (const uint16_t *)b->rec_lqname.p;
+    rc_.n_cigar = (const uint32_t *)b->rec_ncig.p;
+    rc_.l_qseq = (const int32_t *)b->rec_lqseq.p;
+    rc_.ref = b->ref;
+    rc_.ref_len = b->ref_len;
+    rc = lfq_readset_create_from_bam(r->ctx, &rc_, &b->rs);
+    if (rc == LFQ_OK) {
+        rc = lfq_readset_fetch_bases(r->ctx, b->rs, NULL, NULL, NULL, NULL, (uint8_t *)b->flags.p);
+        if (rc != LFQ_OK) {
+            lfq_readset_destroy(b->rs);
+            b->rs = NULL;
+        }
+    }
+    for (i = 0; rc == LFQ_OK && i < b->n; i++) {
+        b->any_bi |= ((const uint8_t *)b->flags.p)[i] & 1;
+        b->any_bd |= (((const uint8_t *)b->flags.p)[i] >> 1) & 1;
+    }
+    return rc;
+}
+
 /* region k: upload (asynchronous) + BAQ / IDAQ kernels (queued) + source quality */
 static int region_start(lfq_region *r, reg_buf *b)
 {
@@ -304,23 +402,27 @@ static int region_start(lfq_region *r, reg_buf *b)
         b->started = 1;
         return LFQ_OK;
     }
-    memset(&rd, 0, sizeof(rd));
-    memset(&tg, 0, sizeof(tg));
-    rd.n_reads = b->n;
-    rd.pos = (const int32_t *)b->pos.p;
-    rd.cigar_off = (const int64_t *)b->cig_off.p;
-    rd.cigar = (const uint32_t *)b->cig.p;
-    rd.seq_off = (const int64_t *)b->seq_off.p;
-    rd.seq = (const uint8_t *)b->seq.p;
-    rd.qual = (const uint8_t *)b->qual.p;
-    rd.mapq = (const uint8_t *)b->mapq.p;
-    rd.reverse = (const uint8_t *)b->rev.p;
-    rd.ref = b->ref;
-    rd.ref_len = b->ref_len;
-    tg.bi = b->any_bi ? (const uint8_t *)b->bi.p : NULL;
-    tg.bd = b->any_bd ? (const uint8_t *)b->bd.p : NULL;
-    tg.tag_flags = (const uint8_t *)b->flags.p;
-    rc = lfq_readset_create(r->ctx, &rd, &tg, &b->rs);
+    if (b->fed_by == 2) {
+        rc = region_readset_from_records(r, b);
+    } else {
+        memset(&rd, 0, sizeof(rd));
+        memset(&tg, 0, sizeof(tg));
+        rd.n_reads = b->n;
+        rd.pos = (const int32_t *)b->pos.p;
+        rd.cigar_off = (const int64_t *)b->cig_off.p;
+        rd.cigar = (const uint32_t *)b->cig.p;
+        rd.seq_off = (const int64_t *)b->seq_off.p;
+        rd.seq = (const uint8_t *)b->seq.p;
+        rd.qual = (const uint8_t *)b->qual.p;
+        rd.mapq = (const uint8_t *)b->mapq.p;
+        rd.reverse = (const uint8_t *)b->rev.p;
+        rd.ref = b->ref;
+        rd.ref_len = b->ref_len;
+        tg.bi = b->any_bi ? (const uint8_t *)b->bi.p : NULL;
+        tg.bd = b->any_bd ? (const uint8_t *)b->bd.p : NULL;
+        tg.tag_flags = (const uint8_t *)b->flags.p;
+        rc = lfq_readset_create(r->ctx, &rd, &tg, &b->rs);
+    }
     if (rc != LFQ_OK) {
         return rc;
     }

@@ -6,8 +6,9 @@
  *     mplp_func's per-read work            plp.c:667-683 (BAQ / IDAQ: bam_prob_realn_core_ext), :727-735 (source quality)
  *     bam_mplp_auto + compile_plp_col      plp.c:1406-1447, 797-1288 (the pileup and the column builder)
  *     call_vars per column                 lofreq_call.c:887-935 (call_indels, call_snvs, report_var)
- * What stays with htslib on the CPU: opening the BAM, the index query, decoding records, the read-level filters of
- * mplp_func (plp.c:608-632: unmapped / secondary / QC-fail / duplicate, BED overlap).  The column callback
+ * What stays with htslib on the CPU: opening the BAM, the index query, decompressing records into bam1_t, the read-level
+ * filters of mplp_func (plp.c:608-632: unmapped / secondary / QC-fail / duplicate, BED overlap).  Unpacking a record's bases,
+ * qualities and BI / BD tags is the device's with lfq_region_add_record, the caller's thread's with lfq_region_add_read.  The column callback
  * (integration/lofreq_amd_shim.c) keeps working for everything that wants plp_col_t; this path is for `lofreq call`
  * itself, whose end-to-end time was the CPU pileup + BAQ once the per-column statistics ran on the GPU.
  *
@@ -92,6 +93,15 @@ int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, in
  * Applies min_mq / max_mq / no_orphan itself (plp.c:706-720).  Returns 1 if the read was taken, 0 if filtered. */
 int lfq_region_add_read(lfq_region *r, int32_t pos, int flag, int mapq, int n_cigar, const uint32_t *cigar, int l_qseq,
                         const uint8_t *seq4, const uint8_t *qual, const char *bi_or_null, const char *bd_or_null);
+/* The same record handed over AS IT LIES in bam1_t: core.pos, core.flag, core.qual, core.l_qname, core.n_cigar, core.l_qseq,
+ * b->data, b->l_data.  No bam_aux_get, no per-base loop on this thread: the record is copied into a pinned staging buffer and
+ * lfq_region_end decodes the region's records on the device (lfq_readset_create_from_bam) -- bases, qualities, and BI / BD from the
+ * first Z field of that tag with at least l_qseq bytes, exactly what lfq_region_add_read makes of bam_aux_get(...) + 1.  Same
+ * filters and return values as lfq_region_add_read; LFQ_ERR_INVALID for a record shorter than its fields.  A region is fed by ONE
+ * of the two functions: mixing them within a region is LFQ_ERR_INVALID.  A malformed aux field fails the region
+ * (LFQ_ERR_INVALID from lfq_region_end).  lfq_region_end blocks for the decode of the region it starts. */
+int lfq_region_add_record(lfq_region *r, int32_t pos, int flag, int mapq, int l_qname, int n_cigar, int l_qseq,
+                          const uint8_t *data, int l_data);
 int lfq_region_end(lfq_region *r);
 /* finishes the last region; *indel_calls_wo_idaq_or_null: report_var's counter (lofreq_call.c:109-111) */
 int lfq_region_close(lfq_region *r, int64_t *indel_calls_wo_idaq_or_null);

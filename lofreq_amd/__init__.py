@@ -15,7 +15,7 @@ from .baq import baq_batch, encode_seq
 from .viterbi import viterbi_batch
 from .indelqual import indelqual_batch
 from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_indel_quals, format_plp_quals,
-                     format_plp_summary, last_plp_quals_times, pileup_indel_columns, pileup_snv_tracks, plp_quals,
+                     format_plp_summary, last_bam_decode_times, last_plp_quals_times, pileup_indel_columns, pileup_snv_tracks, plp_quals,
                      skip_snv_columns)
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
@@ -28,4 +28,5 @@ __all__ = [
     "source_qual_batch", "pileup_indel_columns", "skip_snv_columns", "ReadSet", "binom_cdf", "uniq_mtc",
     "PlpSummary", "format_plp_summary",
     "PlpQuals", "plp_quals", "format_plp_quals", "format_plp_indel_quals", "last_plp_quals_times",
+    "last_bam_decode_times",
 ]

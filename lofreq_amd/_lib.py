@@ -134,6 +134,17 @@ class PileupReads(C.Structure):
                                                                                               ("sq", C.c_void_p)]
 
 
+class BamRecords(C.Structure):
+    """lfq_bam_records"""
+    _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in (
+        "data", "data_off", "pos", "flag", "mapq", "l_qname", "n_cigar", "l_qseq", "ref")] + [("ref_len", C.c_int64)]
+
+
+class BamDecodeTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("kernels_ms", C.c_double), ("download_ms", C.c_double), ("n_reads", C.c_int64),
+                ("n_bases", C.c_int64), ("n_data_bytes", C.c_int64), ("n_launches", C.c_int)]
+
+
 class PileupIndelTags(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("bi", "bd", "ai", "ad", "tag_flags", "sq")]
 
@@ -194,6 +205,7 @@ EXPORTS = [
     "lfq_readset_pileup_snv", "lfq_readset_pileup_indels", "lfq_readset_fetch_tags",
     "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
     "lfq_readset_viterbi",
+    "lfq_readset_create_from_bam", "lfq_readset_fetch_bases", "lfq_last_bam_decode_times",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
     "lfq_plp_quals_from_tracks", "lfq_format_plp_quals", "lfq_set_indel_arrays_all_columns", "lfq_format_plp_indel_quals",
@@ -324,6 +336,9 @@ def load():
     L.lfq_binom_cdf.restype = C.c_double
     L.lfq_binom_cdf.argtypes = [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int)]
     L.lfq_readset_create.argtypes = [vp, C.POINTER(PileupReads), C.POINTER(PileupIndelTags), C.POINTER(vp)]
+    L.lfq_readset_create_from_bam.argtypes = [vp, C.POINTER(BamRecords), C.POINTER(vp)]
+    L.lfq_readset_fetch_bases.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lfq_last_bam_decode_times.argtypes = [vp, C.POINTER(BamDecodeTimes)]
     L.lfq_readset_destroy.argtypes = [vp]
     L.lfq_readset_destroy.restype = None
     L.lfq_readset_baq.argtypes = [vp, vp, C.c_int, C.c_int]

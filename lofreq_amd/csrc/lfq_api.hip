@@ -470,8 +470,8 @@ void lfq_destroy(lfq_ctx *c)
         for (int i = 0; i < 5; i++) {
             if (c->d_tmp[i]) (void)hipFree(c->d_tmp[i]);
         }
-        for (int k = 0; k < 7; k++) {                   /* 4 = LFQ_RSC_PINFL: pinned host memory */
-            if (c->rs_cache[k].p) (void)(k == 4 ? hipHostFree(c->rs_cache[k].p) : hipFree(c->rs_cache[k].p));
+        for (int k = 0; k < 8; k++) {                   /* 4 = LFQ_RSC_PINFL, 7 = LFQ_RSC_PINBASES: pinned host memory */
+            if (c->rs_cache[k].p) (void)(k == 4 || k == 7 ? hipHostFree(c->rs_cache[k].p) : hipFree(c->rs_cache[k].p));
         }
         if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
         if (c->priv_stream) (void)hipStreamDestroy(c->priv_stream);
@@ -508,6 +508,7 @@ void lfq_destroy(lfq_ctx *c)
         if (c->d_baq_itab) (void)hipFree(c->d_baq_itab);
         if (c->d_baq_terms) (void)hipFree(c->d_baq_terms);
         lfq_viterbi_release(c);
+        lfq_bam_release(c);
         if (c->h_tuples) (void)hipHostFree(c->h_tuples);
         if (c->h_nheavy) (void)hipHostFree(c->h_nheavy);
         if (c->ev_heavy) (void)hipEventDestroy(c->ev_heavy);

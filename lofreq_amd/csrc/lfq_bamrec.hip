@@ -1,0 +1,471 @@
+/*
+ * lfq_bamrec.hip -- BAM records decoded on the device (lfq_readset_create_from_bam): the bytes of the records go
+ * down as they lie in bam1_t.data, an aux pass finds BI / BD per read, a base pass writes the per-base arrays of the read set.
+ * The host side that builds the read set around these two launches is in lfq_readset.hip.
+ */
+#include "lfq_ctx.h"
+
+#define LFQ_BAM_AUX_READS 256           /* reads per workgroup of the aux pass: one lane each */
+#define LFQ_BAM_BASE_CHUNKS 256         /* 16-byte chunks of the destination arrays per workgroup of the base pass: one lane each */
+
+struct LfqBamArgs {
+    const uint8_t *data;                /* the records; 4-byte aligned, 16 bytes of slack behind the last record */
+    const int64_t *seq_off;             /* [n + 1] */
+    const int64_t *seq_src;             /* [n] offset in `data` of the read's first 4-bit base byte */
+    const int64_t *rec_end;             /* [n] offset in `data` one past the read's record */
+    int64_t *bi_src, *bd_src;           /* [n] offset of the BI / BD string the read counts as having, or -1 (written by the aux pass) */
+    uint8_t *flags;                     /* [n] bit 0: BI, bit 1: BD */
+    int32_t *err;                       /* [0]: a read has BI, [1]: a read has BD, [2]: a malformed aux field */
+    int64_t *tile_read;                 /* [workgroups of the base pass] the read that holds the first base of the workgroup's tile
+                                           (written by the aux pass) */
+    int64_t n_reads, n_bases;
+    uint8_t *seq, *qual, *bi, *bd;      /* the read set's per-base arrays (16-byte aligned, 16 bytes of slack); bi / bd may be null */
+};
+
+/* the first NUL of [p, end), or a value >= end: four bytes a load, as the aligned dwords that hold them (BI / BD strings are most
+ * of a record, and a lane's byte loads are as many memory transactions as a wavefront's dword loads) */
+__device__ __forceinline__ int64_t bam_find_nul(const uint8_t *d, int64_t p, int64_t end)
+{
+    if (p >= end) {
+        return end;
+    }
+    const uint32_t *w = (const uint32_t *)d;
+    int64_t a = p >> 2;
+    uint32_t x = w[a] | ((1u << ((int)(p & 3) * 8)) - 1u);     /* the bytes in front of p count as non-zero */
+    for (;;) {
+        const uint32_t z = (x - 0x01010101u) & ~x & 0x80808080u;            /* lowest set bit: the first zero byte */
+        if (z) {
+            return a * 4 + ((__ffs((int)z) - 1) >> 3);
+        }
+        a++;
+        if (a * 4 >= end) {
+            return end;
+        }
+        x = w[a];
+    }
+}
+
+/* ---- aux pass: one lane per read walks the aux fields of its record -----------------------------------------------------
+ * Every read stays inside [aux start, rec_end): a field whose header, NUL or payload would lie beyond rec_end ends the walk
+ * and marks the batch malformed. */
+__global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamArgs A)
+{
+    const int64_t r = (int64_t)blockIdx.x * LFQ_BAM_AUX_READS + threadIdx.x;
+    bool bad = false, has_bi = false, has_bd = false;
+    if (r < A.n_reads) {
+        const uint8_t *d = A.data;
+        const int64_t l = A.seq_off[r + 1] - A.seq_off[r];
+        const int64_t end = A.rec_end[r];
+        int64_t p = A.seq_src[r] + (l + 1) / 2 + l;
+        int64_t bi = -1, bd = -1;
+        bool seen_bi = false, seen_bd = false;
+        while (p < end) {
+            if (end - p < 3) {
+                bad = true;
+                break;
+            }
+            const uint8_t t0 = d[p], t1 = d[p + 1], ty = d[p + 2];
+            p += 3;
+            int64_t size = -1, zlen = -1;
+            switch (ty) {
+            case 'A': case 'c': case 'C':
+                size = 1;
+                break;
+            case 's': case 'S':
+                size = 2;
+                break;
+            case 'i': case 'I': case 'f':
+                size = 4;
+                break;
+            case 'Z': case 'H': {
+                const int64_t q = bam_find_nul(d, p, end);
+                if (q < end) {
+                    zlen = q - p;
+                    size = zlen + 1;
+                }
+                break;
+            }
+            case 'B':
+                if (end - p >= 5) {
+                    const uint8_t sub = d[p];
+                    const int64_t cnt = (int64_t)d[p + 1] | ((int64_t)d[p + 2] << 8) | ((int64_t)d[p + 3] << 16) | ((int64_t)d[p + 4] << 24);
+                    const int64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
+                                       : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+                    if (es) {
+                        size = 5 + es * cnt;
+                    }
+                }
+                break;
+            default:
+                break;
+            }
+            if (size < 0 || size > end - p) {
+                bad = true;
+                break;
+            }
+            if (t0 == 'B' && t1 == 'I' && !seen_bi) {       /* the FIRST field of the tag decides (bam_aux_get) */
+                seen_bi = true;
+                if (ty == 'Z' && zlen >= l) {
+                    bi = p;
+                }
+            } else if (t0 == 'B' && t1 == 'D' && !seen_bd) {
+                seen_bd = true;
+                if (ty == 'Z' && zlen >= l) {
+                    bd = p;
+                }
+            }
+            p += size;
+        }
+        if (bad) {
+            bi = bd = -1;
+        }
+        has_bi = bi >= 0;
+        has_bd = bd >= 0;
+        /* the base pass finds the reads of a tile here instead of searching seq_off */
+        const int64_t tile = (int64_t)LFQ_BAM_BASE_CHUNKS * 16, so = A.seq_off[r];
+        for (int64_t t = (so + tile - 1) / tile; t * tile < so + l; t++) {
+            A.tile_read[t] = r;
+        }
+        A.bi_src[r] = bi;
+        A.bd_src[r] = bd;
+        A.flags[r] = (uint8_t)((has_bi ? 1 : 0) | (has_bd ? 2 : 0));
+    }
+    const bool any_bi = __any(has_bi), any_bd = __any(has_bd), any_bad = __any(bad);
+    if ((threadIdx.x & 63) == 0) {
+        if (any_bi) atomicOr(&A.err[0], 1);
+        if (any_bd) atomicOr(&A.err[1], 1);
+        if (any_bad) atomicOr(&A.err[2], 1);
+    }
+}
+
+/* ---- base pass: output-major, one lane per 16 bytes of the destination arrays -----------------------------------------------
+ * 16 bytes in two registers pairs; byte k of the chunk is byte k of the value */
+struct LfqB16 {
+    uint64_t lo, hi;
+};
+
+__device__ __forceinline__ LfqB16 b16_shl_bytes(LfqB16 v, int nbytes)       /* 0 .. 15 */
+{
+    const int s = nbytes * 8;
+    LfqB16 o;
+    if (s == 0) {
+        o = v;
+    } else if (s >= 64) {
+        o.lo = 0;
+        o.hi = v.lo << (s - 64);
+    } else {
+        o.lo = v.lo << s;
+        o.hi = (v.hi << s) | (v.lo >> (64 - s));
+    }
+    return o;
+}
+
+__device__ __forceinline__ LfqB16 b16_mask(int cnt)                         /* the first cnt (1 .. 16) bytes */
+{
+    LfqB16 m;
+    m.lo = cnt >= 8 ? ~0ull : ((1ull << (cnt * 8)) - 1);
+    m.hi = cnt >= 16 ? ~0ull : cnt > 8 ? ((1ull << ((cnt - 8) * 8)) - 1) : 0ull;
+    return m;
+}
+
+/* cnt (1 .. 16) bytes from byte offset s of the records, read as the aligned dwords that hold them -- at most 3 bytes before
+ * the first and 3 behind the last one, which the buffer's alignment and slack cover; the bytes behind cnt are 0 */
+__device__ __forceinline__ LfqB16 b16_fetch(const uint8_t *data, int64_t s, int cnt)
+{
+    const uint32_t *w32 = (const uint32_t *)data + (s >> 2);
+    const int sh = (int)(s & 3) * 8;
+    const int nd = ((int)(s & 3) + cnt + 3) >> 2;                           /* 1 .. 5 */
+    uint32_t w[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        w[i] = i < nd ? w32[i] : 0u;
+    }
+    uint32_t o[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        o[i] = (uint32_t)((((uint64_t)w[i + 1] << 32) | w[i]) >> sh);
+    }
+    const LfqB16 m = b16_mask(cnt);
+    LfqB16 v;
+    v.lo = (o[0] | ((uint64_t)o[1] << 32)) & m.lo;
+    v.hi = (o[2] | ((uint64_t)o[3] << 32)) & m.hi;
+    return v;
+}
+
+/* cnt (1 .. 16) base codes of a read from its base i0 on.  The 4-bit BAM base "=ACMGRSVTWYHKDBN" -> the library's code: 0..3 =
+ * A, C, G, T, 4 = N, 5..15 = the other letters in the order "=MRSVWYHKDB" (include/lofreq_amd.h); the table is a register pair */
+__device__ __forceinline__ LfqB16 b16_bases(const uint8_t *data, int64_t seq_src, int64_t i0, int cnt)
+{
+    const uint64_t T0 = 0x0908070206010005ull, T1 = 0x040f0e0d0c0b0a03ull;
+    const int odd = (int)(i0 & 1);
+    LfqB16 v = b16_fetch(data, seq_src + (i0 >> 1), (odd + cnt + 1) >> 1);  /* at most 9 bytes */
+    /* high nibble first -> nibble k at bit 4 k, then the first base to bit 0 */
+    v.lo = ((v.lo & 0x0f0f0f0f0f0f0f0full) << 4) | ((v.lo >> 4) & 0x0f0f0f0f0f0f0f0full);
+    v.hi = ((v.hi & 0x0f0f0f0f0f0f0f0full) << 4) | ((v.hi >> 4) & 0x0f0f0f0f0f0f0f0full);
+    const uint64_t nib = odd ? (v.lo >> 4) | (v.hi << 60) : v.lo;
+    LfqB16 o;
+    o.lo = o.hi = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t a = (uint32_t)(nib >> (4 * j)) & 0xf, b = (uint32_t)(nib >> (4 * (j + 8))) & 0xf;
+        o.lo |= (((a & 8) ? T1 : T0) >> ((a & 7) * 8) & 0xff) << (8 * j);
+        o.hi |= (((b & 8) ? T1 : T0) >> ((b & 7) * 8) & 0xff) << (8 * j);
+    }
+    const LfqB16 m = b16_mask(cnt);
+    o.lo &= m.lo;
+    o.hi &= m.hi;
+    return o;
+}
+
+__device__ __forceinline__ void b16_store(uint8_t *dst, LfqB16 v)
+{
+    *(uint4 *)dst = make_uint4((uint32_t)v.lo, (uint32_t)(v.lo >> 32), (uint32_t)v.hi, (uint32_t)(v.hi >> 32));
+}
+
+/* the first read r of [lo, hi] with seq_off[r + 1] > b: the read that holds base b (reads without bases are stepped over) */
+__device__ __forceinline__ int64_t bam_read_of_base(const int64_t *seq_off, int64_t lo, int64_t hi, int64_t b)
+{
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (seq_off[mid + 1] > b) {
+            hi = mid;
+        } else {
+            lo = mid + 1;
+        }
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(LFQ_BAM_BASE_CHUNKS) void lfq_bam_bases_kernel(LfqBamArgs A)
+{
+    /* the reads of the workgroup's 4096 bases: from the first read of this tile to the first read of the next one (the aux pass
+     * wrote both down); a lane looks for its chunk's first read among those few -- 27 reads of 150 bases -- and walks on */
+    const int64_t tile0 = (int64_t)blockIdx.x * LFQ_BAM_BASE_CHUNKS * 16;
+    const int64_t b0 = tile0 + (int64_t)threadIdx.x * 16;
+    if (b0 >= A.n_bases) {
+        return;
+    }
+    const int64_t r_lo = A.tile_read[blockIdx.x], r_hi = blockIdx.x + 1 < gridDim.x ? A.tile_read[blockIdx.x + 1] : A.n_reads - 1;
+    const int total = (int)min((int64_t)16, A.n_bases - b0);
+    int64_t r = bam_read_of_base(A.seq_off, r_lo, r_hi, b0);
+    LfqB16 vs, vq, vi, vd;
+    vs.lo = vs.hi = vq.lo = vq.hi = vi.lo = vi.hi = vd.lo = vd.hi = 0;
+    int j = 0;
+    while (j < total) {                 /* one round per read the chunk touches: one for 9 chunks in 10 of 150-base reads */
+        const int64_t b = b0 + j;
+        while (A.seq_off[r + 1] <= b) {
+            r++;
+        }
+        const int64_t so = A.seq_off[r], e = A.seq_off[r + 1], i0 = b - so, l = e - so;
+        const int cnt = (int)min(e - b, (int64_t)(total - j));
+        const int64_t src = A.seq_src[r];
+        const LfqB16 ps = b16_shl_bytes(b16_bases(A.data, src, i0, cnt), j);
+        const LfqB16 pq = b16_shl_bytes(b16_fetch(A.data, src + (l + 1) / 2 + i0, cnt), j);
+        vs.lo |= ps.lo; vs.hi |= ps.hi;
+        vq.lo |= pq.lo; vq.hi |= pq.hi;
+        if (A.bi || A.bd) {
+            LfqB16 none = b16_mask(cnt);                    /* a read without the tag: '!' */
+            none.lo &= 0x2121212121212121ull;
+            none.hi &= 0x2121212121212121ull;
+            if (A.bi) {
+                const int64_t s = A.bi_src[r];
+                const LfqB16 pi = b16_shl_bytes(s >= 0 ? b16_fetch(A.data, s + i0, cnt) : none, j);
+                vi.lo |= pi.lo; vi.hi |= pi.hi;
+            }
+            if (A.bd) {
+                const int64_t s = A.bd_src[r];
+                const LfqB16 pd = b16_shl_bytes(s >= 0 ? b16_fetch(A.data, s + i0, cnt) : none, j);
+                vd.lo |= pd.lo; vd.hi |= pd.hi;
+            }
+        }
+        j += cnt;
+    }
+    b16_store(A.seq + b0, vs);
+    b16_store(A.qual + b0, vq);
+    if (A.bi) b16_store(A.bi + b0, vi);
+    if (A.bd) b16_store(A.bd + b0, vd);
+}
+
+/* ---- host side of the two launches ---------------------------------------------------------------------------------------- */
+struct LfqBamState {
+    uint8_t *d_buf;                     /* records | descriptors | what the aux pass writes (grow-only) */
+    int64_t d_bytes;
+    uint8_t *h_stage;                   /* pinned staging of records that come in pageable memory (grow-only) */
+    int64_t h_bytes;
+    hipEvent_t ev[8];                   /* around the upload, the aux pass, the base pass, the copies back */
+    LfqBamArgs args;                    /* of the decode in flight between lfq_bam_aux and lfq_bam_bases */
+    lfq_bam_decode_times times;
+};
+
+static LfqBamState *bam_state(lfq_ctx *c)
+{
+    if (!c->bam) {
+        c->bam = new LfqBamState();
+        memset(c->bam, 0, sizeof(*c->bam));
+    }
+    return c->bam;
+}
+
+void lfq_bam_release(lfq_ctx *c)
+{
+    if (c->bam) {
+        if (c->bam->d_buf) (void)hipFree(c->bam->d_buf);
+        if (c->bam->h_stage) (void)hipHostFree(c->bam->h_stage);
+        for (hipEvent_t e : c->bam->ev) {
+            if (e) (void)hipEventDestroy(e);
+        }
+        delete c->bam;
+        c->bam = nullptr;
+    }
+}
+
+void lfq_bam_times_reset(lfq_ctx *c, int64_t n_reads, int64_t n_bases, int64_t n_data_bytes)
+{
+    LfqBamState *S = bam_state(c);
+    memset(&S->times, 0, sizeof(S->times));
+    S->times.n_reads = n_reads;
+    S->times.n_bases = n_bases;
+    S->times.n_data_bytes = n_data_bytes;
+}
+
+static float bam_ms(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+}
+
+/* records down, aux pass, its verdict back: flags_out[n], *any_bi / *any_bd; LFQ_ERR_INVALID for a malformed aux field.
+ * data[0 .. data_bytes) are the records, first_shift (0 .. 15) bytes of room are left in front of them on the device so that a
+ * record keeps the alignment it has in the caller's buffer; desc = seq_off[n + 1] | seq_src[n] | rec_end[n], the last two as
+ * offsets from data - first_shift.  Blocks. */
+int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_shift, bool data_pinned, const int64_t *desc,
+                int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi, int *any_bd)
+{
+    LfqBamState *S = bam_state(c);
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    for (hipEvent_t &e : S->ev) {
+        if (!e) {
+            LFQ_TRY_HIP(hipEventCreate(&e));
+        }
+    }
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t o_desc = al(first_shift + data_bytes + 16), o_bi = o_desc + al((3 * n + 1) * 8), o_bd = o_bi + al(n * 8),
+                  o_err = o_bd + al(n * 8), o_fl = o_err + 256, o_tile = o_fl + al(n),
+                  n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), total = o_tile + al(n_tiles * 8);
+    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
+    if (!data_pinned) {
+        if (data_bytes > S->h_bytes) {
+            if (S->h_stage) (void)hipHostFree(S->h_stage);
+            S->h_stage = nullptr;
+            S->h_bytes = 0;
+            const int64_t want = std::max<int64_t>(data_bytes + data_bytes / 4, 1 << 16);
+            if (hipHostMalloc((void **)&S->h_stage, (size_t)want, hipHostMallocDefault) != hipSuccess) {
+                return LFQ_ERR_NOMEM;
+            }
+            S->h_bytes = want;
+        }
+        /* (a few threads: one copies at a fraction of what the link takes) */
+        const unsigned hw = std::max(1u, lfq_cpu_budget() / (unsigned)std::max(lfq_knobs().local_world_size, 1));
+        const int parts = data_bytes >= ((int64_t)32 << 20) ? (int)std::min(8u, hw) : 1;
+        uint8_t *stage = S->h_stage;
+        auto copy_part = [=](int p) {
+            const int64_t a = data_bytes * p / parts, b = data_bytes * (p + 1) / parts;
+            memcpy(stage + a, data + a, (size_t)(b - a));
+        };
+        std::vector<std::thread> th;
+        for (int p = 1; p < parts; p++) {
+            th.emplace_back(copy_part, p);
+        }
+        copy_part(0);
+        for (auto &t : th) {
+            t.join();
+        }
+        data = S->h_stage;
+    }
+    LfqPin<int32_t> verdict(c, 4);
+    LFQ_PIN_OK(verdict);
+    LfqPin<uint8_t> fl(c, (size_t)n);
+    LFQ_PIN_OK(fl);
+    hipStream_t st = c->stream;
+    LFQ_TRY_HIP(hipEventRecord(S->ev[0], st));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + first_shift, data, (size_t)data_bytes, hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_desc, desc, (size_t)(3 * n + 1) * 8, hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemsetAsync(S->d_buf + o_err, 0, 256, st));
+    LFQ_TRY_HIP(hipEventRecord(S->ev[1], st));
+    LfqBamArgs &A = S->args;
+    memset(&A, 0, sizeof(A));
+    A.data = S->d_buf;
+    A.seq_off = (const int64_t *)(S->d_buf + o_desc);
+    A.seq_src = A.seq_off + n + 1;
+    A.rec_end = A.seq_src + n;
+    A.bi_src = (int64_t *)(S->d_buf + o_bi);
+    A.bd_src = (int64_t *)(S->d_buf + o_bd);
+    A.err = (int32_t *)(S->d_buf + o_err);
+    A.flags = S->d_buf + o_fl;
+    A.tile_read = (int64_t *)(S->d_buf + o_tile);
+    A.n_reads = n;
+    A.n_bases = nb;
+    LFQ_TRY_HIP(hipEventRecord(S->ev[2], st));
+    hipLaunchKernelGGL(lfq_bam_aux_kernel, dim3((unsigned)((n + LFQ_BAM_AUX_READS - 1) / LFQ_BAM_AUX_READS)),
+                       dim3(LFQ_BAM_AUX_READS), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY_HIP(hipEventRecord(S->ev[3], st));
+    S->times.n_launches += 1;
+    LFQ_TRY_HIP(hipMemcpyAsync(verdict.data(), A.err, 16, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(fl.data(), A.flags, (size_t)n, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    S->times.upload_ms = bam_ms(S->ev[0], S->ev[1]);
+    S->times.kernels_ms = bam_ms(S->ev[2], S->ev[3]);
+    if (verdict[2]) {
+        return LFQ_ERR_INVALID;
+    }
+    memcpy(flags_out, fl.data(), (size_t)n);
+    *any_bi = verdict[0] != 0;
+    *any_bd = verdict[1] != 0;
+    return LFQ_OK;
+}
+
+/* base pass of the decode lfq_bam_aux began, into the read set's device arrays (d_bi / d_bd null: the read set has none), and
+ * their copies back into the pinned host arrays.  Blocks. */
+int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, uint8_t *d_bd, uint8_t *h_seq, uint8_t *h_qual,
+                  uint8_t *h_bi, uint8_t *h_bd)
+{
+    LfqBamState *S = bam_state(c);
+    LfqBamArgs A = S->args;
+    const int64_t nb = A.n_bases;
+    if (nb <= 0) {
+        return LFQ_OK;
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    A.seq = d_seq; A.qual = d_qual; A.bi = d_bi; A.bd = d_bd;
+    const int64_t per_wg = (int64_t)LFQ_BAM_BASE_CHUNKS * 16;
+    LFQ_TRY_HIP(hipEventRecord(S->ev[4], st));
+    hipLaunchKernelGGL(lfq_bam_bases_kernel, dim3((unsigned)((nb + per_wg - 1) / per_wg)), dim3(LFQ_BAM_BASE_CHUNKS), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY_HIP(hipEventRecord(S->ev[5], st));
+    S->times.n_launches += 1;
+    LFQ_TRY_HIP(hipEventRecord(S->ev[6], st));
+    LFQ_TRY_HIP(hipMemcpyAsync(h_seq, d_seq, (size_t)nb, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(h_qual, d_qual, (size_t)nb, hipMemcpyDeviceToHost, st));
+    if (d_bi) {
+        LFQ_TRY_HIP(hipMemcpyAsync(h_bi, d_bi, (size_t)nb, hipMemcpyDeviceToHost, st));
+    }
+    if (d_bd) {
+        LFQ_TRY_HIP(hipMemcpyAsync(h_bd, d_bd, (size_t)nb, hipMemcpyDeviceToHost, st));
+    }
+    LFQ_TRY_HIP(hipEventRecord(S->ev[7], st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    S->times.kernels_ms += bam_ms(S->ev[4], S->ev[5]);
+    S->times.download_ms = bam_ms(S->ev[6], S->ev[7]);
+    return LFQ_OK;
+}
+
+extern "C" int lfq_last_bam_decode_times(lfq_ctx *c, lfq_bam_decode_times *t)
+{
+    if (!c || !t) {
+        return LFQ_ERR_INVALID;
+    }
+    *t = bam_state(c)->times;
+    return LFQ_OK;
+}

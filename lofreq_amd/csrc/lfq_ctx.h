@@ -6,6 +6,7 @@
  *   lfq_api.hip        context, streams, the batch driver (layer 1), the call_snvs loop (layer 2), uniq, generator
  *   lfq_indel_api.hip  the indel tests (lfq_call_indel_tests_batch, lfq_call_indels_batch)
  *   lfq_readset.hip    the resident read set: upload, BAQ / IDAQ, source quality, both pileups
+ *   lfq_bamrec.hip     BAM records decoded on the device: kernels and their launches (for lfq_readset.hip)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -330,7 +331,7 @@ struct lfq_ctx {
     /* the allocations of the read set destroyed last (reads, tags, read ends, tag flags, pinned flags): the next
      * lfq_readset_create / _baq takes them over when they are large enough -- a worker goes from region to region, and
      * hipMalloc + hipFree of 2 GB per region are milliseconds and a device synchronisation each */
-    struct { void *p; size_t cap; } rs_cache[7];
+    struct { void *p; size_t cap; } rs_cache[8];
     int priv_stream_on;
     hipStream_t priv_stream;         /* lfq_set_private_stream: this context's own launch stream (null = the device's shared one) */
     hipStream_t up_stream;           /* lfq_readset_create's uploads and the staging copies of host tracks (created on first use) */
@@ -412,6 +413,7 @@ struct lfq_ctx {
     int sb_pending;                  /* strand-bias precomputes of this context not finished yet (under lm) */
     struct { void *p; size_t cap; int used; } pin_pool[LFQ_PIN_SLOTS];   /* LfqPin: pinned host temporaries */
     struct LfqViterbiState *vit;     /* lfq_viterbi_batch: its result and device buffers (lfq_viterbi.hip; created on first use) */
+    struct LfqBamState *bam;         /* lfq_readset_create_from_bam: records, descriptors and timing (lfq_bamrec.hip; created on first use) */
 };
 
 template <typename T>
@@ -490,6 +492,14 @@ int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *reads, int def_qual, const 
 /* dst[k][new order] = src[k][old order] for up to four per-base arrays; returns when the kernel is done */
 int lfq_viterbi_permute(lfq_ctx *c, int64_t n_reads, int64_t n_bases, const int64_t *d_new_off, const int64_t *old_start,
                         int n_arrays, const uint8_t *const *src, uint8_t *const *dst);
+/* lfq_bamrec.hip, for lfq_readset_create_from_bam (lfq_readset.hip): upload + aux pass, then the base pass into a read set's
+ * device arrays and the copies back; both block */
+void lfq_bam_release(lfq_ctx *c);
+void lfq_bam_times_reset(lfq_ctx *c, int64_t n_reads, int64_t n_bases, int64_t n_data_bytes);
+int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_shift, bool data_pinned, const int64_t *desc,
+                int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi, int *any_bd);
+int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, uint8_t *d_bd, uint8_t *h_seq, uint8_t *h_qual,
+                  uint8_t *h_bi, uint8_t *h_bd);
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

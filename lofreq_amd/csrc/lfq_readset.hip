@@ -14,16 +14,21 @@ extern "C" {
  * copy and leave their per-base results (lb, ai, ad, sq) there for the next stage.  The host arrays handed to
  * lfq_readset_create stay the caller's and must outlive the read set: the sparse host-side steps (geometry from the
  * CIGARs, the indel event tables) read them in place. */
-enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5, LFQ_RSC_IDQ = 6 };
+enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5, LFQ_RSC_IDQ = 6, LFQ_RSC_PINBASES = 7 };
+
+static bool rs_cache_pinned(int kind)
+{
+    return kind == LFQ_RSC_PINFL || kind == LFQ_RSC_PINBASES;
+}
 
 static void rs_cache_free(int kind, void *p)
 {
     if (p) {
-        (void)(kind == LFQ_RSC_PINFL ? hipHostFree(p) : hipFree(p));
+        (void)(rs_cache_pinned(kind) ? hipHostFree(p) : hipFree(p));
     }
 }
 
-/* `bytes` of device memory (pinned host memory for LFQ_RSC_PINFL): the cached block of this kind if it is large enough */
+/* `bytes` of device memory (pinned host memory for LFQ_RSC_PINFL and LFQ_RSC_PINBASES): the cached block of this kind if it is large enough */
 static void *rs_cache_take(lfq_ctx *c, int kind, size_t bytes, size_t *cap_out)
 {
     auto &e = c->rs_cache[kind];
@@ -39,7 +44,7 @@ static void *rs_cache_take(lfq_ctx *c, int kind, size_t bytes, size_t *cap_out)
     e.cap = 0;
     void *p = nullptr;
     const size_t want = std::max<size_t>(bytes, 256);
-    const hipError_t rc = (kind == LFQ_RSC_PINFL) ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+    const hipError_t rc = rs_cache_pinned(kind) ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
     if (rc != hipSuccess) {
         return nullptr;
     }
@@ -62,13 +67,16 @@ static void rs_cache_give(lfq_ctx *c, int kind, void *p, size_t cap)
     }
 }
 
-/* what a read set made by lfq_readset_viterbi owns: the host arrays its host-side steps read, in its own read order */
+/* what a read set made by lfq_readset_viterbi or lfq_readset_create_from_bam owns: the host arrays its host-side steps read, in
+ * its own read order */
 struct LfqReadsetOwned {
     LfqVec<int32_t> pos;
     LfqVec<int64_t> cigar_off, seq_off, order;
     LfqVec<uint32_t> cigar;
     LfqVec<uint8_t> mapq, reverse, flags, seq, qual, bi, bd;
     LfqVec<char> ref;
+    uint8_t *pin_bases = nullptr;       /* lfq_readset_create_from_bam: seq | qual | BI | BD as they came back from the device, pinned */
+    size_t pin_cap = 0;                 /* (rs_cache kind LFQ_RSC_PINBASES: goes back to the context with the read set) */
 };
 
 #define LFQ_UP_CHUNKS 6
@@ -250,6 +258,9 @@ void lfq_readset_destroy(lfq_readset *rs)
         }
         rs_cache_give(rs->c, LFQ_RSC_IDQ, rs->idq_blob, rs->cap[LFQ_RSC_IDQ]);
         if (rs->ev_keep) (void)hipEventDestroy(rs->ev_keep);
+        if (rs->own) {
+            rs_cache_give(rs->c, LFQ_RSC_PINBASES, rs->own->pin_bases, rs->own->pin_cap);
+        }
         delete rs->own;
         delete rs;
     }
@@ -3209,6 +3220,143 @@ int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset *
     *out = ns;
     if (result_out) *result_out = res;
     if (order_out) *order_out = ns->own->order.data();
+    return LFQ_OK;
+}
+
+/* The read set of BAM records as they lie in memory (bam1_t.data): what lfq_region_add_read's loop and lfq_readset_create build
+ * from them, with the per-base work -- nibbles -> base codes, qualities, the BI / BD strings found among the aux fields -- done
+ * by the two launches of lfq_bamrec.hip.  The host reads per READ only: descriptor checks, prefix sums, the CIGAR words.  *out
+ * owns its host arrays (LfqReadsetOwned); the per-base ones come back from the device into pinned memory.  Blocks. */
+int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_readset **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !recs || !out || recs->n_reads < 0) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = recs->n_reads;
+    if (n > 0 && (!recs->data || !recs->data_off || !recs->pos || !recs->flag || !recs->mapq || !recs->l_qname || !recs->n_cigar
+                  || !recs->l_qseq || !recs->ref)) {
+        return LFQ_ERR_INVALID;
+    }
+    std::unique_ptr<LfqReadsetOwned> own(new LfqReadsetOwned());
+    own->cigar_off.resize((size_t)n + 1);
+    own->seq_off.resize((size_t)n + 1);
+    own->cigar_off[0] = own->seq_off[0] = 0;
+    for (int64_t r = 0; r < n; r++) {
+        const int64_t o0 = recs->data_off[r], o1 = recs->data_off[r + 1], l = recs->l_qseq[r];
+        if (o1 < o0 || l < 0 || o1 - o0 < (int64_t)recs->l_qname[r] + 4 * (int64_t)recs->n_cigar[r] + (l + 1) / 2 + l) {
+            return LFQ_ERR_INVALID;
+        }
+        own->cigar_off[(size_t)r + 1] = own->cigar_off[(size_t)r] + recs->n_cigar[r];
+        own->seq_off[(size_t)r + 1] = own->seq_off[(size_t)r] + l;
+    }
+    const int64_t nb = own->seq_off[(size_t)n], first = n > 0 ? recs->data_off[0] : 0,
+                  data_bytes = n > 0 ? recs->data_off[n] - first : 0;
+    own->pos.resize((size_t)std::max<int64_t>(n, 1));
+    own->mapq.resize((size_t)std::max<int64_t>(n, 1));
+    own->reverse.resize((size_t)std::max<int64_t>(n, 1));
+    own->flags.resize((size_t)std::max<int64_t>(n, 1));
+    own->cigar.resize((size_t)own->cigar_off[(size_t)n] + 1);
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    lfq_bam_times_reset(c, n, nb, data_bytes);
+    lfq_pileup_reads pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.n_reads = n;
+    pr.ref = recs->ref; pr.ref_len = recs->ref_len;
+    if (n == 0) {
+        lfq_readset *es = nullptr;
+        LFQ_TRY(readset_create(c, &pr, nullptr, &es));
+        es->own = own.release();
+        *out = es;
+        return LFQ_OK;
+    }
+    /* device offsets: the records keep the alignment they have in the caller's memory */
+    const uint8_t *data = recs->data + first;
+    const int first_shift = (int)((uintptr_t)data & 15);
+    LfqPin<int64_t> desc(c, (size_t)(3 * n + 1));       /* seq_off[n + 1] | seq_src[n] | rec_end[n] */
+    LFQ_PIN_OK(desc);
+    memcpy(desc.data(), own->seq_off.data(), (size_t)(n + 1) * sizeof(int64_t));
+    int64_t *seq_src = desc.data() + n + 1, *rec_end = seq_src + n;
+    LfqReadsetOwned *o = own.get();
+    lfq_for_reads(n, [&](int64_t r0, int64_t r1, int) {
+        for (int64_t r = r0; r < r1; r++) {
+            const int64_t at = recs->data_off[r] - first + recs->l_qname[r], nc = recs->n_cigar[r];
+            o->pos[(size_t)r] = recs->pos[r];
+            o->mapq[(size_t)r] = recs->mapq[r];
+            o->reverse[(size_t)r] = (uint8_t)((recs->flag[r] >> 4) & 1);
+            if (nc > 0) {
+                memcpy(o->cigar.data() + o->cigar_off[(size_t)r], data + at, (size_t)nc * 4);
+            }
+            seq_src[r] = first_shift + at + 4 * nc;
+            rec_end[r] = first_shift + recs->data_off[r + 1] - first;
+        }
+    });
+    int any_bi = 0, any_bd = 0;
+    LFQ_TRY(lfq_bam_aux(c, data, data_bytes, first_shift, lfq_is_pinned(data), desc.data(), n, nb, own->flags.data(), &any_bi,
+                        &any_bd));
+    /* the pinned landing area of the per-base arrays, from the context's cache; the host views of the read set point into it */
+    const size_t stride = (size_t)((nb + 16 + 255) / 256 * 256);
+    own->pin_bases = (uint8_t *)rs_cache_take(c, LFQ_RSC_PINBASES, stride * (size_t)(2 + any_bi + any_bd), &own->pin_cap);
+    if (!own->pin_bases) {
+        return LFQ_ERR_NOMEM;
+    }
+    uint8_t *h_seq = own->pin_bases, *h_qual = h_seq + stride, *h_bi = any_bi ? h_qual + stride : nullptr,
+            *h_bd = any_bd ? h_qual + stride * (size_t)(1 + any_bi) : nullptr;
+    pr.pos = own->pos.data(); pr.cigar_off = own->cigar_off.data(); pr.cigar = own->cigar.data();
+    pr.seq_off = own->seq_off.data(); pr.seq = h_seq; pr.qual = h_qual;
+    pr.mapq = own->mapq.data(); pr.reverse = own->reverse.data();
+    lfq_pileup_indel_tags tg;
+    memset(&tg, 0, sizeof(tg));
+    tg.bi = h_bi;
+    tg.bd = h_bd;
+    tg.tag_flags = own->flags.data();
+    lfq_readset *ns = nullptr;
+    int rc = readset_create(c, &pr, &tg, &ns, true);
+    if (rc != LFQ_OK) {
+        rs_cache_give(c, LFQ_RSC_PINBASES, own->pin_bases, own->pin_cap);
+        return rc;
+    }
+    ns->own = own.release();
+    rc = lfq_bam_bases(c, ns->d_seq, ns->d_qual, any_bi ? ns->d_bi : nullptr, any_bd ? ns->d_bd : nullptr, h_seq, h_qual, h_bi, h_bd);
+    if (rc == LFQ_OK) {
+        rc = readset_upload_wait(ns);               /* the per-read arrays are on the device */
+    }
+    if (rc != LFQ_OK) {
+        lfq_readset_destroy(ns);
+        return rc;
+    }
+    *out = ns;
+    return LFQ_OK;
+}
+
+/* copies of the resident per-base inputs, from the DEVICE: bases (0..15), qualities, BI / BD bytes ('!' throughout for an array the
+ * read set does not have) and per read bit 0 / 1 = has BI / BD; NULL = not wanted */
+int lfq_readset_fetch_bases(lfq_ctx *c, lfq_readset *rs, uint8_t *seq_out, uint8_t *qual_out, uint8_t *bi_out, uint8_t *bd_out,
+                            uint8_t *tag_flags_out)
+{
+    if (!c || !rs || rs->c != c || ((bi_out || bd_out || tag_flags_out) && rs->idq_mode)
+        || (rs->n > 0 && ((seq_out && !rs->seq) || (qual_out && !rs->qual)))) {
+        return LFQ_ERR_INVALID;                     /* (after lfq_readset_indelqual: lfq_readset_fetch_indelquals) */
+    }
+    if (rs->n == 0) {
+        return LFQ_OK;
+    }
+    const size_t nb = (size_t)rs->n_bases;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    LFQ_TRY(readset_upload_wait(rs));
+    const struct { uint8_t *dst; const uint8_t *src; bool have; } todo[4] = {
+        {seq_out, rs->d_seq, true}, {qual_out, rs->d_qual, true}, {bi_out, rs->d_bi, rs->has_bi}, {bd_out, rs->d_bd, rs->has_bd}};
+    for (const auto &x : todo) {
+        if (x.dst && x.have && nb > 0) {
+            LFQ_TRY_HIP(hipMemcpyAsync(x.dst, x.src, nb, hipMemcpyDeviceToHost, c->stream));
+        } else if (x.dst) {
+            memset(x.dst, 33, nb);
+        }
+    }
+    LFQ_TRY_HIP(hipStreamSynchronize(c->stream));
+    for (int64_t r = 0; tag_flags_out && r < rs->n; r++) {
+        tag_flags_out[r] = (uint8_t)(rs->fl[(size_t)r] & 3u);
+    }
     return LFQ_OK;
 }
 

@@ -320,6 +320,13 @@ def last_plp_quals_times(caller):
     return t
 
 
+def last_bam_decode_times(caller):
+    """lfq_last_bam_decode_times -> dict(upload_ms, kernels_ms, download_ms, n_reads, n_bases, n_data_bytes, n_launches)"""
+    t = _lib.BamDecodeTimes()
+    _lib.check(_lib.load().lfq_last_bam_decode_times(caller.h, C.byref(t)), "lfq_last_bam_decode_times")
+    return {k: getattr(t, k) for k, _ in _lib.BamDecodeTimes._fields_}
+
+
 def _format_grown(call, what):
     """a formatter whose text grows with the depth: ask for the length, then write"""
     n = call(None, 0)
@@ -441,6 +448,47 @@ class ReadSet:
             caller._readsets = weakref.WeakSet()
         caller._readsets.add(self)
         return self
+
+    @classmethod
+    def from_bam_records(cls, caller, data, data_off, pos, flag, mapq, l_qname, n_cigar, l_qseq, ref):
+        """lfq_readset_create_from_bam: the read set of BAM records as they lie in memory -- data: the bytes of every record from
+        read_name on (bam1_t.data), concatenated; data_off [n + 1] into it; pos, flag, mapq, l_qname, n_cigar, l_qseq: the core
+        fields per read; ref: the contig (bytes).  Bases, qualities and BI / BD are decoded on the device; the read set owns
+        its host arrays, so only `ref` is kept alive here."""
+        self = cls.__new__(cls)
+        self.caller = caller
+        self.L = _lib.load()
+        a = {k: np.ascontiguousarray(v, dt) for k, v, dt in (
+            ("data", data, np.uint8), ("data_off", data_off, np.int64), ("pos", pos, np.int32), ("flag", flag, np.uint16),
+            ("mapq", mapq, np.uint8), ("l_qname", l_qname, np.uint16), ("n_cigar", n_cigar, np.uint32), ("l_qseq", l_qseq, np.int32))}
+        self.n = len(a["pos"])
+        if len(a["data_off"]) != self.n + 1 or any(len(a[k]) != self.n for k in ("flag", "mapq", "l_qname", "n_cigar", "l_qseq")):
+            raise ValueError("from_bam_records: data_off takes n + 1 entries, every other per-read array n")
+        rc = _lib.BamRecords()
+        rc.n_reads = self.n
+        for k in a:
+            setattr(rc, k, a[k].ctypes.data)
+        self._keep = {"ref": bytes(ref)}
+        rc.ref = C.cast(C.c_char_p(self._keep["ref"]), C.c_void_p)
+        rc.ref_len = len(self._keep["ref"])
+        self.seq_off = np.concatenate([[0], np.cumsum(a["l_qseq"], dtype=np.int64)]).astype(np.int64)
+        h = C.c_void_p()
+        _lib.check(self.L.lfq_readset_create_from_bam(caller.h, C.byref(rc), C.byref(h)), "lfq_readset_create_from_bam")
+        self.h = h
+        if not hasattr(caller, "_readsets"):
+            import weakref
+            caller._readsets = weakref.WeakSet()
+        caller._readsets.add(self)
+        return self
+
+    def fetch_bases(self):
+        """lfq_readset_fetch_bases: the resident per-base inputs read back from the device -> (seq codes 0..15, qual, bi, bd:
+        uint8 per base in the seq_off layout, '!' throughout for a tag array the read set lacks; flags: uint8 per read, bit 0 / 1
+        = has BI / BD)"""
+        nb = int(self.seq_off[-1])
+        out = [np.zeros(max(nb, 1), np.uint8) for _ in range(4)] + [np.zeros(max(self.n, 1), np.uint8)]
+        _lib.check(self.L.lfq_readset_fetch_bases(self.caller.h, self.h, *[o.ctypes.data for o in out]), "lfq_readset_fetch_bases")
+        return tuple(o[:nb] for o in out[:4]) + (out[4][: self.n],)
 
     def close(self):
         if getattr(self, "h", None):

@@ -46,6 +46,7 @@ extern "C" {
 /* (10 still: lfq_readset_plp_summary, lfq_format_plp_summary, lfq_last_summary_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_plp_quals_from_tracks, lfq_format_plp_quals, lfq_format_plp_indel_quals, lfq_set_indel_arrays_all_columns, lfq_last_plp_quals_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_readset_create_from_bam, lfq_readset_fetch_bases, lfq_last_bam_decode_times are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_readset_encode_bam, lfq_last_bam_encode_times are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -611,6 +612,73 @@ typedef struct lfq_bam_decode_times {
     int n_launches;
 } lfq_bam_decode_times;
 int lfq_last_bam_decode_times(lfq_ctx *ctx, lfq_bam_decode_times *t);
+
+/* The way back: the results of a read set's steps WRITTEN INTO THE BYTES OF BAM RECORDS on the device -- what `lofreq viterbi`,
+ * `lofreq alnqual` and `lofreq indelqual` do to a record with bam_aux_get / bam_aux_del / bam_aux_append and replace_cigar -- so
+ * that one copy of the original records goes down and one blob of rewritten records comes back, instead of three to five per-base
+ * arrays and a memmove per deleted or appended field on the calling thread.
+ *   recs          the ORIGINAL records, in the struct of the decode (ref / ref_len are not read);
+ *   src_or_null   src[j] = the record of read j of `rs`; NULL = the identity.  After lfq_readset_viterbi: its `order`;
+ *   what          LFQ_BAM_* bits, at least one.
+ * Output record j = qname | cigar | seq | qual | aux', made from record src[j]; qname, seq and qual are copied byte for byte, and
+ * l_qname, l_qseq, flag and mapq of the output record are those of record src[j].  aux' = the surviving fields of the record in
+ * their order, then the appended ones in the order lb, ai, ad, BI, BD, each as tag 'Z' <l_qseq bytes> NUL.  "The first field" of a
+ * tag is the first aux field with that tag in record order WHATEVER ITS TYPE (bam_aux_get); later fields with the same tag are
+ * never touched.
+ *   LFQ_BAM_PUT_ALIGNMENT   CIGAR words, n_cigar and pos come from the read set, for every read (replace_cigar,
+ *                           lofreq_viterbi.c:340); without it they are the record's.
+ *   LFQ_BAM_DROP_ALN_TAGS   `lofreq viterbi` without -k: the first NM, MC, MD and AS field of EVERY record is removed, any type,
+ *                           unmapped reads included (lofreq_viterbi.c:119-146).
+ *   LFQ_BAM_PUT_LB, LFQ_BAM_PUT_IDAQ, LFQ_BAM_KEEP_EXISTING   `lofreq alnqual`, only for records with !(flag & 4) and l_qseq > 0;
+ *                           the others pass through (bam_md_ext.c:291).  For t in lb, ai, ad let F_t be the first field of the
+ *                           tag.  Without KEEP_EXISTING (= alnqual -r): if t is selected -- lb by PUT_LB, ai and ad by PUT_IDAQ --
+ *                           and F_t is of type Z, F_t is removed and P_t = false; otherwise P_t = (F_t exists), so a non-Z lb is
+ *                           neither removed nor replaced (:297-314).  With KEEP_EXISTING nothing is removed and P_t = (F_t
+ *                           exists).  has_ins / has_del = the read set's CIGAR of the read has an I / D operation.  Nothing is
+ *                           appended when (!PUT_LB || P_lb) && (!has_del || P_ad) && (!has_ins || P_ai) (:352-366; the removals
+ *                           stand).  Otherwise lb is appended iff PUT_LB && !P_lb (:409, :472), and with PUT_IDAQ && (has_ins ||
+ *                           has_del) ai is appended iff the read got an ai tag and ad iff it got an ad tag (tag_flags of
+ *                           lfq_readset_fetch_tags; :241-246) -- WHATEVER P_ai / P_ad say: the reference can duplicate a tag
+ *                           here, and so does this.
+ *   LFQ_BAM_PUT_INDELQUAL   `lofreq indelqual`: the first BI and the first BD field are removed, any type, and BI then BD are
+ *                           appended from the read set's computed qualities -- in uniform mode for every record, unmapped and
+ *                           empty ones included (lofreq_indelqual.c:69-104), in Dindel mode for records with !(flag & 0x704)
+ *                           only, the others pass through (:143-148).
+ * With several bits set the result is that of the reference commands run one after the other (their tag sets are disjoint).
+ * What the caller still does when it writes the records out: the core fields in front of each record -- block_size, refID, pos
+ * and n_cigar from the result, mate fields --, core.bin, which depends on the new pos and CIGAR and is the caller's to recompute,
+ * and BGZF.
+ * *out is the context's: valid until its next encode or lfq_destroy.  The call blocks until the blob is complete.
+ * LFQ_ERR_INVALID, before a device is touched: a NULL ctx, rs, recs or out; what == 0, an unknown bit, KEEP_EXISTING without
+ * PUT_LB / PUT_IDAQ; the descriptor cases of the decode (ref aside) and a record of 2^31 bytes or more; a read set of another
+ * context; recs->n_reads different from the read set's; src not a permutation of 0 .. n-1; recs->l_qseq[src[j]] different from the
+ * length of read j; PUT_LB on a read set without lb (no lfq_readset_baq), PUT_IDAQ without ai / ad (no lfq_readset_baq with
+ * want_idaq), PUT_INDELQUAL before lfq_readset_indelqual.  LFQ_ERR_INVALID from the device (*out = NULL, the context stays
+ * usable): a malformed aux block, the cases of the decode.  n_reads == 0: LFQ_OK, an empty result, nothing launched. */
+#define LFQ_BAM_PUT_ALIGNMENT  1
+#define LFQ_BAM_DROP_ALN_TAGS  2
+#define LFQ_BAM_PUT_LB         4
+#define LFQ_BAM_PUT_IDAQ       8
+#define LFQ_BAM_KEEP_EXISTING 16
+#define LFQ_BAM_PUT_INDELQUAL 32
+typedef struct lfq_bam_encoded {
+    int64_t n_reads;
+    const uint8_t *data;      /* the records from read_name on, concatenated, in the READ SET's read order (pinned memory) */
+    const int64_t *data_off;  /* [n + 1], data_off[0] = 0 */
+    const int64_t *src;       /* [n] index in recs of the record read j was made from */
+    const int32_t *pos;       /* [n] core.pos to write */
+    const uint32_t *n_cigar;  /* [n] core.n_cigar to write */
+} lfq_bam_encoded;
+int lfq_readset_encode_bam(lfq_ctx *ctx, lfq_readset *rs, const lfq_bam_records *recs, const int64_t *src_or_null,
+                           unsigned what, const lfq_bam_encoded **out);
+/* the context's last lfq_readset_encode_bam on the device's clock: the records and descriptors down, the two kernels (plan pass +
+ * copy pass), the blob back into pinned memory */
+typedef struct lfq_bam_encode_times {
+    double upload_ms, kernels_ms, download_ms;
+    int64_t n_reads, n_in_bytes, n_out_bytes;
+    int n_launches;
+} lfq_bam_encode_times;
+int lfq_last_bam_encode_times(lfq_ctx *ctx, lfq_bam_encode_times *t);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

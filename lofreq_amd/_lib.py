@@ -145,6 +145,20 @@ class BamDecodeTimes(C.Structure):
                 ("n_bases", C.c_int64), ("n_data_bytes", C.c_int64), ("n_launches", C.c_int)]
 
 
+LFQ_BAM_PUT_ALIGNMENT, LFQ_BAM_DROP_ALN_TAGS, LFQ_BAM_PUT_LB, LFQ_BAM_PUT_IDAQ = 1, 2, 4, 8
+LFQ_BAM_KEEP_EXISTING, LFQ_BAM_PUT_INDELQUAL = 16, 32
+
+
+class BamEncoded(C.Structure):
+    """lfq_bam_encoded: owned by the context, valid until its next lfq_readset_encode_bam"""
+    _fields_ = [("n_reads", C.c_int64)] + [(n, C.c_void_p) for n in ("data", "data_off", "src", "pos", "n_cigar")]
+
+
+class BamEncodeTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("kernels_ms", C.c_double), ("download_ms", C.c_double), ("n_reads", C.c_int64),
+                ("n_in_bytes", C.c_int64), ("n_out_bytes", C.c_int64), ("n_launches", C.c_int)]
+
+
 class PileupIndelTags(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("bi", "bd", "ai", "ad", "tag_flags", "sq")]
 
@@ -206,6 +220,7 @@ EXPORTS = [
     "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
     "lfq_readset_viterbi",
     "lfq_readset_create_from_bam", "lfq_readset_fetch_bases", "lfq_last_bam_decode_times",
+    "lfq_readset_encode_bam", "lfq_last_bam_encode_times",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
     "lfq_plp_quals_from_tracks", "lfq_format_plp_quals", "lfq_set_indel_arrays_all_columns", "lfq_format_plp_indel_quals",
@@ -339,6 +354,8 @@ def load():
     L.lfq_readset_create_from_bam.argtypes = [vp, C.POINTER(BamRecords), C.POINTER(vp)]
     L.lfq_readset_fetch_bases.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.lfq_last_bam_decode_times.argtypes = [vp, C.POINTER(BamDecodeTimes)]
+    L.lfq_readset_encode_bam.argtypes = [vp, vp, C.POINTER(BamRecords), vp, C.c_uint, C.POINTER(C.POINTER(BamEncoded))]
+    L.lfq_last_bam_encode_times.argtypes = [vp, C.POINTER(BamEncodeTimes)]
     L.lfq_readset_destroy.argtypes = [vp]
     L.lfq_readset_destroy.restype = None
     L.lfq_readset_baq.argtypes = [vp, vp, C.c_int, C.c_int]

@@ -1,7 +1,8 @@
 /*
  * lfq_bamrec.hip -- BAM records decoded on the device (lfq_readset_create_from_bam): the bytes of the records go
  * down as they lie in bam1_t.data, an aux pass finds BI / BD per read, a base pass writes the per-base arrays of the read set.
- * The host side that builds the read set around these two launches is in lfq_readset.hip.
+ * The host side that builds the read set around these two launches is in lfq_readset.hip.  Further down, the way back
+ * (lfq_readset_encode_bam): the records rewritten with a read set's results, a plan pass per read and a copy pass per 16 output bytes.
  */
 #include "lfq_ctx.h"
 
@@ -295,6 +296,7 @@ struct LfqBamState {
     hipEvent_t ev[8];                   /* around the upload, the aux pass, the base pass, the copies back */
     LfqBamArgs args;                    /* of the decode in flight between lfq_bam_aux and lfq_bam_bases */
     lfq_bam_decode_times times;
+    struct LfqBamEncState *enc;         /* lfq_readset_encode_bam: its result and buffers (below; created on first use) */
 };
 
 static LfqBamState *bam_state(lfq_ctx *c)
@@ -306,9 +308,12 @@ static LfqBamState *bam_state(lfq_ctx *c)
     return c->bam;
 }
 
+static void bam_enc_release(struct LfqBamEncState *E);
+
 void lfq_bam_release(lfq_ctx *c)
 {
     if (c->bam) {
+        bam_enc_release(c->bam->enc);
         if (c->bam->d_buf) (void)hipFree(c->bam->d_buf);
         if (c->bam->h_stage) (void)hipHostFree(c->bam->h_stage);
         for (hipEvent_t e : c->bam->ev) {
@@ -334,6 +339,40 @@ static float bam_ms(hipEvent_t a, hipEvent_t b)
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
 }
 
+/* records that come in pageable memory: *data becomes their copy in the pinned staging area */
+static int bam_stage(lfq_ctx *c, LfqBamState *S, const uint8_t **data_io, int64_t data_bytes)
+{
+    const uint8_t *data = *data_io;
+    if (data_bytes > S->h_bytes) {
+        if (S->h_stage) (void)hipHostFree(S->h_stage);
+        S->h_stage = nullptr;
+        S->h_bytes = 0;
+        const int64_t want = std::max<int64_t>(data_bytes + data_bytes / 4, 1 << 16);
+        if (hipHostMalloc((void **)&S->h_stage, (size_t)want, hipHostMallocDefault) != hipSuccess) {
+            return LFQ_ERR_NOMEM;
+        }
+        S->h_bytes = want;
+    }
+    /* (a few threads: one copies at a fraction of what the link takes) */
+    const unsigned hw = std::max(1u, lfq_cpu_budget() / (unsigned)std::max(lfq_knobs().local_world_size, 1));
+    const int parts = data_bytes >= ((int64_t)32 << 20) ? (int)std::min(8u, hw) : 1;
+    uint8_t *stage = S->h_stage;
+    auto copy_part = [=](int p) {
+        const int64_t a = data_bytes * p / parts, b = data_bytes * (p + 1) / parts;
+        memcpy(stage + a, data + a, (size_t)(b - a));
+    };
+    std::vector<std::thread> th;
+    for (int p = 1; p < parts; p++) {
+        th.emplace_back(copy_part, p);
+    }
+    copy_part(0);
+    for (auto &t : th) {
+        t.join();
+    }
+    *data_io = S->h_stage;
+    return LFQ_OK;
+}
+
 /* records down, aux pass, its verdict back: flags_out[n], *any_bi / *any_bd; LFQ_ERR_INVALID for a malformed aux field.
  * data[0 .. data_bytes) are the records, first_shift (0 .. 15) bytes of room are left in front of them on the device so that a
  * record keeps the alignment it has in the caller's buffer; desc = seq_off[n + 1] | seq_src[n] | rec_end[n], the last two as
@@ -354,33 +393,7 @@ int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_s
                   n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), total = o_tile + al(n_tiles * 8);
     LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
     if (!data_pinned) {
-        if (data_bytes > S->h_bytes) {
-            if (S->h_stage) (void)hipHostFree(S->h_stage);
-            S->h_stage = nullptr;
-            S->h_bytes = 0;
-            const int64_t want = std::max<int64_t>(data_bytes + data_bytes / 4, 1 << 16);
-            if (hipHostMalloc((void **)&S->h_stage, (size_t)want, hipHostMallocDefault) != hipSuccess) {
-                return LFQ_ERR_NOMEM;
-            }
-            S->h_bytes = want;
-        }
-        /* (a few threads: one copies at a fraction of what the link takes) */
-        const unsigned hw = std::max(1u, lfq_cpu_budget() / (unsigned)std::max(lfq_knobs().local_world_size, 1));
-        const int parts = data_bytes >= ((int64_t)32 << 20) ? (int)std::min(8u, hw) : 1;
-        uint8_t *stage = S->h_stage;
-        auto copy_part = [=](int p) {
-            const int64_t a = data_bytes * p / parts, b = data_bytes * (p + 1) / parts;
-            memcpy(stage + a, data + a, (size_t)(b - a));
-        };
-        std::vector<std::thread> th;
-        for (int p = 1; p < parts; p++) {
-            th.emplace_back(copy_part, p);
-        }
-        copy_part(0);
-        for (auto &t : th) {
-            t.join();
-        }
-        data = S->h_stage;
+        LFQ_TRY(bam_stage(c, S, &data, data_bytes));
     }
     LfqPin<int32_t> verdict(c, 4);
     LFQ_PIN_OK(verdict);
@@ -467,5 +480,495 @@ extern "C" int lfq_last_bam_decode_times(lfq_ctx *c, lfq_bam_decode_times *t)
         return LFQ_ERR_INVALID;
     }
     *t = bam_state(c)->times;
+    return LFQ_OK;
+}
+
+/* ==== the way back: lfq_readset_encode_bam =======================================================================================
+ * The records of a read set rewritten on the device (include/lofreq_amd.h has the rules): a plan pass, one lane per read, walks
+ * the aux fields of the read's record once and writes down which byte ranges survive, which of lb / ai / ad / BI / BD are appended
+ * and how long the new record is; the host makes offsets of the lengths; a copy pass, output-major like the base pass of the
+ * decode, writes the blob. */
+#define LFQ_BAM_PLAN_READS 256          /* reads per workgroup of the plan pass: one lane each */
+#define LFQ_BAM_COPY_CHUNKS 256         /* 16-byte chunks of the output blob per workgroup of the copy pass: one lane each */
+#define LFQ_BAM_MAX_KEEP 10             /* NM MC MD AS lb ai ad BI BD: at most 9 removed fields, 10 surviving ranges around them */
+#define LFQ_BAM_N_APPEND 5              /* lb ai ad BI BD, in the order they are appended */
+#define LFQ_BAM_N_SEGMENTS (3 + LFQ_BAM_MAX_KEEP + 3 * LFQ_BAM_N_APPEND)
+
+struct LfqBamPlan {                     /* per read, written by the plan pass */
+    int32_t keep_beg[LFQ_BAM_MAX_KEEP]; /* surviving ranges of the aux block, from the record's first byte */
+    int32_t keep_len[LFQ_BAM_MAX_KEEP];
+    int32_t n_keep;
+    uint32_t append;                    /* bit f: field f of lb ai ad BI BD is appended */
+};
+
+struct LfqBamEncArgs {
+    const uint8_t *data;                /* the records; 4-byte aligned, 16 bytes of slack behind the last record */
+    const LfqBamRead *reads;            /* [n] */
+    LfqBamPlan *plan;                   /* [n] */
+    int64_t *out_len;                   /* [n] bytes of the new record (plan pass) */
+    int32_t *err;                       /* [0]: a malformed aux field */
+    const int64_t *out_off;             /* [n + 1] (host) */
+    const int64_t *tile_rec;            /* [workgroups of the copy pass] the read whose record holds the first byte of the tile (host) */
+    const int64_t *coff, *soff;         /* the read set's */
+    const uint32_t *cig;
+    const uint8_t *fl;
+    const uint8_t *lb, *ai, *ad, *bi, *bd;
+    uint8_t *out;                       /* 16-byte aligned, 16 bytes of slack */
+    int64_t n_reads, n_out;
+    uint32_t what;
+    int32_t uniform;
+};
+
+/* ---- plan pass: the aux walk of lfq_bam_aux_kernel with the reference's deletion and append rules ---------------------------------
+ * No read leaves [aux start, rec_end) */
+__global__ __launch_bounds__(LFQ_BAM_PLAN_READS) void lfq_bam_plan_kernel(LfqBamEncArgs A)
+{
+    const int64_t j = (int64_t)blockIdx.x * LFQ_BAM_PLAN_READS + threadIdx.x;
+    bool bad = false;
+    if (j < A.n_reads) {
+        const LfqBamRead R = A.reads[j];
+        const uint8_t *d = A.data;
+        const int64_t l = R.l_qseq, end = R.end;
+        const int64_t fixed = (int64_t)R.l_qname + 4 * (int64_t)R.n_cigar + (l + 1) / 2 + l, aux0 = R.rec + fixed;
+        const int64_t c0 = A.coff[j], c1 = A.coff[j + 1];
+        bool has_ins = false, has_del = false;
+        for (int64_t k = c0; k < c1; k++) {
+            const uint32_t op = A.cig[k] & 0xf;
+            has_ins = has_ins || op == 1;
+            has_del = has_del || op == 2;
+        }
+        const bool put_lb = (A.what & LFQ_BAM_PUT_LB) != 0, put_idaq = (A.what & LFQ_BAM_PUT_IDAQ) != 0;
+        const bool alnq = (put_lb || put_idaq) && !(R.flag & 4) && l > 0;                     /* bam_md_ext.c:291 */
+        const bool idq = (A.what & LFQ_BAM_PUT_INDELQUAL) && (A.uniform || !(R.flag & 0x704));  /* lofreq_indelqual.c:143-148 */
+        const bool drop = (A.what & LFQ_BAM_DROP_ALN_TAGS) != 0, keep_existing = (A.what & LFQ_BAM_KEEP_EXISTING) != 0;
+        uint32_t seen = 0;              /* bit 0..3: NM MC MD AS, 4..6: lb ai ad, 7..8: BI BD -- the FIRST field of a tag decides */
+        uint32_t present = 0;           /* bit 0..2: P_lb, P_ai, P_ad */
+        LfqBamPlan *P = A.plan + j;
+        int nk = 0;
+        int64_t kept = 0, run = aux0, p = aux0;
+        while (p < end) {
+            if (end - p < 3) {
+                bad = true;
+                break;
+            }
+            const uint8_t t0 = d[p], t1 = d[p + 1], ty = d[p + 2];
+            p += 3;
+            int64_t size = -1;
+            switch (ty) {
+            case 'A': case 'c': case 'C':
+                size = 1;
+                break;
+            case 's': case 'S':
+                size = 2;
+                break;
+            case 'i': case 'I': case 'f':
+                size = 4;
+                break;
+            case 'Z': case 'H': {
+                const int64_t q = bam_find_nul(d, p, end);
+                if (q < end) {
+                    size = q - p + 1;
+                }
+                break;
+            }
+            case 'B':
+                if (end - p >= 5) {
+                    const uint8_t sub = d[p];
+                    const int64_t cnt = (int64_t)d[p + 1] | ((int64_t)d[p + 2] << 8) | ((int64_t)d[p + 3] << 16) | ((int64_t)d[p + 4] << 24);
+                    const int64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
+                                       : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+                    if (es) {
+                        size = 5 + es * cnt;
+                    }
+                }
+                break;
+            default:
+                break;
+            }
+            if (size < 0 || size > end - p) {
+                bad = true;
+                break;
+            }
+            const int64_t f0 = p - 3, f1 = p + size;
+            int id = -1;
+            switch (((uint32_t)t0 << 8) | t1) {
+            case ('N' << 8) | 'M': id = 0; break;
+            case ('M' << 8) | 'C': id = 1; break;
+            case ('M' << 8) | 'D': id = 2; break;
+            case ('A' << 8) | 'S': id = 3; break;
+            case ('l' << 8) | 'b': id = 4; break;
+            case ('a' << 8) | 'i': id = 5; break;
+            case ('a' << 8) | 'd': id = 6; break;
+            case ('B' << 8) | 'I': id = 7; break;
+            case ('B' << 8) | 'D': id = 8; break;
+            default: break;
+            }
+            bool del = false;
+            if (id >= 0 && !((seen >> id) & 1u)) {
+                if (id < 4) {
+                    if (drop) {                             /* lofreq_viterbi.c:119-146: any type, every record */
+                        seen |= 1u << id;
+                        del = true;
+                    }
+                } else if (id < 7) {
+                    if (alnq) {                             /* bam_md_ext.c:297-314 */
+                        seen |= 1u << id;
+                        const bool selected = id == 4 ? put_lb : put_idaq;
+                        if (!keep_existing && selected && ty == 'Z') {
+                            del = true;
+                        } else {
+                            present |= 1u << (id - 4);
+                        }
+                    }
+                } else if (idq) {                           /* lofreq_indelqual.c:69-104 */
+                    seen |= 1u << id;
+                    del = true;
+                }
+            }
+            if (del) {
+                if (f0 > run && nk < LFQ_BAM_MAX_KEEP) {    /* (adjacent removals merge: nothing lies between them) */
+                    P->keep_beg[nk] = (int32_t)(run - R.rec);
+                    P->keep_len[nk] = (int32_t)(f0 - run);
+                    kept += f0 - run;
+                    nk++;
+                }
+                run = f1;
+            }
+            p = f1;
+        }
+        uint32_t app = 0;
+        if (bad) {
+            nk = 0;
+            kept = 0;
+        } else {
+            if (end > run && nk < LFQ_BAM_MAX_KEEP) {
+                P->keep_beg[nk] = (int32_t)(run - R.rec);
+                P->keep_len[nk] = (int32_t)(end - run);
+                kept += end - run;
+                nk++;
+            }
+            if (alnq) {
+                const bool p_lb = present & 1u, p_ai = present & 2u, p_ad = present & 4u;
+                const bool skip = (!put_lb || p_lb) && (!has_del || p_ad) && (!has_ins || p_ai);      /* bam_md_ext.c:352-366 */
+                if (!skip) {
+                    if (put_lb && !p_lb) {
+                        app |= 1u;
+                    }
+                    if (put_idaq && (has_ins || has_del)) { /* whatever P_ai / P_ad say (:241-246) */
+                        const uint8_t tf = A.fl[j];
+                        app |= ((tf & 4u) ? 2u : 0u) | ((tf & 8u) ? 4u : 0u);
+                    }
+                }
+            }
+            if (idq) {
+                app |= 8u | 16u;
+            }
+        }
+        P->n_keep = nk;
+        P->append = app;
+        const int64_t nc_out = (A.what & LFQ_BAM_PUT_ALIGNMENT) ? c1 - c0 : (int64_t)R.n_cigar;
+        A.out_len[j] = bad ? 0 : fixed - 4 * (int64_t)R.n_cigar + 4 * nc_out + kept + (int64_t)__popc(app) * (l + 4);
+    }
+    const bool any_bad = __any(bad);
+    if ((threadIdx.x & 63) == 0 && any_bad) {
+        atomicOr(&A.err[0], 1);
+    }
+}
+
+/* ---- copy pass: output-major, one lane per 16 bytes of the blob, one aligned 16-byte store per lane --------------------------------
+ * A new record is a list of LFQ_BAM_N_SEGMENTS segments, empty ones included: qname, CIGAR words, seq + qual, the surviving aux
+ * ranges, and per appended field its 3-byte head, its l_qseq bytes and its NUL.  Segment k of read j: `len` bytes from byte `src`
+ * of `base`, or -- base null -- the bytes of `cval`. */
+__device__ __forceinline__ void bam_enc_segment(const LfqBamEncArgs &A, int64_t j, const LfqBamRead &R, int k, const uint8_t **base,
+                                                int64_t *src, int64_t *len, uint32_t *cval)
+{
+    const int64_t l = R.l_qseq;
+    *base = A.data;
+    *cval = 0;
+    if (k == 0) {
+        *src = R.rec;
+        *len = R.l_qname;
+    } else if (k == 1) {
+        if (A.what & LFQ_BAM_PUT_ALIGNMENT) {
+            const int64_t c0 = A.coff[j];
+            *base = (const uint8_t *)A.cig;
+            *src = 4 * c0;
+            *len = 4 * (A.coff[j + 1] - c0);
+        } else {
+            *src = R.rec + R.l_qname;
+            *len = 4 * (int64_t)R.n_cigar;
+        }
+    } else if (k == 2) {
+        *src = R.rec + R.l_qname + 4 * (int64_t)R.n_cigar;
+        *len = (l + 1) / 2 + l;
+    } else if (k < 3 + LFQ_BAM_MAX_KEEP) {
+        const LfqBamPlan *P = A.plan + j;
+        const int i = k - 3;
+        if (i < P->n_keep) {
+            *src = R.rec + P->keep_beg[i];
+            *len = P->keep_len[i];
+        } else {
+            *src = 0;
+            *len = 0;
+        }
+    } else {
+        const int f = (k - 3 - LFQ_BAM_MAX_KEEP) / 3, part = (k - 3 - LFQ_BAM_MAX_KEEP) % 3;
+        *src = 0;
+        if (!((A.plan[j].append >> f) & 1u)) {
+            *len = 0;
+        } else if (part == 1) {
+            *base = f == 0 ? A.lb : f == 1 ? A.ai : f == 2 ? A.ad : f == 3 ? A.bi : A.bd;
+            *src = A.soff[j];
+            *len = l;
+        } else {
+            *base = nullptr;
+            *len = part == 0 ? 3 : 1;
+            if (part == 0) {            /* tag, then the type Z */
+                const uint32_t tag = f == 0 ? ('l' | 'b' << 8) : f == 1 ? ('a' | 'i' << 8) : f == 2 ? ('a' | 'd' << 8)
+                                     : f == 3 ? ('B' | 'I' << 8) : ('B' | 'D' << 8);
+                *cval = tag | ((uint32_t)'Z' << 16);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(LFQ_BAM_COPY_CHUNKS) void lfq_bam_copy_kernel(LfqBamEncArgs A)
+{
+    const int64_t b0 = ((int64_t)blockIdx.x * LFQ_BAM_COPY_CHUNKS + threadIdx.x) * 16;
+    if (b0 >= A.n_out) {
+        return;
+    }
+    /* the chunk's first record: among those of the workgroup's tile (the host wrote down where each tile begins) */
+    const int64_t r_lo = A.tile_rec[blockIdx.x], r_hi = blockIdx.x + 1 < gridDim.x ? A.tile_rec[blockIdx.x + 1] : A.n_reads - 1;
+    int64_t j = bam_read_of_base(A.out_off, r_lo, r_hi, b0);
+    const int total = (int)min((int64_t)16, A.n_out - b0);
+    LfqBamRead R = A.reads[j];
+    int64_t o = b0 - A.out_off[j];      /* where in record j the next byte comes from, and the segment that starts at seg0 */
+    int64_t seg0 = 0;
+    int k = 0, filled = 0;
+    LfqB16 acc;
+    acc.lo = acc.hi = 0;
+    while (filled < total) {
+        if (k == LFQ_BAM_N_SEGMENTS) {  /* on to the next record */
+            j++;
+            if (j >= A.n_reads) {
+                break;
+            }
+            R = A.reads[j];
+            k = 0;
+            seg0 = 0;
+            o = 0;
+            continue;
+        }
+        const uint8_t *base;
+        int64_t src, len;
+        uint32_t cval;
+        bam_enc_segment(A, j, R, k, &base, &src, &len, &cval);
+        if (o >= seg0 + len) {
+            seg0 += len;
+            k++;
+            continue;
+        }
+        const int64_t at = o - seg0;
+        const int cnt = (int)min(len - at, (int64_t)(total - filled));
+        LfqB16 v;
+        if (base) {
+            v = b16_fetch(base, src + at, cnt);
+        } else {
+            const LfqB16 m = b16_mask(cnt);
+            v.lo = (uint64_t)(cval >> ((int)at * 8)) & m.lo;
+            v.hi = 0;
+        }
+        v = b16_shl_bytes(v, filled);
+        acc.lo |= v.lo;
+        acc.hi |= v.hi;
+        filled += cnt;
+        o += cnt;
+    }
+    b16_store(A.out + b0, acc);
+}
+
+/* ---- host side --------------------------------------------------------------------------------------------------------------------- */
+struct LfqBamEncState {
+    uint8_t *d_out = nullptr;           /* offsets | tile table | the blob (grow-only) */
+    int64_t d_out_bytes = 0;
+    uint8_t *h_out = nullptr;           /* the blob on the host, pinned (grow-only) */
+    int64_t h_out_bytes = 0;
+    hipEvent_t ev[8] = {};              /* around the upload, the plan pass, the offsets' way down, the copy pass, the blob's way back */
+    std::vector<int64_t> data_off, src;
+    std::vector<int32_t> pos;
+    std::vector<uint32_t> n_cigar;
+    uint8_t none[16] = {};              /* `data` of an empty result */
+    lfq_bam_encoded result = {};
+    lfq_bam_encode_times times = {};
+};
+
+static void bam_enc_release(LfqBamEncState *E)
+{
+    if (E) {
+        if (E->d_out) (void)hipFree(E->d_out);
+        if (E->h_out) (void)hipHostFree(E->h_out);
+        for (hipEvent_t e : E->ev) {
+            if (e) (void)hipEventDestroy(e);
+        }
+        delete E;
+    }
+}
+
+static LfqBamEncState *bam_enc_state(lfq_ctx *c)
+{
+    LfqBamState *S = bam_state(c);
+    if (!S->enc) {
+        S->enc = new LfqBamEncState();
+    }
+    return S->enc;
+}
+
+int lfq_bam_encode_empty(lfq_ctx *c, const lfq_bam_encoded **out)
+{
+    LfqBamEncState *E = bam_enc_state(c);
+    memset(&E->times, 0, sizeof(E->times));
+    E->data_off.assign(1, 0);
+    E->src.assign(1, 0);
+    E->pos.assign(1, 0);
+    E->n_cigar.assign(1, 0);
+    E->result.n_reads = 0;
+    E->result.data = E->none;
+    E->result.data_off = E->data_off.data();
+    E->result.src = E->src.data();
+    E->result.pos = E->pos.data();
+    E->result.n_cigar = E->n_cigar.data();
+    *out = &E->result;
+    return LFQ_OK;
+}
+
+/* records down, plan pass, lengths back, offsets down, copy pass, blob back.  Blocks. */
+int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **out)
+{
+    LfqBamState *S = bam_state(c);
+    LfqBamEncState *E = bam_enc_state(c);
+    const int64_t n = in->n;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    for (hipEvent_t &e : E->ev) {
+        if (!e) {
+            LFQ_TRY_HIP(hipEventCreate(&e));
+        }
+    }
+    memset(&E->times, 0, sizeof(E->times));
+    E->times.n_reads = n;
+    E->times.n_in_bytes = in->data_bytes;
+    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
+    const int64_t o_reads = al(in->first_shift + in->data_bytes + 16), o_plan = o_reads + al(n * (int64_t)sizeof(LfqBamRead)),
+                  o_len = o_plan + al(n * (int64_t)sizeof(LfqBamPlan)), o_err = o_len + al(n * 8), total = o_err + 256;
+    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
+    const uint8_t *data = in->data;
+    if (!in->data_pinned) {
+        LFQ_TRY(bam_stage(c, S, &data, in->data_bytes));
+    }
+    LfqPin<int32_t> verdict(c, 4);
+    LFQ_PIN_OK(verdict);
+    LfqPin<int64_t> lens(c, (size_t)n);
+    LFQ_PIN_OK(lens);
+    hipStream_t st = c->stream;
+    LFQ_TRY_HIP(hipEventRecord(E->ev[0], st));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + in->first_shift, data, (size_t)in->data_bytes, hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_reads, in->reads, (size_t)n * sizeof(LfqBamRead), hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemsetAsync(S->d_buf + o_err, 0, 256, st));
+    LFQ_TRY_HIP(hipEventRecord(E->ev[1], st));
+    LfqBamEncArgs A;
+    memset(&A, 0, sizeof(A));
+    A.data = S->d_buf;
+    A.reads = (const LfqBamRead *)(S->d_buf + o_reads);
+    A.plan = (LfqBamPlan *)(S->d_buf + o_plan);
+    A.out_len = (int64_t *)(S->d_buf + o_len);
+    A.err = (int32_t *)(S->d_buf + o_err);
+    A.coff = in->d_coff; A.soff = in->d_soff; A.cig = in->d_cig; A.fl = in->d_fl;
+    A.lb = in->d_lb; A.ai = in->d_ai; A.ad = in->d_ad; A.bi = in->d_bi; A.bd = in->d_bd;
+    A.n_reads = n;
+    A.what = in->what;
+    A.uniform = in->uniform ? 1 : 0;
+    LFQ_TRY_HIP(hipEventRecord(E->ev[2], st));
+    hipLaunchKernelGGL(lfq_bam_plan_kernel, dim3((unsigned)((n + LFQ_BAM_PLAN_READS - 1) / LFQ_BAM_PLAN_READS)),
+                       dim3(LFQ_BAM_PLAN_READS), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY_HIP(hipEventRecord(E->ev[3], st));
+    E->times.n_launches += 1;
+    LFQ_TRY_HIP(hipMemcpyAsync(verdict.data(), A.err, 16, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(lens.data(), A.out_len, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    E->times.upload_ms = bam_ms(E->ev[0], E->ev[1]);
+    E->times.kernels_ms = bam_ms(E->ev[2], E->ev[3]);
+    if (verdict[0]) {
+        return LFQ_ERR_INVALID;
+    }
+    /* offsets in read-set order, and for every tile of the copy pass the record that holds its first byte */
+    const int64_t tile = (int64_t)LFQ_BAM_COPY_CHUNKS * 16;
+    E->data_off.resize((size_t)n + 1);
+    E->data_off[0] = 0;
+    for (int64_t j = 0; j < n; j++) {
+        E->data_off[(size_t)j + 1] = E->data_off[(size_t)j] + lens[(size_t)j];
+    }
+    const int64_t n_out = E->data_off[(size_t)n], n_tiles = (n_out + tile - 1) / tile;
+    LfqPin<int64_t> down(c, (size_t)(n + 1 + n_tiles));
+    LFQ_PIN_OK(down);
+    memcpy(down.data(), E->data_off.data(), (size_t)(n + 1) * 8);
+    for (int64_t t = 0, j = 0; t < n_tiles; t++) {
+        while (E->data_off[(size_t)j + 1] <= t * tile) {    /* (t * tile < n_out = data_off[n]: j stays below n) */
+            j++;
+        }
+        down[(size_t)(n + 1 + t)] = j;
+    }
+    const int64_t o_off = 0, o_tile = al((n + 1) * 8), o_blob = o_tile + al(n_tiles * 8), out_total = o_blob + al(n_out + 16);
+    LFQ_TRY(grow(&E->d_out, &E->d_out_bytes, out_total));
+    if (n_out + 16 > E->h_out_bytes) {
+        if (E->h_out) (void)hipHostFree(E->h_out);
+        E->h_out = nullptr;
+        E->h_out_bytes = 0;
+        const int64_t want = std::max<int64_t>(n_out + n_out / 4 + 16, 1 << 16);
+        if (hipHostMalloc((void **)&E->h_out, (size_t)want, hipHostMallocDefault) != hipSuccess) {
+            return LFQ_ERR_NOMEM;
+        }
+        E->h_out_bytes = want;
+    }
+    if (n_out > 0) {
+        A.out_off = (const int64_t *)(E->d_out + o_off);
+        A.tile_rec = (const int64_t *)(E->d_out + o_tile);
+        A.out = E->d_out + o_blob;
+        A.n_out = n_out;
+        LFQ_TRY_HIP(hipEventRecord(E->ev[4], st));
+        LFQ_TRY_HIP(hipMemcpyAsync(E->d_out + o_off, down.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+        LFQ_TRY_HIP(hipMemcpyAsync(E->d_out + o_tile, down.data() + n + 1, (size_t)n_tiles * 8, hipMemcpyHostToDevice, st));
+        LFQ_TRY_HIP(hipEventRecord(E->ev[5], st));
+        hipLaunchKernelGGL(lfq_bam_copy_kernel, dim3((unsigned)n_tiles), dim3(LFQ_BAM_COPY_CHUNKS), 0, st, A);
+        LFQ_TRY_HIP(hipGetLastError());
+        LFQ_TRY_HIP(hipEventRecord(E->ev[6], st));
+        E->times.n_launches += 1;
+        LFQ_TRY_HIP(hipMemcpyAsync(E->h_out, A.out, (size_t)n_out, hipMemcpyDeviceToHost, st));
+        LFQ_TRY_HIP(hipEventRecord(E->ev[7], st));
+        LFQ_TRY_HIP(hipStreamSynchronize(st));
+        E->times.upload_ms += bam_ms(E->ev[4], E->ev[5]);
+        E->times.kernels_ms += bam_ms(E->ev[5], E->ev[6]);
+        E->times.download_ms = bam_ms(E->ev[6], E->ev[7]);
+    }
+    E->times.n_out_bytes = n_out;
+    E->src.assign(in->src, in->src + n);
+    E->pos.assign(in->pos, in->pos + n);
+    E->n_cigar.assign(in->n_cigar, in->n_cigar + n);
+    E->result.n_reads = n;
+    E->result.data = E->h_out;
+    E->result.data_off = E->data_off.data();
+    E->result.src = E->src.data();
+    E->result.pos = E->pos.data();
+    E->result.n_cigar = E->n_cigar.data();
+    *out = &E->result;
+    return LFQ_OK;
+}
+
+extern "C" int lfq_last_bam_encode_times(lfq_ctx *c, lfq_bam_encode_times *t)
+{
+    if (!c || !t) {
+        return LFQ_ERR_INVALID;
+    }
+    *t = bam_enc_state(c)->times;
     return LFQ_OK;
 }

@@ -6,7 +6,7 @@
  *   lfq_api.hip        context, streams, the batch driver (layer 1), the call_snvs loop (layer 2), uniq, generator
  *   lfq_indel_api.hip  the indel tests (lfq_call_indel_tests_batch, lfq_call_indels_batch)
  *   lfq_readset.hip    the resident read set: upload, BAQ / IDAQ, source quality, both pileups
- *   lfq_bamrec.hip     BAM records decoded on the device: kernels and their launches (for lfq_readset.hip)
+ *   lfq_bamrec.hip     BAM records decoded and rewritten on the device: kernels and their launches (for lfq_readset.hip)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -413,7 +413,7 @@ struct lfq_ctx {
     int sb_pending;                  /* strand-bias precomputes of this context not finished yet (under lm) */
     struct { void *p; size_t cap; int used; } pin_pool[LFQ_PIN_SLOTS];   /* LfqPin: pinned host temporaries */
     struct LfqViterbiState *vit;     /* lfq_viterbi_batch: its result and device buffers (lfq_viterbi.hip; created on first use) */
-    struct LfqBamState *bam;         /* lfq_readset_create_from_bam: records, descriptors and timing (lfq_bamrec.hip; created on first use) */
+    struct LfqBamState *bam;         /* lfq_readset_create_from_bam / _encode_bam: records, descriptors, results and timing (lfq_bamrec.hip; created on first use) */
 };
 
 template <typename T>
@@ -500,6 +500,35 @@ int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_s
                 int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi, int *any_bd);
 int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, uint8_t *d_bd, uint8_t *h_seq, uint8_t *h_qual,
                   uint8_t *h_bi, uint8_t *h_bd);
+/* lfq_bamrec.hip, for lfq_readset_encode_bam (lfq_readset.hip): the records rewritten on the device.  One LfqBamRead per read of
+ * the read set, in its order; rec / end are offsets from data - first_shift, as for the decode */
+struct LfqBamRead {
+    int64_t rec, end;                   /* the read's record: its first byte (read_name) and one past its last */
+    int32_t l_qseq;
+    uint32_t n_cigar;                   /* the record's own */
+    uint16_t l_qname, flag;
+    uint32_t pad_;
+};
+struct LfqBamEncIn {
+    const uint8_t *data;
+    int64_t data_bytes;
+    int first_shift;
+    bool data_pinned;
+    const LfqBamRead *reads;            /* [n] */
+    int64_t n;
+    unsigned what;                      /* LFQ_BAM_* */
+    bool uniform;                       /* PUT_INDELQUAL: the read set's indel qualities are uniform ones */
+    /* the read set's device arrays; lb / ai / ad / bi / bd null where `what` does not ask for them */
+    const int64_t *d_coff, *d_soff;
+    const uint32_t *d_cig;
+    const uint8_t *d_fl, *d_lb, *d_ai, *d_ad, *d_bi, *d_bd;
+    /* [n] what the result hands out beside the blob (copied) */
+    const int64_t *src;
+    const int32_t *pos;
+    const uint32_t *n_cigar;
+};
+int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **out);
+int lfq_bam_encode_empty(lfq_ctx *c, const lfq_bam_encoded **out);
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

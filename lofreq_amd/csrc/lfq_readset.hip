@@ -3360,4 +3360,114 @@ int lfq_readset_fetch_bases(lfq_ctx *c, lfq_readset *rs, uint8_t *seq_out, uint8
     return LFQ_OK;
 }
 
+/* The inverse of lfq_readset_create_from_bam: the results of the read set's steps written into the bytes of the records the reads
+ * came from, by the two launches of the encode in lfq_bamrec.hip.  The host reads per READ only: the checks, one descriptor per
+ * read, pos and n_cigar of the result.  Blocks. */
+int lfq_readset_encode_bam(lfq_ctx *c, lfq_readset *rs, const lfq_bam_records *recs, const int64_t *src, unsigned what,
+                           const lfq_bam_encoded **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !rs || !recs || !out) {
+        return LFQ_ERR_INVALID;
+    }
+    const unsigned known = LFQ_BAM_PUT_ALIGNMENT | LFQ_BAM_DROP_ALN_TAGS | LFQ_BAM_PUT_LB | LFQ_BAM_PUT_IDAQ | LFQ_BAM_KEEP_EXISTING
+                           | LFQ_BAM_PUT_INDELQUAL;
+    if (what == 0 || (what & ~known) || ((what & LFQ_BAM_KEEP_EXISTING) && !(what & (LFQ_BAM_PUT_LB | LFQ_BAM_PUT_IDAQ)))) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = recs->n_reads;
+    if (n < 0 || (n > 0 && (!recs->data || !recs->data_off || !recs->pos || !recs->flag || !recs->mapq || !recs->l_qname
+                            || !recs->n_cigar || !recs->l_qseq))) {
+        return LFQ_ERR_INVALID;
+    }
+    for (int64_t r = 0; r < n; r++) {
+        const int64_t o0 = recs->data_off[r], o1 = recs->data_off[r + 1], l = recs->l_qseq[r];
+        if (o1 < o0 || o1 - o0 > INT32_MAX || l < 0
+            || o1 - o0 < (int64_t)recs->l_qname[r] + 4 * (int64_t)recs->n_cigar[r] + (l + 1) / 2 + l) {
+            return LFQ_ERR_INVALID;
+        }
+    }
+    if (rs->c != c || rs->n != n) {
+        return LFQ_ERR_INVALID;
+    }
+    if (src) {
+        std::vector<uint8_t> hit((size_t)n, 0);
+        for (int64_t j = 0; j < n; j++) {
+            if (src[j] < 0 || src[j] >= n || hit[(size_t)src[j]]) {
+                return LFQ_ERR_INVALID;
+            }
+            hit[(size_t)src[j]] = 1;
+        }
+    }
+    for (int64_t j = 0; j < n; j++) {
+        if (recs->l_qseq[src ? src[j] : j] != rs->seq_off[j + 1] - rs->seq_off[j]) {
+            return LFQ_ERR_INVALID;
+        }
+    }
+    if (((what & LFQ_BAM_PUT_LB) && !rs->has_lb) || ((what & LFQ_BAM_PUT_IDAQ) && !rs->has_idaq)
+        || ((what & LFQ_BAM_PUT_INDELQUAL) && !rs->idq_mode)) {
+        return LFQ_ERR_INVALID;
+    }
+    if (n == 0) {
+        return lfq_bam_encode_empty(c, out);
+    }
+    const int64_t first = recs->data_off[0];
+    const uint8_t *data = recs->data + first;
+    LfqBamEncIn in;
+    memset(&in, 0, sizeof(in));
+    in.data = data;
+    in.data_bytes = recs->data_off[n] - first;
+    in.first_shift = (int)((uintptr_t)data & 15);       /* the records keep the alignment they have in the caller's memory */
+    in.n = n;
+    in.what = what;
+    in.uniform = rs->idq_mode == LFQ_IDQ_UNIFORM;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    in.data_pinned = lfq_is_pinned(data);
+    LfqPin<LfqBamRead> reads(c, (size_t)n);
+    LFQ_PIN_OK(reads);
+    std::vector<int64_t> src_v((size_t)n);
+    std::vector<int32_t> pos_v((size_t)n);
+    std::vector<uint32_t> nc_v((size_t)n);
+    const bool put_aln = (what & LFQ_BAM_PUT_ALIGNMENT) != 0;
+    LfqBamRead *rd = reads.data();
+    lfq_for_reads(n, [&](int64_t j0, int64_t j1, int) {
+        for (int64_t j = j0; j < j1; j++) {
+            const int64_t s = src ? src[j] : j;
+            LfqBamRead &R = rd[j];
+            R.rec = in.first_shift + recs->data_off[s] - first;
+            R.end = in.first_shift + recs->data_off[s + 1] - first;
+            R.l_qseq = recs->l_qseq[s];
+            R.n_cigar = recs->n_cigar[s];
+            R.l_qname = recs->l_qname[s];
+            R.flag = recs->flag[s];
+            R.pad_ = 0;
+            src_v[(size_t)j] = s;
+            pos_v[(size_t)j] = put_aln ? rs->pos[j] : recs->pos[s];
+            nc_v[(size_t)j] = put_aln ? (uint32_t)(rs->cigar_off[j + 1] - rs->cigar_off[j]) : recs->n_cigar[s];
+        }
+    });
+    in.reads = rd;
+    in.src = src_v.data();
+    in.pos = pos_v.data();
+    in.n_cigar = nc_v.data();
+    /* what the kernels read of the read set is on the device and complete in the order of the context's stream */
+    LFQ_TRY(readset_upload_wait(rs));
+    if (rs->baq_pending) {
+        LFQ_TRY_HIP(hipStreamWaitEvent(c->stream, rs->ev_baq, 0));
+    }
+    if ((what & LFQ_BAM_PUT_INDELQUAL) && rs->ev_idq) {
+        LFQ_TRY_HIP(hipStreamWaitEvent(c->stream, rs->ev_idq, 0));
+    }
+    in.d_coff = (const int64_t *)rs->d_coff;
+    in.d_soff = (const int64_t *)rs->d_soff;
+    in.d_cig = (const uint32_t *)rs->d_cig;
+    in.d_fl = rs->d_fl;
+    in.d_lb = (what & LFQ_BAM_PUT_LB) ? rs->d_lb : nullptr;
+    in.d_ai = (what & LFQ_BAM_PUT_IDAQ) ? rs->d_ai : nullptr;
+    in.d_ad = (what & LFQ_BAM_PUT_IDAQ) ? rs->d_ad : nullptr;
+    in.d_bi = (what & LFQ_BAM_PUT_INDELQUAL) ? rs->d_bi : nullptr;
+    in.d_bd = (what & LFQ_BAM_PUT_INDELQUAL) ? rs->d_bd : nullptr;
+    return lfq_bam_encode(c, &in, out);
+}
+
 }  // extern "C"

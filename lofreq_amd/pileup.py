@@ -327,6 +327,13 @@ def last_bam_decode_times(caller):
     return {k: getattr(t, k) for k, _ in _lib.BamDecodeTimes._fields_}
 
 
+def last_bam_encode_times(caller):
+    """lfq_last_bam_encode_times -> dict(upload_ms, kernels_ms, download_ms, n_reads, n_in_bytes, n_out_bytes, n_launches)"""
+    t = _lib.BamEncodeTimes()
+    _lib.check(_lib.load().lfq_last_bam_encode_times(caller.h, C.byref(t)), "lfq_last_bam_encode_times")
+    return {k: getattr(t, k) for k, _ in _lib.BamEncodeTimes._fields_}
+
+
 def _format_grown(call, what):
     """a formatter whose text grows with the depth: ask for the length, then write"""
     n = call(None, 0)
@@ -489,6 +496,47 @@ class ReadSet:
         out = [np.zeros(max(nb, 1), np.uint8) for _ in range(4)] + [np.zeros(max(self.n, 1), np.uint8)]
         _lib.check(self.L.lfq_readset_fetch_bases(self.caller.h, self.h, *[o.ctypes.data for o in out]), "lfq_readset_fetch_bases")
         return tuple(o[:nb] for o in out[:4]) + (out[4][: self.n],)
+
+    def encode_bam(self, recs, src=None, what=_lib.LFQ_BAM_PUT_ALIGNMENT):
+        """lfq_readset_encode_bam: the results of this read set's steps written into the bytes of the BAM records its reads came
+        from, on the device.  recs: dict with the arrays from_bam_records takes (data, data_off, pos, flag, mapq, l_qname, n_cigar,
+        l_qseq) -- the ORIGINAL records; src[j]: the record of this set's read j (None: the identity; after viterbi() its order);
+        what: LFQ_BAM_* bits.  -> dict in the same layout, records in this set's read order: data, data_off, pos, n_cigar, src,
+        and flag / mapq / l_qname / l_qseq gathered through src (+ "ref" where recs has it) -- ready for from_bam_records"""
+        a = {k: np.ascontiguousarray(recs[k], dt) for k, dt in (
+            ("data", np.uint8), ("data_off", np.int64), ("pos", np.int32), ("flag", np.uint16), ("mapq", np.uint8),
+            ("l_qname", np.uint16), ("n_cigar", np.uint32), ("l_qseq", np.int32))}
+        n = len(a["pos"])
+        if len(a["data_off"]) != n + 1 or any(len(a[k]) != n for k in ("flag", "mapq", "l_qname", "n_cigar", "l_qseq")):
+            raise ValueError("encode_bam: data_off takes n + 1 entries, every other per-read array n")
+        if src is not None:
+            src = np.ascontiguousarray(src, np.int64)
+            if len(src) != n:
+                raise ValueError("encode_bam: src takes n entries")
+        rc = _lib.BamRecords()
+        rc.n_reads = n
+        for k in a:
+            setattr(rc, k, a[k].ctypes.data)
+        out = C.POINTER(_lib.BamEncoded)()
+        _lib.check(self.L.lfq_readset_encode_bam(self.caller.h, self.h, C.byref(rc), src.ctypes.data if src is not None else None,
+                                                 int(what), C.byref(out)), "lfq_readset_encode_bam")
+        e = out.contents
+        m = int(e.n_reads)
+
+        def arr(p, count, dt):
+            if count == 0 or not p:
+                return np.zeros(0, dt)
+            return np.frombuffer(C.string_at(p, count * np.dtype(dt).itemsize), dtype=dt).copy()
+
+        off = arr(e.data_off, m + 1, np.int64) if m else np.zeros(1, np.int64)
+        s = arr(e.src, m, np.int64)
+        res = {"data": arr(e.data, int(off[-1]), np.uint8), "data_off": off, "pos": arr(e.pos, m, np.int32),
+               "n_cigar": arr(e.n_cigar, m, np.uint32), "src": s}
+        for k in ("flag", "mapq", "l_qname", "l_qseq"):
+            res[k] = a[k][s]
+        if "ref" in recs:
+            res["ref"] = recs["ref"]
+        return res
 
     def close(self):
         if getattr(self, "h", None):

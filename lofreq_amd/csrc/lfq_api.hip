@@ -477,30 +477,22 @@ void lfq_destroy(lfq_ctx *c)
         if (c->priv_stream) (void)hipStreamDestroy(c->priv_stream);
         if (c->ev_up) (void)hipEventDestroy(c->ev_up);
         if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
+        free_pinned(&c->h_pin, &c->pin_bytes);
+        free_pinned(&c->h_pin2, &c->pin2_bytes);
+        free_pinned(&c->h_sum, &c->h_sum_bytes);
+        free_pinned(&c->h_pq, &c->h_pq_bytes);
         for (int i = 0; i < LFQ_PIN_SLOTS; i++) {
             if (c->pin_pool[i].p) (void)hipHostFree(c->pin_pool[i].p);
         }
-        if (c->h_pin2) (void)hipHostFree(c->h_pin2);
+        for (LfqEvPair *t : {&c->baq_t, &c->idq_t, &c->sites_t[0], &c->sites_t[1], &c->sum_t, &c->pq_t}) {
+            t->destroy();
+        }
         if (c->d_detlim) (void)hipFree(c->d_detlim);
         if (c->d_sites_in) (void)hipFree(c->d_sites_in);
         if (c->d_sites_out) (void)hipFree(c->d_sites_out);
-        for (int i = 0; i < 4; i++) {
-            if (c->ev_sites_t[i]) (void)hipEventDestroy(c->ev_sites_t[i]);
-        }
         if (c->d_sum) (void)hipFree(c->d_sum);
-        if (c->h_sum) (void)hipHostFree(c->h_sum);
         delete c->plp_sum;
-        if (c->ev_sum_t[0]) (void)hipEventDestroy(c->ev_sum_t[0]);
-        if (c->ev_sum_t[1]) (void)hipEventDestroy(c->ev_sum_t[1]);
         if (c->d_pq) (void)hipFree(c->d_pq);
-        if (c->h_pq) (void)hipHostFree(c->h_pq);
-        if (c->ev_pq_t[0]) (void)hipEventDestroy(c->ev_pq_t[0]);
-        if (c->ev_pq_t[1]) (void)hipEventDestroy(c->ev_pq_t[1]);
-        if (c->ev_baq_t[0]) (void)hipEventDestroy(c->ev_baq_t[0]);
-        if (c->ev_baq_t[1]) (void)hipEventDestroy(c->ev_baq_t[1]);
-        if (c->ev_idq_t[0]) (void)hipEventDestroy(c->ev_idq_t[0]);
-        if (c->ev_idq_t[1]) (void)hipEventDestroy(c->ev_idq_t[1]);
         if (c->d_baq_scr) (void)hipFree(c->d_baq_scr);
         if (c->d_baq_expect) (void)hipFree(c->d_baq_expect);
         if (c->d_baq_tmp8) (void)hipFree(c->d_baq_tmp8);

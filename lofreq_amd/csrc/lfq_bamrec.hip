@@ -387,10 +387,9 @@ int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_s
             LFQ_TRY_HIP(hipEventCreate(&e));
         }
     }
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t o_desc = al(first_shift + data_bytes + 16), o_bi = o_desc + al((3 * n + 1) * 8), o_bd = o_bi + al(n * 8),
-                  o_err = o_bd + al(n * 8), o_fl = o_err + 256, o_tile = o_fl + al(n),
-                  n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), total = o_tile + al(n_tiles * 8);
+    const int64_t o_desc = lfq_al(first_shift + data_bytes + 16), o_bi = o_desc + lfq_al((3 * n + 1) * 8), o_bd = o_bi + lfq_al(n * 8),
+                  o_err = o_bd + lfq_al(n * 8), o_fl = o_err + 256, o_tile = o_fl + lfq_al(n),
+                  n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), total = o_tile + lfq_al(n_tiles * 8);
     LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
     if (!data_pinned) {
         LFQ_TRY(bam_stage(c, S, &data, data_bytes));
@@ -857,9 +856,8 @@ int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **ou
     memset(&E->times, 0, sizeof(E->times));
     E->times.n_reads = n;
     E->times.n_in_bytes = in->data_bytes;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t o_reads = al(in->first_shift + in->data_bytes + 16), o_plan = o_reads + al(n * (int64_t)sizeof(LfqBamRead)),
-                  o_len = o_plan + al(n * (int64_t)sizeof(LfqBamPlan)), o_err = o_len + al(n * 8), total = o_err + 256;
+    const int64_t o_reads = lfq_al(in->first_shift + in->data_bytes + 16), o_plan = o_reads + lfq_al(n * (int64_t)sizeof(LfqBamRead)),
+                  o_len = o_plan + lfq_al(n * (int64_t)sizeof(LfqBamPlan)), o_err = o_len + lfq_al(n * 8), total = o_err + 256;
     LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
     const uint8_t *data = in->data;
     if (!in->data_pinned) {
@@ -882,7 +880,7 @@ int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **ou
     A.plan = (LfqBamPlan *)(S->d_buf + o_plan);
     A.out_len = (int64_t *)(S->d_buf + o_len);
     A.err = (int32_t *)(S->d_buf + o_err);
-    A.coff = in->d_coff; A.soff = in->d_soff; A.cig = in->d_cig; A.fl = in->d_fl;
+    A.coff = in->rd.cigar_off; A.soff = in->rd.seq_off; A.cig = in->rd.cigar; A.fl = in->d_fl;
     A.lb = in->d_lb; A.ai = in->d_ai; A.ad = in->d_ad; A.bi = in->d_bi; A.bd = in->d_bd;
     A.n_reads = n;
     A.what = in->what;
@@ -918,7 +916,7 @@ int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **ou
         }
         down[(size_t)(n + 1 + t)] = j;
     }
-    const int64_t o_off = 0, o_tile = al((n + 1) * 8), o_blob = o_tile + al(n_tiles * 8), out_total = o_blob + al(n_out + 16);
+    const int64_t o_off = 0, o_tile = lfq_al((n + 1) * 8), o_blob = o_tile + lfq_al(n_tiles * 8), out_total = o_blob + lfq_al(n_out + 16);
     LFQ_TRY(grow(&E->d_out, &E->d_out_bytes, out_total));
     if (n_out + 16 > E->h_out_bytes) {
         if (E->h_out) (void)hipHostFree(E->h_out);

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(64) void lfq_baq_kernel(LfqBaqArgs A, int64_t n_lau
                 y += oplen;
             }
         }
-        A.tag_flags[rid] = (uint8_t)((n_ins ? 1 : 0) | (n_del ? 2 : 0));
+        A.tagfl_out[rid] = (uint8_t)((n_ins ? 1 : 0) | (n_del ? 2 : 0));
     }
 
     /* ---- backward (:206-238), with the MAP step of a row (:254-281) as soon as the row exists ---- */
@@ -1144,7 +1144,7 @@ __global__ __launch_bounds__(64, LFQ_BAQ_WAVES) void lfq_baq_reg_kernel(LfqBaqAr
                 y += oplen;
             }
         }
-        A.tag_flags[rid] = (uint8_t)((n_ins ? 1 : 0) | (n_del ? 2 : 0));
+        A.tagfl_out[rid] = (uint8_t)((n_ins ? 1 : 0) | (n_del ? 2 : 0));
     }
 
 

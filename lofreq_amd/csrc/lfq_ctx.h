@@ -268,6 +268,40 @@ struct LfqSummaryOwned {
 
 #define LFQ_PIN_SLOTS 40
 
+/* the event pair around the kernels of a timed call, for its lfq_last_*_times getter: created on first use, kept until
+ * lfq_destroy.  ms() leaves *out alone before the first begin() and where the runtime has no time to give */
+struct LfqEvPair {
+    hipEvent_t ev[2];
+    int begin(hipStream_t st)
+    {
+        for (hipEvent_t &e : ev) {
+            if (!e && hipEventCreate(&e) != hipSuccess) {
+                return LFQ_ERR_HIP;
+            }
+        }
+        return hipEventRecord(ev[0], st) == hipSuccess ? (int)LFQ_OK : (int)LFQ_ERR_HIP;
+    }
+    int end(hipStream_t st) { return !ev[1] || hipEventRecord(ev[1], st) == hipSuccess ? (int)LFQ_OK : (int)LFQ_ERR_HIP; }
+    template <typename T> int ms(T *out) const        /* (the public structs hold float or double milliseconds) */
+    {
+        float t = 0.f;
+        if (ev[1] && hipEventSynchronize(ev[1]) != hipSuccess) {
+            return LFQ_ERR_HIP;
+        }
+        if (ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) {
+            *out = (T)t;
+        }
+        return LFQ_OK;
+    }
+    void destroy()
+    {
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+};
+
 struct lfq_ctx {
     int device;
     hipStream_t stream;
@@ -337,7 +371,7 @@ struct lfq_ctx {
     hipStream_t up_stream;           /* lfq_readset_create's uploads and the staging copies of host tracks (created on first use) */
     hipEvent_t ev_up;                /* end of the staging copies of a batch of host tracks */
     hipEvent_t ev_apply;             /* lfq_readset_pileup_snv: the column positions are final (created on first use) */
-    uint8_t *h_pin;                  /* pinned host staging of the BAQ geometry + launch order (grow-only) */
+    uint8_t *h_pin;                  /* pinned host staging of the BAQ geometry + launch order (grow-only: grow_pinned, as the three below) */
     int64_t pin_bytes;
     uint8_t *h_pin2;                 /* pinned landing area of the indel pileup's per-position counters (grow-only) */
     int64_t pin2_bytes;
@@ -350,10 +384,10 @@ struct lfq_ctx {
     int dense_counts;                /* lfq_set_dense_counts: 0 = a caller's dense array may keep stale entries for untested columns */
     int dense_strand;                /* lfq_set_dense_strand_counts: layer 1 / async layer 2 fill the strand fields of every dense entry */
     int lazy_forced;                 /* set by lfq_call_snvs_batch around its submit */
-    hipEvent_t ev_baq_t[2];          /* around the BAQ kernels of the last lfq_readset_baq / lfq_baq_batch call (timing; created on first use) */
+    LfqEvPair baq_t;                 /* around the BAQ kernels of the last lfq_readset_baq / lfq_baq_batch call */
     int32_t baq_launches;            /* kernel launches between them on the context's stream */
     int64_t baq_reads, baq_bases;    /* reads / bases of that call */
-    hipEvent_t ev_idq_t[2];          /* around the kernels of the last lfq_readset_indelqual / lfq_indelqual_batch call (created on first use) */
+    LfqEvPair idq_t;                 /* around the kernels of the last lfq_readset_indelqual / lfq_indelqual_batch call */
     lfq_indelqual_times idq_times;   /* launches, reads and bases of that call (ms_kernels: from the events, when asked for) */
     int batch_gate;                  /* lfq_set_batch_gate: what this context's next count kernel waits for (LFQ_GATE_*) */
     int lazy_now;                    /* this batch: strand counts only for the columns of the sparse output */
@@ -374,7 +408,7 @@ struct lfq_ctx {
      * not d_plp_in / d_plp_out: the region pileup's tracks stay as they are) */
     uint8_t *d_sites_in, *d_sites_out;
     int64_t sites_in_bytes, sites_out_bytes;
-    hipEvent_t ev_sites_t[4];        /* around the count pass, around the scatter pass (created on first use) */
+    LfqEvPair sites_t[2];            /* around the count pass, around the scatter pass */
     lfq_sites_times sites_times;     /* sites, observations and launches of the last call (the ms: from the events, when asked for) */
     int64_t plp_ncols;
     /* lfq_readset_plp_summary: column list, increment table and the kernel's output (grow-only); the host arrays handed out */
@@ -383,7 +417,7 @@ struct lfq_ctx {
     uint8_t *h_sum;                  /* pinned: what the kernel wrote (fw | rv | heads | tails | consensus letter | path), handed out as it lies */
     int64_t h_sum_bytes;
     struct LfqSummaryOwned *plp_sum;
-    hipEvent_t ev_sum_t[2];          /* around the summary kernel (created on first use) */
+    LfqEvPair sum_t;                 /* around the summary kernel */
     lfq_summary_times sum_times;     /* columns, ordered columns and launches of the last call (the ms: from the events, when asked for) */
     /* lfq_plp_quals_from_tracks: the uploaded slice of host tracks | the kernel's output (grow-only); its pinned copy, handed out */
     uint8_t *d_pq;
@@ -391,7 +425,7 @@ struct lfq_ctx {
     uint8_t *h_pq;                   /* pinned: nt_off | bq | baq | mq | sq as the kernel wrote them */
     int64_t h_pq_bytes;
     lfq_plp_quals plp_quals;         /* the struct handed out */
-    hipEvent_t ev_pq_t[2];           /* around the group kernel (created on first use) */
+    LfqEvPair pq_t;                  /* around the group kernel */
     lfq_plp_quals_times pq_times;    /* columns, observations and launches of the last call (the ms: from the events, when asked for) */
     int indel_all_columns;           /* lfq_set_indel_arrays_all_columns */
     /* BAQ scratch (lfq_baq_batch), kept between calls */
@@ -433,6 +467,30 @@ int grow(T **ptr, int64_t *cap, int64_t need)
     }
     *cap = n;
     return LFQ_OK;
+}
+
+/* ... and the same contract for a pinned host block (what a copy from the device lands in, or one to it starts from) */
+static inline int grow_pinned(uint8_t **ptr, int64_t *cap, int64_t need)
+{
+    if (need <= *cap && *ptr) {
+        return LFQ_OK;
+    }
+    if (*ptr) {
+        (void)hipHostFree(*ptr);
+        *ptr = nullptr;
+    }
+    if (hipHostMalloc((void **)ptr, (size_t)std::max<int64_t>(need, 16), hipHostMallocDefault) != hipSuccess) {
+        *cap = 0;
+        return LFQ_ERR_NOMEM;
+    }
+    *cap = std::max<int64_t>(need, 16);
+    return LFQ_OK;
+}
+static inline void free_pinned(uint8_t **ptr, int64_t *cap)
+{
+    if (*ptr) (void)hipHostFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
 }
 
 /* Host temporaries a DMA reads or writes come from a grow-only pool of pinned blocks owned by the context (lfq_api.hip) */
@@ -480,14 +538,9 @@ struct LfqPin {
 /* ---- internal functions that cross file boundaries (lfq_api.hip) ---- */
 int lfq_make_params(const lfq_conf *conf, const lfq_tracks *tr, LfqParams *P, bool indel_mode);
 void lfq_viterbi_release(lfq_ctx *c);      /* lfq_viterbi.hip: what lfq_destroy frees of lfq_ctx::vit */
-/* lfq_viterbi.hip, for lfq_readset_viterbi: the device arrays of a read set whose host arrays are the `reads` of the call */
-struct LfqVitResident {
-    const int64_t *d_seq_off, *d_cigar_off;
-    const uint32_t *d_cigar;
-    const uint8_t *d_seq, *d_qual, *d_ref;
-};
-/* lfq_viterbi_batch; with `res`, query, q2def and windows are gathered on the device instead of packed and uploaded */
-int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *reads, int def_qual, const LfqVitResident *res,
+/* lfq_viterbi_batch; with `res` (lfq_readset_viterbi: the device view of a read set whose host arrays are the `reads` of the call),
+ * query, q2def and windows are gathered on the device instead of packed and uploaded */
+int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *reads, int def_qual, const LfqReadsDev *res,
                     const lfq_viterbi_result **out);
 /* dst[k][new order] = src[k][old order] for up to four per-base arrays; returns when the kernel is done */
 int lfq_viterbi_permute(lfq_ctx *c, int64_t n_reads, int64_t n_bases, const int64_t *d_new_off, const int64_t *old_start,
@@ -518,9 +571,8 @@ struct LfqBamEncIn {
     int64_t n;
     unsigned what;                      /* LFQ_BAM_* */
     bool uniform;                       /* PUT_INDELQUAL: the read set's indel qualities are uniform ones */
-    /* the read set's device arrays; lb / ai / ad / bi / bd null where `what` does not ask for them */
-    const int64_t *d_coff, *d_soff;
-    const uint32_t *d_cig;
+    /* the read set's device arrays (of rd: offsets and CIGARs); lb / ai / ad / bi / bd null where `what` does not ask for them */
+    LfqReadsDev rd;
     const uint8_t *d_fl, *d_lb, *d_ai, *d_ad, *d_bi, *d_bd;
     /* [n] what the result hands out beside the blob (copied) */
     const int64_t *src;

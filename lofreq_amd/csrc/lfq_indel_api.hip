@@ -214,9 +214,8 @@ int lfq_call_indels_batch(lfq_ctx *c, lfq_conf *conf, const lfq_indel_columns *b
         uint8_t *d_trk = nullptr;
         if (dev_pack) {
             const int64_t nt_ = (int64_t)descs.size(), trk = (int64_t)((dev_obs + 15) / 16 * 16) + 32;
-            auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-            const int64_t o_desc = 0, o_off = o_desc + al(nt_ * (int64_t)sizeof(LfqIndelTestDesc)), o_ref = o_off + al((nt_ + 1) * 8),
-                          o_trk = o_ref + al(nt_ + 16), total = o_trk + 5 * trk;
+            const int64_t o_desc = 0, o_off = o_desc + lfq_al(nt_ * (int64_t)sizeof(LfqIndelTestDesc)), o_ref = o_off + lfq_al((nt_ + 1) * 8),
+                          o_trk = o_ref + lfq_al(nt_ + 16), total = o_trk + 5 * trk;
             LFQ_TRY(grow(&c->d_tmp[4], &c->tmp_bytes[4], total));
             d_trk = c->d_tmp[4];
             /* descriptors, offsets and reference bytes in one pinned block (laid out as on the device), one copy */

@@ -155,8 +155,8 @@ __global__ __launch_bounds__(256) void lfq_idq_fill_kernel(LfqIdqArgs A)
     }
     if (A.tab == nullptr) {                     /* uniform: ENCODE_Q(ins_qual + 33) / ENCODE_Q(del_qual + 33) in every byte */
         const uint32_t wi = A.ins_byte * 0x01010101u, wd = A.del_byte * 0x01010101u;
-        *(uint4 *)(A.bi + b0) = make_uint4(wi, wi, wi, wi);
-        *(uint4 *)(A.bd + b0) = make_uint4(wd, wd, wd, wd);
+        *(uint4 *)(A.bi_out + b0) = make_uint4(wi, wi, wi, wi);
+        *(uint4 *)(A.bd_out + b0) = make_uint4(wd, wd, wd, wd);
         return;
     }
     /* the read of byte b0: the last r with seq_off[r] <= b0 (reads without bases in front of it are passed over) */
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void lfq_idq_fill_kernel(LfqIdqArgs A)
         }
         out[i >> 2] |= v << (8 * (i & 3));
     }
-    *(uint4 *)(A.bi + b0) = make_uint4(out[0], out[1], out[2], out[3]);       /* (BD is the same array: see the head of the file) */
+    *(uint4 *)(A.bi_out + b0) = make_uint4(out[0], out[1], out[2], out[3]);       /* (BD is the same array: see the head of the file) */
 }
 
 int lfq_launch_idq_table(const uint8_t *ref, int64_t ref_len, int64_t tab_begin, int64_t tab_end, uint8_t *tab, void *stream)

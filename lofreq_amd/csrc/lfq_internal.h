@@ -252,6 +252,36 @@ unsigned lfq_cpu_budget(void);
 /* tuples: n x {ref_fw, ref_rv, alt_fw, alt_rv}; all-zero tuples are skipped. */
 void lfq_sb_precompute(const int32_t *tuples, int64_t n);
 
+/* byte offsets of the sub-arrays of one device (or pinned) block: every one starts on a 256-byte boundary */
+static inline int64_t lfq_al(int64_t b)
+{
+    return (b + 255) / 256 * 256;
+}
+
+/* ---- the device view of a resident read set (lfq_readset.hip: readset_view / readset_pileup_view) -----------------------
+ * What a kernel may read of the reads.  Every argument struct of a read-set step derives from it and adds its own fields; the
+ * host fills it in one place, where the rules of the optional arrays are decided.  (The order of the first ten fields is the one
+ * the pileup kernels' argument block always had: moving them changes how many scalar registers those kernels spill.) */
+struct LfqReadsDev {
+    int64_t n_reads;
+    const int32_t *pos;                   /* [n] bam1_core_t.pos */
+    const int64_t *cigar_off, *seq_off;   /* [n + 1] */
+    const uint32_t *cigar;
+    const uint8_t *seq, *qual;            /* 0..4 (5..15: LFQ_SEQ_LETTERS) / phred */
+    const uint8_t *baq;                   /* lb tag bytes (BAQ + 33) or null */
+    const uint8_t *mapq, *reverse;        /* [n] */
+    const uint8_t *ref;                   /* the contig, ASCII */
+    int64_t ref_len;
+    const uint8_t *sq;                    /* [n] per-read source quality byte or null */
+    const uint8_t *bi, *bd;               /* per base tag bytes (quality + 33) or null */
+    const uint8_t *tag_flags;             /* [n] bit 0: read has BI, bit 1: BD; null = wherever the array exists */
+    const int32_t *pmax_end;              /* [n] sorted reads: max over reads 0..r of the end coordinate (exclusive); null = unsorted
+                                           * input (selects the read-major kernels) */
+    const int32_t *read_idx;              /* [n] -d cap (lfq_set_max_depth): read r of the pileup is input read read_idx[r]; null =
+                                           * identity.  n_reads, pos and pmax_end are then those of the kept reads, every other
+                                           * per-read field is read through read_idx */
+};
+
 /* ---- BAQ (lfq_baq.hip) ----------------------------------------------------------------------------------- */
 struct LfqBaqGeom {            /* 12 bytes per read, built on the host from the CIGAR (bam_md_ext.c:312-380) and uploaded */
     int32_t xb, l_ref;         /* reference window [xb, xb + l_ref) */
@@ -266,20 +296,13 @@ struct LfqBaqRead {            /* what a kernel works with: the geometry + the r
     int64_t cigar_off;
 };
 
-struct LfqBaqArgs {
+struct LfqBaqArgs : LfqReadsDev {
     const LfqBaqGeom *geom;    /* [n] */
-    const int32_t *pos;        /* [n] */
-    const int64_t *cigar_off;  /* [n+1] */
-    const int64_t *seq_off;    /* [n+1] */
-    const uint32_t *cigar;
-    const uint8_t *seq, *qual; /* 0..4 / phred */
-    const uint8_t *ref;        /* contig, ASCII */
     uint8_t *lb_out;           /* [seq_off[n]] */
     double *scratch;           /* per wavefront: F[rows][W][64], B[2][W][64], S[rows + 2][64], 1/S[rows + 2][64] */
     int32_t *expect;           /* per wavefront: [rows][64] expected reference offset of a matched base, INT32_MIN otherwise */
     uint8_t *tmp8;             /* per wavefront: [2][rows][64] running maxima of the extended BAQ */
     const float *qual2prob;    /* [256] pow(10, -q/10.) as float, computed on the host (kprobaln_ext.c:121-123) */
-    int64_t n_reads;
     int32_t rows, W;           /* scratch geometry: rows >= max l_qseq + 1, W >= max (2 bw + 1) * 3 + 6 */
     int32_t baq_extended;
     float par_d, par_e;        /* kpa_ext_par_t.d / .e (kprobaln_ext.c:48-51): gap open, gap extension */
@@ -289,7 +312,7 @@ struct LfqBaqArgs {
     int32_t lds_rows;          /* longest narrow-band read + 1: rows of the per-row scalars the register kernel keeps in LDS */
     /* indel alignment qualities (idaq, bam_md_ext.c:73-248); all null / 0 = not requested */
     uint8_t *ai_out, *ad_out;  /* [seq_off[n]] bytes of the ai / ad tags ('~' = nothing) */
-    uint8_t *tag_flags;        /* [n] bit 0: the read gets an ai tag, bit 1: an ad tag */
+    uint8_t *tagfl_out;        /* [n] bit 0: the read gets an ai tag, bit 1: an ad tag */
     int32_t *itab;             /* per wavefront: [LFQ_BAQ_MAX_INDELS][4][64] kept indels: type|qpos, k0, rep, term offset */
     double *terms;             /* per wavefront: [LFQ_BAQ_MAX_TERMS][64] posterior terms, summed in the reference's order */
     uint8_t *nflag;            /* per wavefront of the launch: it meets an N (lfq_baq_nflag_kernel); null = one instantiation for all */
@@ -306,38 +329,20 @@ struct LfqBaqArgs {
 int lfq_launch_baq(const LfqBaqArgs &a, int64_t n_launch, int lds, void *stream, int nmode = 0);
 
 /* ---- device-side pileup (lfq_pileup.hip) ------------------------------------------------------------------ */
-struct LfqPileupArgs {
-    int64_t n_reads;
-    const int32_t *pos;
-    const int64_t *cigar_off, *seq_off;
-    const uint32_t *cigar;
-    const uint8_t *seq, *qual, *baq;      /* baq: lb tag bytes (BAQ + 33) or null */
-    const uint8_t *mapq, *reverse;        /* [n] */
+struct LfqPileupArgs : LfqReadsDev {
     int64_t begin, width;                 /* region [begin, begin + width) */
     int32_t min_plp_bq;
     int32_t *cov, *nb, *cursor;           /* [width] per reference position */
     const int32_t *col_index;             /* [width] position -> column (covered positions only) */
     const uint64_t *col_off;              /* [ncols + 1] */
     uint8_t *t_nt, *t_bq, *t_baq, *t_mq;  /* packed tracks */
-    const uint8_t *sq;                    /* [n] per-read source quality byte or null */
     uint8_t *t_sq;
-    const int32_t *pmax_end;              /* [n] sorted reads: max over reads 0..r of the end coordinate (exclusive); null = unsorted input */
-    const int32_t *read_idx;              /* [n] -d cap (lfq_set_max_depth): read r of the pileup is input read read_idx[r]; null =
-                                           * identity.  n_reads, pos and pmax_end are then those of the kept reads, every other
-                                           * per-read field is read through read_idx */
 };
 int lfq_launch_pileup_count(const LfqPileupArgs &a, void *stream);
 int lfq_launch_pileup_columns(const LfqPileupArgs &a, int scatter, void *stream);
 
 /* the indel fields of compile_plp_col (plp.c:1019-1192), dense part on the device */
-struct LfqPlpIndelArgs {
-    int64_t n_reads;
-    const int32_t *pos;
-    const int64_t *cigar_off, *seq_off;
-    const uint32_t *cigar;
-    const uint8_t *bi, *bd;               /* per base tag bytes (quality + 33) or null */
-    const uint8_t *tag_flags;             /* [n] bit 0: read has BI, bit 1: BD; null = wherever the array exists */
-    const uint8_t *mapq, *reverse;        /* [n] */
+struct LfqPlpIndelArgs : LfqReadsDev {     /* pmax_end selects the column-major kernel */
     int64_t begin, width;
     int32_t min_plp_idq;
     /* per reference position of the region */
@@ -347,22 +352,12 @@ struct LfqPlpIndelArgs {
     const int64_t *ne_off[2];             /* [width] start of the position's slice per side, -1 = not wanted */
     int32_t *cursor[2];                   /* [width] */
     int16_t *ne_q[2], *ne_mq[2];
-    const int32_t *pmax_end;              /* sorted reads: see LfqPileupArgs; selects the column-major kernel */
-    const int32_t *read_idx;              /* kept reads under a -d cap: see LfqPileupArgs */
 };
 int lfq_launch_plp_indel(const LfqPlpIndelArgs &a, int scatter, void *stream);
 int lfq_launch_plp_indel_columns(const LfqPlpIndelArgs &a, int scatter, void *stream);
 /* the pileup at a LIST of positions (lfq_readset_pileup_sites / lfq_readset_uniq): position-sorted reads only, one wavefront
  * per site, column i = site i.  Count pass: counts + win; scatter pass: the kept bases to col_off[i] + rank */
-struct LfqSitesArgs {
-    int64_t n_reads;
-    const int32_t *pos, *pmax_end;        /* [n] see LfqPileupArgs */
-    const int64_t *cigar_off, *seq_off;
-    const uint32_t *cigar;
-    const uint8_t *seq, *qual, *baq;      /* baq: lb tag bytes or null */
-    const uint8_t *mapq, *reverse, *sq;   /* [n]; sq: source quality byte or null */
-    const uint8_t *ref;                   /* the contig (deletion keys) */
-    int64_t ref_len;
+struct LfqSitesArgs : LfqReadsDev {        /* ref: the deletion keys */
     int64_t n_sites;
     const int64_t *site_pos;              /* [n_sites] */
     int32_t min_plp_bq;
@@ -377,12 +372,7 @@ struct LfqSitesArgs {
 };
 int lfq_launch_pileup_sites(const LfqSitesArgs &a, int scatter, void *stream);
 /* the header line of plp_summary (lfq_readset_plp_summary): position-sorted reads only, one wavefront per column */
-struct LfqSummaryArgs {
-    int64_t n_reads;
-    const int32_t *pos, *pmax_end, *read_idx;   /* see LfqPileupArgs (read_idx: the kept reads of a -d cap, or null) */
-    const int64_t *cigar_off, *seq_off;
-    const uint32_t *cigar;
-    const uint8_t *seq, *qual, *reverse;
+struct LfqSummaryArgs : LfqReadsDev {
     int64_t n_cols;
     const int64_t *col_pos;               /* [n_cols] the covered positions of the region */
     int32_t min_plp_bq;
@@ -403,7 +393,7 @@ struct LfqPlpGroupArgs {
     int64_t *nt_off;                          /* [5 * n_cols + 1] group offsets, relative to col_off[0] */
 };
 int lfq_launch_plp_group(const LfqPlpGroupArgs &a, void *stream);
-/* the kept reads of a -d cap as the pileup kernels take them (read_idx / pos / pmax_end of LfqPileupArgs): keep[r] != 0 for a
+/* the kept reads of a -d cap as the pileup kernels take them (read_idx / pos / pmax_end of LfqReadsDev): keep[r] != 0 for a
  * kept read; kept_idx / kept_pos / kept_pmax get one entry per kept read.  scratch: lfq_keep_compact_scratch(n) bytes, whose
  * first n int32 the caller fills with the reads' exclusive ends (computed on the host with the keep decision) */
 int64_t lfq_keep_compact_scratch(int64_t n);
@@ -411,18 +401,15 @@ int lfq_launch_keep_compact(const uint8_t *keep, const int32_t *pos, int64_t n, 
                             int32_t *kept_pos, int32_t *kept_pmax, void *stream);
 /* `lofreq indelqual` (lfq_indelqual.hip).  Table: one Dindel byte per reference position of [tab_begin, tab_end), tab_begin a
  * multiple of 16 and tab_end <= ref_len; the kernel stores whole 16-byte words, so `tab` holds the length rounded up to 16.
- * Fill: bi / bd are 16-byte aligned and hold n_bases rounded up to 16; tab == null selects the uniform fill of ins_byte /
+ * Fill: bi_out / bd_out are 16-byte aligned and hold n_bases rounded up to 16; tab == null selects the uniform fill of ins_byte /
  * del_byte, otherwise the Dindel string goes to bi alone (BD is the same string: the caller lets both pointers name one array).
  * The CIGARs were checked on the host: only M I D S H = X, query length = the seq_off span. */
-struct LfqIdqArgs {
-    int64_t n_reads, n_bases;
-    const int32_t *pos;
-    const int64_t *cigar_off, *seq_off;
-    const uint32_t *cigar;
+struct LfqIdqArgs : LfqReadsDev {
+    int64_t n_bases;
     const uint8_t *tab;
     int64_t tab_begin, tab_end;
     uint32_t ins_byte, del_byte;
-    uint8_t *bi, *bd;
+    uint8_t *bi_out, *bd_out;
 };
 int lfq_launch_idq_table(const uint8_t *ref, int64_t ref_len, int64_t tab_begin, int64_t tab_end, uint8_t *tab, void *stream);
 int lfq_launch_idq_fill(const LfqIdqArgs &a, void *stream);
@@ -468,14 +455,7 @@ int lfq_launch_indel_pack(const LfqIndelPackArgs &a, void *stream);
 #define LFQ_SRCQ_NA 0               /* count_cigar_ops found nothing: source_qual returns -1 */
 #define LFQ_SRCQ_PERFECT 1          /* at most one non-match: PROB_TO_PHREDQUAL(LDBL_MIN) */
 #define LFQ_SRCQ_VALUE 2            /* prob[r] = P(X = K - 1) of the row poissbin stopped at */
-struct LfqSrcqArgs {
-    int64_t n_reads;
-    const int32_t *pos;
-    const int64_t *cigar_off, *seq_off;
-    const uint32_t *cigar;
-    const uint8_t *seq, *qual;
-    const char *ref;
-    int64_t ref_len;
+struct LfqSrcqArgs : LfqReadsDev {
     const uint8_t *ign;                 /* [ref_len] or null */
     int32_t nonmatch_qual, min_bq;
     double *scratch;                    /* 2 * scratch_cells doubles per wavefront of the launch, or null */

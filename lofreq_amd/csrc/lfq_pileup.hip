@@ -1869,12 +1869,11 @@ int lfq_launch_plp_compact_apply(const int32_t *cov, const int32_t *nb, int64_t 
 #define LFQ_KC_ITEMS 16
 #define LFQ_KC_TILE (LFQ_KC_THREADS * LFQ_KC_ITEMS)
 
-static inline int64_t lfq_kc_al(int64_t b) { return (b + 255) / 256 * 256; }
 
 int64_t lfq_keep_compact_scratch(int64_t n)
 {
     const int64_t ntiles = (n + LFQ_KC_TILE - 1) / LFQ_KC_TILE;
-    return lfq_kc_al(n * 4) + lfq_kc_al(ntiles * 4) + lfq_kc_al(ntiles * 4);
+    return lfq_al(n * 4) + lfq_al(ntiles * 4) + lfq_al(ntiles * 4);
 }
 
 /* inclusive scan of (count, max) over the threads of the block */
@@ -1990,8 +1989,8 @@ int lfq_launch_keep_compact(const uint8_t *keep, const int32_t *pos, int64_t n, 
     const int64_t ntiles = (n + LFQ_KC_TILE - 1) / LFQ_KC_TILE;
     uint8_t *sc = (uint8_t *)scratch;
     const int32_t *ends = (const int32_t *)sc;
-    int32_t *tile_n = (int32_t *)(sc + lfq_kc_al(n * 4));
-    int32_t *tile_m = (int32_t *)(sc + lfq_kc_al(n * 4) + lfq_kc_al(ntiles * 4));
+    int32_t *tile_n = (int32_t *)(sc + lfq_al(n * 4));
+    int32_t *tile_m = (int32_t *)(sc + lfq_al(n * 4) + lfq_al(ntiles * 4));
     hipLaunchKernelGGL(lfq_keep_tiles_kernel, dim3((unsigned)ntiles), dim3(LFQ_KC_THREADS), 0, (hipStream_t)stream, keep, ends, n,
                        tile_n, tile_m);
     hipLaunchKernelGGL(lfq_keep_sums_kernel, dim3(1), dim3(LFQ_KC_THREADS), 0, (hipStream_t)stream, ntiles, tile_n, tile_m);

@@ -109,7 +109,8 @@ struct lfq_readset {
     hipEvent_t ev_baq;
     bool baq_pending, baq_idaq;
     int32_t *d_pmax;                    /* position-sorted reads: running maximum of the end coordinates (lazily) */
-    int pmax_state;                     /* 0 unknown, 1 sorted (d_pmax valid), 2 unsorted */
+    int pmax_state;                     /* 0 unknown, 1 sorted (d_pmax valid), 2 unsorted, LFQ_ERR_NOMEM / LFQ_ERR_HIP: sorted, but d_pmax
+                                         * could not be made */
     /* -d cap (lfq_set_max_depth): the reads both pileups take, decided once per cap value (readset_keep) */
     bool keep_valid;                    /* a decision for the cap keep_for has been made; keep_rc is its result */
     int64_t keep_for;
@@ -323,9 +324,8 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
         *out = rs;
         return LFQ_OK;
     }
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     int64_t off = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = off; off += al(bytes); return o; };
+    auto take = [&](int64_t bytes) { const int64_t o = off; off += lfq_al(bytes); return o; };
     /* per-base arrays only where there is something to put: device allocations of this size are not free.  The
      * outputs of lfq_readset_baq (lb, ai, ad) get their own allocation when that step runs. */
     const int64_t o_pos = take(n * 4), o_coff = take((n + 1) * 8), o_soff = take((n + 1) * 8), o_cig = take(rs->n_cig * 4),
@@ -504,15 +504,31 @@ int lfq_readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_
     return readset_create(c, rd, tg, out);
 }
 
+/* Reads that are not position-sorted: the column-major kernels cannot take them (no window to search), the read-major ones hand
+ * a column's observations out in the order their threads get there (an atomic cursor), so that the last bits of a p-value can
+ * differ from run to run.  The reference cannot take such input at all (bam_mplp_auto needs a coordinate-sorted file,
+ * plp.c:1406-1447): refused unless the caller asked for it (lfq_set_pileup_unsorted; the tuning build's LFQ_PILEUP_ATOMIC sends
+ * even sorted reads that way, for the tests that hold the two kernel families against each other). */
+static bool readset_unsorted_ok(const lfq_ctx *c)
+{
+    return c->plp_unsorted_ok || lfq_knobs().pileup_atomic;
+}
+
 /* position-sorted reads (what mpileup requires) take the column-major pileup kernels, which find the reads that can
- * overlap a position by binary search: they need the running maximum of the end coordinates.  -> device array or null */
-static const int32_t *readset_pmax(lfq_ctx *c, lfq_readset *rs, hipStream_t st)
+ * overlap a position by binary search: they need the running maximum of the end coordinates, rs->d_pmax (made on the first
+ * call, its upload waited for on `st`; null: the reads are not sorted).  -> LFQ_ERR_INVALID for unsorted reads, unless the entry
+ * can take them at all (unsorted_may: the two region pileups, which have read-major kernels) and the caller asked for it */
+static int readset_pmax(lfq_ctx *c, lfq_readset *rs, hipStream_t st, bool unsorted_may)
 {
     if (rs->pmax_state == 0) {
         rs->pmax_state = 2;
         const int64_t n = rs->n;
         LfqPin<int32_t> pmax(c, (size_t)std::max<int64_t>(n, 1));
-        if (!lfq_knobs().pileup_atomic && n > 0 && pmax.ok()) {
+        const bool wanted = !lfq_knobs().pileup_atomic && n > 0;
+        if (wanted && !pmax.ok()) {
+            rs->pmax_state = LFQ_ERR_NOMEM;
+        }
+        if (wanted && pmax.ok()) {
             /* two passes split over a few threads: end coordinate and running maximum inside a part (and whether the
              * part is sorted), then the maximum of the parts before it */
             int32_t part_max[LFQ_HOST_PARTS];
@@ -562,23 +578,19 @@ static const int32_t *readset_pmax(lfq_ctx *c, lfq_readset *rs, hipStream_t st)
                     && hipStreamSynchronize(st) == hipSuccess) {
                     rs->pmax_state = 1;
                 } else if (rs->d_pmax) {
+                    rs->pmax_state = LFQ_ERR_HIP;
                     rs_cache_give(c, LFQ_RSC_PMAX, rs->d_pmax, rs->cap[LFQ_RSC_PMAX]);
                     rs->d_pmax = nullptr;
+                } else {
+                    rs->pmax_state = LFQ_ERR_NOMEM;
                 }
             }
         }
     }
-    return rs->pmax_state == 1 ? rs->d_pmax : nullptr;
-}
-
-/* Reads that are not position-sorted: the column-major kernels cannot take them (no window to search), the read-major ones hand
- * a column's observations out in the order their threads get there (an atomic cursor), so that the last bits of a p-value can
- * differ from run to run.  The reference cannot take such input at all (bam_mplp_auto needs a coordinate-sorted file,
- * plp.c:1406-1447): refused unless the caller asked for it (lfq_set_pileup_unsorted; the tuning build's LFQ_PILEUP_ATOMIC sends
- * even sorted reads that way, for the tests that hold the two kernel families against each other). */
-static bool readset_unsorted_ok(const lfq_ctx *c, const lfq_readset *rs)
-{
-    return rs->n == 0 || c->plp_unsorted_ok || lfq_knobs().pileup_atomic;
+    if (rs->pmax_state < 0) {
+        return rs->pmax_state;
+    }
+    return rs->d_pmax || rs->n == 0 || (unsorted_may && readset_unsorted_ok(c)) ? (int)LFQ_OK : (int)LFQ_ERR_INVALID;
 }
 
 /* ---- -d / --max-depth (lfq_set_max_depth) --------------------------------------------------------------------
@@ -721,8 +733,7 @@ static int readset_keep_device(lfq_ctx *c, lfq_readset *rs, hipStream_t st, cons
         return LFQ_OK;
     }
     const int64_t n = rs->n;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t o_idx = al(n), o_pos = o_idx + al(n * 4), o_pmax = o_pos + al(n * 4), o_scr = o_pmax + al(n * 4),
+    const int64_t o_idx = lfq_al(n), o_pos = o_idx + lfq_al(n * 4), o_pmax = o_pos + lfq_al(n * 4), o_scr = o_pmax + lfq_al(n * 4),
                   total = o_scr + lfq_keep_compact_scratch(n);
     if (!rs->keep_dev_valid || rs->keep_dev_for != c->plp_max_depth) {
         if (!rs->d_keep || rs->cap[LFQ_RSC_KEEP] < (size_t)total) {
@@ -752,6 +763,51 @@ static int readset_keep_device(lfq_ctx *c, lfq_readset *rs, hipStream_t st, cons
     *kept_idx = (const int32_t *)(rs->d_keep + o_idx);
     *kept_pos = (const int32_t *)(rs->d_keep + o_pos);
     *kept_pmax = (const int32_t *)(rs->d_keep + o_pmax);
+    return LFQ_OK;
+}
+
+/* ---- the device view of the reads (LfqReadsDev, lfq_internal.h) ---------------------------------------------------------------
+ * What every read-set step hands its kernels, filled here and nowhere else.  An array the read set does not have (yet) is null:
+ * lb before lfq_readset_baq, the source-quality byte before lfq_readset_source_qual, BI / BD that neither the caller nor
+ * lfq_readset_indelqual gave; after lfq_readset_indelqual every read has both tags, so no flags are consulted. */
+static void readset_view(const lfq_readset *rs, LfqReadsDev *v)
+{
+    v->n_reads = rs->n;
+    v->pos = (const int32_t *)rs->d_pos;
+    v->cigar_off = (const int64_t *)rs->d_coff;
+    v->seq_off = (const int64_t *)rs->d_soff;
+    v->cigar = (const uint32_t *)rs->d_cig;
+    v->seq = rs->d_seq;
+    v->qual = rs->d_qual;
+    v->mapq = rs->d_mapq;
+    v->reverse = rs->d_rev;
+    v->ref = rs->d_ref;
+    v->ref_len = rs->ref_len;
+    v->baq = rs->has_lb ? rs->d_lb : nullptr;
+    v->sq = rs->has_sqb ? rs->d_sqb : nullptr;
+    v->bi = rs->has_bi ? rs->d_bi : nullptr;
+    v->bd = rs->has_bd ? rs->d_bd : nullptr;
+    v->tag_flags = rs->idq_mode ? nullptr : rs->d_fl;
+    v->pmax_end = nullptr;
+    v->read_idx = nullptr;
+}
+
+/* ... for a pileup entry: sorted or refused (readset_pmax), then the -d cap -- the kernels walk the kept reads only, one decision
+ * per read set and cap value, so that the column lists of the pileups agree.  Queues on `st` what readset_pmax and
+ * readset_keep_device queue, in that order. */
+static int readset_pileup_view(lfq_ctx *c, lfq_readset *rs, hipStream_t st, bool unsorted_may, LfqReadsDev *v)
+{
+    readset_view(rs, v);
+    LFQ_TRY(readset_pmax(c, rs, st, unsorted_may));
+    v->pmax_end = rs->d_pmax;
+    const int32_t *k_idx, *k_pos, *k_pmax;
+    LFQ_TRY(readset_keep_device(c, rs, st, &k_idx, &k_pos, &k_pmax));
+    if (k_idx) {                            /* (null: the cap drops nothing, or there is none) */
+        v->n_reads = rs->n_kept;
+        v->read_idx = k_idx;
+        v->pos = k_pos;
+        v->pmax_end = k_pmax;
+    }
     return LFQ_OK;
 }
 
@@ -857,14 +913,8 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     /* geometry of every read: alignment window and band width (bam_md_ext.c:312-380, :396-399) */
     /* (pinned, grow-only host buffers: 28 bytes per read are written once by the threads below and go out by DMA; a
      * std::vector would zero 56 MB for 2 M reads first and be copied through a staging buffer afterwards) */
-    const int64_t h_bytes = (n * (int64_t)sizeof(LfqBaqGeom) + 255) / 256 * 256, ord_bytes = (n * 4 + 255) / 256 * 256;
-    if (h_bytes + ord_bytes > c->pin_bytes) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr;
-        c->pin_bytes = 0;
-        LFQ_TRY_HIP(hipHostMalloc((void **)&c->h_pin, (size_t)(h_bytes + ord_bytes), hipHostMallocDefault));
-        c->pin_bytes = h_bytes + ord_bytes;
-    }
+    const int64_t h_bytes = lfq_al(n * (int64_t)sizeof(LfqBaqGeom)), ord_bytes = lfq_al(n * 4);
+    LFQ_TRY(grow_pinned(&c->h_pin, &c->pin_bytes, h_bytes + ord_bytes));
     LfqBaqGeom *h = (LfqBaqGeom *)c->h_pin;
     int32_t *order = (int32_t *)(c->h_pin + h_bytes);
     /* (from the context's pinned pool: fresh memory would be page-faulted in by the threads below while the upload
@@ -980,7 +1030,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     });
     const int64_t n_bases = rs->n_bases;
     if (!rs->tag_blob) {                        /* lb (+ ai, ad): resident from here on */
-        const int64_t each = (n_bases + 16 + 255) / 256 * 256;
+        const int64_t each = lfq_al(n_bases + 16);
         rs->tag_blob = (uint8_t *)rs_cache_take(c, LFQ_RSC_TAGS, (size_t)(each * (want_idaq ? 3 : 1)), &rs->cap[LFQ_RSC_TAGS]);
         if (!rs->tag_blob) {
             return LFQ_ERR_NOMEM;
@@ -1009,9 +1059,8 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     }();
     /* per-call device data: geometry, launch order, the quality table (the reads themselves are resident) */
     uint8_t *d_blob = nullptr;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t o_reads = 0, o_q2p = o_reads + al(n * (int64_t)sizeof(LfqBaqGeom)), o_ord = o_q2p + al(1024),
-                  total = o_ord + al(n * 4);
+    const int64_t o_reads = 0, o_q2p = o_reads + lfq_al(n * (int64_t)sizeof(LfqBaqGeom)), o_ord = o_q2p + lfq_al(1024),
+                  total = o_ord + lfq_al(n * 4);
     LFQ_TRY(grow(&c->d_tmp[0], &c->tmp_bytes[0], total));
     d_blob = c->d_tmp[0];
     int rc = LFQ_OK;
@@ -1036,17 +1085,10 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     if (rc == LFQ_OK && max_lq > 0) {
         LfqBaqArgs A;
         memset(&A, 0, sizeof(A));
+        readset_view(rs, &A);
         A.geom = (const LfqBaqGeom *)(d_blob + o_reads);
-        A.pos = (const int32_t *)rs->d_pos;
-        A.cigar_off = (const int64_t *)rs->d_coff;
-        A.seq_off = (const int64_t *)rs->d_soff;
-        A.cigar = (const uint32_t *)rs->d_cig;
-        A.seq = rs->d_seq;
-        A.qual = rs->d_qual;
-        A.ref = rs->d_ref;
         A.lb_out = rs->d_lb;
         A.qual2prob = (const float *)(d_blob + o_q2p);
-        A.n_reads = n;
         A.rows = max_lq + 1;
         A.W = max_w;
         A.baq_extended = baq_extended ? 1 : 0;
@@ -1101,7 +1143,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             A.terms = c->d_baq_terms;
             A.ai_out = rs->d_ai;
             A.ad_out = rs->d_ad;
-            A.tag_flags = rs->d_tagfl;
+            A.tagfl_out = rs->d_tagfl;
         }
         d_scr = c->d_baq_scr;
         d_expect = c->d_baq_expect;
@@ -1147,12 +1189,8 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
         if ((use_side0 || use_side1) && hipEventRecord(c->ev_join[0], c->stream) != hipSuccess) {
             rc = LFQ_ERR_HIP;       /* the side streams start after the uploads / memsets queued on c->stream so far */
         }
-        /* timing events around the call's BAQ kernels (lfq_last_baq_times) */
-        if (!c->ev_baq_t[0] && (hipEventCreate(&c->ev_baq_t[0]) != hipSuccess || hipEventCreate(&c->ev_baq_t[1]) != hipSuccess)) {
-            rc = LFQ_ERR_HIP;
-        }
-        if (rc == LFQ_OK && hipEventRecord(c->ev_baq_t[0], c->stream) != hipSuccess) {
-            rc = LFQ_ERR_HIP;
+        if (rc == LFQ_OK) {
+            rc = c->baq_t.begin(c->stream);     /* around the call's BAQ kernels (lfq_last_baq_times) */
         }
         c->baq_launches = 0;
         c->baq_reads = n;
@@ -1162,7 +1200,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             Ap.itab = nullptr;
             Ap.terms = nullptr;
             Ap.ai_out = Ap.ad_out = nullptr;
-            Ap.tag_flags = nullptr;
+            Ap.tagfl_out = nullptr;
             /* (while the reads are still arriving the first launch takes one round only: it starts when the small first
              * chunk of lfq_readset_create has landed, and the link stays ahead of the kernel from there on) */
             const bool early = (rs->up_thread || rs->up_events) && rs->up_nchunks == LFQ_UP_CHUNKS && waves_n >= 4 * round
@@ -1234,15 +1272,17 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             for (int64_t first = n_narrow; rc == LFQ_OK && first < n_narrow + n_band8; first += waves * 64) {
                 A.first_read = (int32_t)first;
                 rc = lfq_launch_baq(A, std::min<int64_t>(waves * 64, n_narrow + n_band8 - first), 2, c->stream);
+                c->baq_launches++;
             }
             for (int64_t first = n_narrow + n_band8; rc == LFQ_OK && first < n; first += waves * 64) {
                 A.first_read = (int32_t)first;
                 rc = lfq_launch_baq(A, std::min<int64_t>(waves * 64, n - first), 0, c->stream);
+                c->baq_launches++;
             }
         }
     }
-    if (rc == LFQ_OK && c->ev_baq_t[1] && hipEventRecord(c->ev_baq_t[1], c->stream) != hipSuccess) {
-        rc = LFQ_ERR_HIP;
+    if (rc == LFQ_OK) {
+        rc = c->baq_t.end(c->stream);
     }
     tmb[3] = lfq_now_ms();
     /* which reads got an ai / ad tag (bam_md_ext.c:238-243) joins the resident flags as bits 2, 3 on the device; the
@@ -1282,15 +1322,11 @@ int lfq_last_baq_times(lfq_ctx *c, lfq_baq_times *t)
         return LFQ_ERR_INVALID;
     }
     memset(t, 0, sizeof(*t));
-    if (!c->ev_baq_t[0] || !c->ev_baq_t[1]) {
+    if (!c->baq_t.ev[1]) {
         return LFQ_OK;                  /* no BAQ call on this context yet */
     }
     LFQ_TRY_HIP(hipSetDevice(c->device));
-    LFQ_TRY_HIP(hipEventSynchronize(c->ev_baq_t[1]));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev_baq_t[0], c->ev_baq_t[1]) == hipSuccess) {
-        t->ms_kernels = ms;
-    }
+    LFQ_TRY(c->baq_t.ms(&t->ms_kernels));
     t->n_launches = c->baq_launches;
     t->n_reads = c->baq_reads;
     t->n_bases = c->baq_bases;
@@ -1361,10 +1397,9 @@ int lfq_readset_indelqual(lfq_ctx *c, lfq_readset *rs, const lfq_indelqual_conf 
     /* Nothing here reads what lfq_readset_baq writes: beside a BAQ step that is still running the kernels take the stream the
      * indel pileup will take (see lfq_readset_pileup_indels); the event orders any other consumer behind them */
     hipStream_t qs = (rs->baq_pending && c->dps && !lfq_knobs().single_stream) ? c->dps : c->stream;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     const int64_t tab_begin = lo < hi ? lo / 16 * 16 : 0, tab_end = lo < hi ? std::min(hi, rs->ref_len) : 0;
-    const int64_t each = al(nb + 16), o_tab = (dindel ? 1 : 2) * each;
-    const int64_t total = o_tab + (dindel ? al(std::max<int64_t>(tab_end - tab_begin, 0) + 16) : 0);
+    const int64_t each = lfq_al(nb + 16), o_tab = (dindel ? 1 : 2) * each;
+    const int64_t total = o_tab + (dindel ? lfq_al(std::max<int64_t>(tab_end - tab_begin, 0) + 16) : 0);
     if (rs->ev_idq) {
         LFQ_TRY_HIP(hipEventSynchronize(rs->ev_idq));       /* a second pass over the same read set: the first one's kernels are done */
     } else {
@@ -1377,23 +1412,15 @@ int lfq_readset_indelqual(lfq_ctx *c, lfq_readset *rs, const lfq_indelqual_conf 
             return LFQ_ERR_NOMEM;
         }
     }
-    if (!c->ev_idq_t[0]) {
-        LFQ_TRY_HIP(hipEventCreate(&c->ev_idq_t[0]));
-        LFQ_TRY_HIP(hipEventCreate(&c->ev_idq_t[1]));
-    }
     LfqIdqArgs A;
     memset(&A, 0, sizeof(A));
-    A.n_reads = n;
+    readset_view(rs, &A);                                   /* (the uniform fill reads none of it) */
     A.n_bases = nb;
-    A.bi = rs->idq_blob;
-    A.bd = dindel ? rs->idq_blob : rs->idq_blob + each;
+    A.bi_out = rs->idq_blob;
+    A.bd_out = dindel ? rs->idq_blob : rs->idq_blob + each;
     int rc = LFQ_OK;
     if (dindel) {
         rc = readset_upload_wait_inputs(rs, {qs});          /* positions, CIGARs, offsets and the contig are on the device */
-        A.pos = (const int32_t *)rs->d_pos;
-        A.cigar_off = (const int64_t *)rs->d_coff;
-        A.seq_off = (const int64_t *)rs->d_soff;
-        A.cigar = (const uint32_t *)rs->d_cig;
         A.tab = rs->idq_blob + o_tab;
         A.tab_begin = tab_begin;
         A.tab_end = tab_end;
@@ -1404,8 +1431,8 @@ int lfq_readset_indelqual(lfq_ctx *c, lfq_readset *rs, const lfq_indelqual_conf 
         A.ins_byte = rs->idq_ins;
         A.del_byte = rs->idq_del;
     }
-    if (rc == LFQ_OK && hipEventRecord(c->ev_idq_t[0], qs) != hipSuccess) {
-        rc = LFQ_ERR_HIP;
+    if (rc == LFQ_OK) {
+        rc = c->idq_t.begin(qs);
     }
     if (rc == LFQ_OK && dindel && tab_end > tab_begin) {
         rc = lfq_launch_idq_table(rs->d_ref, rs->ref_len, tab_begin, tab_end, rs->idq_blob + o_tab, qs);
@@ -1415,7 +1442,7 @@ int lfq_readset_indelqual(lfq_ctx *c, lfq_readset *rs, const lfq_indelqual_conf 
         rc = lfq_launch_idq_fill(A, qs);
         c->idq_times.n_launches++;
     }
-    if (rc == LFQ_OK && (hipEventRecord(c->ev_idq_t[1], qs) != hipSuccess || hipEventRecord(rs->ev_idq, qs) != hipSuccess)) {
+    if (rc == LFQ_OK && (c->idq_t.end(qs) != LFQ_OK || hipEventRecord(rs->ev_idq, qs) != hipSuccess)) {
         rc = LFQ_ERR_HIP;
     }
     if (rc != LFQ_OK) {
@@ -1423,8 +1450,8 @@ int lfq_readset_indelqual(lfq_ctx *c, lfq_readset *rs, const lfq_indelqual_conf 
         return rc;
     }
     rs->idq_mode = conf->mode;
-    rs->d_bi = A.bi;
-    rs->d_bd = A.bd;
+    rs->d_bi = A.bi_out;
+    rs->d_bd = A.bd_out;
     rs->has_bi = rs->has_bd = true;
     rs->h_bi = rs->h_bd = nullptr;              /* superseded by the device result */
     return LFQ_OK;
@@ -1481,13 +1508,9 @@ int lfq_last_indelqual_times(lfq_ctx *c, lfq_indelqual_times *t)
         return LFQ_ERR_INVALID;
     }
     *t = c->idq_times;
-    if (t->n_launches > 0 && c->ev_idq_t[1]) {
+    if (t->n_launches > 0) {
         LFQ_TRY_HIP(hipSetDevice(c->device));
-        LFQ_TRY_HIP(hipEventSynchronize(c->ev_idq_t[1]));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->ev_idq_t[0], c->ev_idq_t[1]) == hipSuccess) {
-            t->ms_kernels = ms;
-        }
+        LFQ_TRY(c->idq_t.ms(&t->ms_kernels));
     }
     return LFQ_OK;
 }
@@ -1521,12 +1544,11 @@ int lfq_readset_pileup_snv(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, in
     }
     LFQ_TRY_HIP(hipSetDevice(c->device));
     LFQ_TRY(readset_upload_wait(rs, c->stream));
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     /* per-position counters (kept until the next call) */
     const int64_t n_tiles = (width + LFQ_PLP_COMPACT_TILE - 1) / LFQ_PLP_COMPACT_TILE;
-    const int64_t o_cov = 0, o_nb = o_cov + al(width * 4), o_cur = o_nb + al(width * 4), o_cidx = o_cur + al(width * 4),
-                  o_tcol = o_cidx + al(width * 4), o_tobs = o_tcol + al(n_tiles * 8), o_tmax = o_tobs + al(n_tiles * 8),
-                  o_tot = o_tmax + al(n_tiles * 4), o_cpos = o_tot + 256, total = o_cpos + al(width * 8);
+    const int64_t o_cov = 0, o_nb = o_cov + lfq_al(width * 4), o_cur = o_nb + lfq_al(width * 4), o_cidx = o_cur + lfq_al(width * 4),
+                  o_tcol = o_cidx + lfq_al(width * 4), o_tobs = o_tcol + lfq_al(n_tiles * 8), o_tmax = o_tobs + lfq_al(n_tiles * 8),
+                  o_tot = o_tmax + lfq_al(n_tiles * 4), o_cpos = o_tot + 256, total = o_cpos + lfq_al(width * 8);
     /* Everything goes to the main stream, behind the BAQ kernels if they are still running (the scatter pass reads their
      * lb bytes; pass 0 beside them was measured: 2 ms alone, 14 ms squeezed between wavefronts that hold 416 of a SIMD's
      * 512 registers, with the host waiting for its result).  Nothing waits for the scatter pass: the tracks are complete
@@ -1538,40 +1560,16 @@ int lfq_readset_pileup_snv(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, in
     LFQ_TRY_HIP(hipMemsetAsync(d + o_cov, 0, (size_t)(o_cidx - o_cov), ps));
     LfqPileupArgs A;
     memset(&A, 0, sizeof(A));
-    A.n_reads = n;
-    A.pos = (const int32_t *)rs->d_pos;
-    A.cigar_off = (const int64_t *)rs->d_coff;
-    A.seq_off = (const int64_t *)rs->d_soff;
-    A.cigar = (const uint32_t *)rs->d_cig;
-    A.seq = rs->d_seq;
-    A.qual = rs->d_qual;
-    A.baq = rs->has_lb ? rs->d_lb : nullptr;
-    A.mapq = rs->d_mapq;
-    A.reverse = rs->d_rev;
-    A.sq = rs->has_sqb ? rs->d_sqb : nullptr;
+    /* position-sorted reads (the normal case): the column-major kernels; otherwise, if asked for, one thread per read + atomics
+     * (as mpileup: bam_mplp_auto stops at a file that is not coordinate-sorted, plp.c:1406-1447) */
+    LFQ_TRY(readset_pileup_view(c, rs, ps, true, &A));
+    const bool sorted = A.pmax_end != nullptr;
     A.begin = region_begin;
     A.width = width;
     A.min_plp_bq = min_plp_bq;
     A.cov = (int32_t *)(d + o_cov);
     A.nb = (int32_t *)(d + o_nb);
     A.cursor = (int32_t *)(d + o_cur);
-    /* position-sorted reads (the normal case): the column-major kernels; otherwise one thread per read + atomics */
-    A.pmax_end = readset_pmax(c, rs, ps);
-    const bool sorted = A.pmax_end != nullptr;
-    if (!sorted && !readset_unsorted_ok(c, rs)) {
-        return LFQ_ERR_INVALID;             /* as mpileup: bam_mplp_auto stops at a file that is not coordinate-sorted (plp.c:1406-1447) */
-    }
-    {
-        /* -d cap: the kernels walk the kept reads only (null: the cap drops nothing, or there is none) */
-        const int32_t *k_idx, *k_pos, *k_pmax;
-        LFQ_TRY(readset_keep_device(c, rs, ps, &k_idx, &k_pos, &k_pmax));
-        if (k_idx) {
-            A.n_reads = rs->n_kept;
-            A.read_idx = k_idx;
-            A.pos = k_pos;
-            A.pmax_end = k_pmax;
-        }
-    }
     LFQ_TRY(sorted ? lfq_launch_pileup_columns(A, 0, ps) : lfq_launch_pileup_count(A, ps));
     /* columns from the counters on the device (lfq_launch_plp_compact_*): the host waits once, for three numbers */
     LfqPin<int64_t> tot(c, 4);
@@ -1581,11 +1579,11 @@ int lfq_readset_pileup_snv(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, in
     LFQ_TRY_HIP(hipMemcpyAsync(tot.data(), d + o_tot, 24, hipMemcpyDeviceToHost, ps));
     LFQ_TRY_HIP(hipStreamSynchronize(ps));
     const int64_t ncols = tot[0], n_obs = tot[1], max_obs = tot[2];
-    const int64_t trk = al(n_obs + 32);
+    const int64_t trk = lfq_al(n_obs + 32);
     const bool nt_packed = !c->plp_nt_bytes;
-    const int64_t t_off = 0, t_ref = t_off + al((ncols + 1) * 8), t_cov = t_ref + al(ncols + 16), t_nb = t_cov + al(ncols * 4 + 16),
-                  t_nt = t_nb + al(ncols * 4 + 16), t_bq = t_nt + trk, t_baq = t_bq + trk, t_mq = t_baq + trk,
-                  t_sq = t_mq + trk, t_ntp = t_sq + (rs->has_sqb ? trk : 0), t_total = t_ntp + (nt_packed ? al(trk / 2 + 16) : 0);
+    const int64_t t_off = 0, t_ref = t_off + lfq_al((ncols + 1) * 8), t_cov = t_ref + lfq_al(ncols + 16), t_nb = t_cov + lfq_al(ncols * 4 + 16),
+                  t_nt = t_nb + lfq_al(ncols * 4 + 16), t_bq = t_nt + trk, t_baq = t_bq + trk, t_mq = t_baq + trk,
+                  t_sq = t_mq + trk, t_ntp = t_sq + (rs->has_sqb ? trk : 0), t_total = t_ntp + (nt_packed ? lfq_al(trk / 2 + 16) : 0);
     LFQ_TRY(grow(&c->d_plp_out, &c->plp_out_bytes, t_total));
     uint8_t *t = c->d_plp_out;
     LFQ_TRY_HIP(hipMemsetAsync(t + t_nt, 0, (size_t)(t_total - t_nt), ps));            /* the 16-byte tails are read */
@@ -1681,25 +1679,18 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
     LFQ_TRY(readset_upload_wait(rs, ps));
     /* the window search needs position-sorted reads, and the reference's -d acts on the reads of each 1-bp query: a cap
      * that drops a read of the region is not that rule */
-    const int32_t *pmax = rs->n > 0 ? readset_pmax(c, rs, ps) : nullptr;
-    if (rs->n > 0 && !pmax) {
-        return LFQ_ERR_INVALID;
-    }
     LFQ_TRY(readset_keep(c, rs));
     if (c->plp_max_depth != LFQ_NO_MAX_DEPTH && !rs->keep.empty()) {
         return LFQ_ERR_INVALID;
     }
+    LfqSitesArgs A;
+    memset(&A, 0, sizeof(A));
+    LFQ_TRY(readset_pileup_view(c, rs, ps, false, &A));   /* (the cap decided above drops nothing: only the running maximum goes up) */
     c->sites_times.n_sites = n_sites;
-    for (int i = 0; i < 4; i++) {
-        if (!c->ev_sites_t[i]) {
-            LFQ_TRY_HIP(hipEventCreate(&c->ev_sites_t[i]));
-        }
-    }
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     const int64_t n = n_sites, n_key = key_off ? key_off[n] - key_off[0] : 0;
     /* what goes up in one copy: positions | key offsets | key sides | key letters; then the windows and the counts */
-    const int64_t o_pos = 0, o_koff = o_pos + al(n * 8), o_kdel = o_koff + al((n + 1) * 8), o_kch = o_kdel + al(n),
-                  o_win = o_kch + al(n_key + 1), o_cnt = o_win + al(n * 16), total = o_cnt + al(n * 16);
+    const int64_t o_pos = 0, o_koff = o_pos + lfq_al(n * 8), o_kdel = o_koff + lfq_al((n + 1) * 8), o_kch = o_kdel + lfq_al(n),
+                  o_win = o_kch + lfq_al(n_key + 1), o_cnt = o_win + lfq_al(n * 16), total = o_cnt + lfq_al(n * 16);
     LFQ_TRY(lfq_order_after_batch(c, ps));                 /* the tracks of the previous call may still be a running batch's input */
     LFQ_TRY(grow(&c->d_sites_in, &c->sites_in_bytes, total));
     uint8_t *d = c->d_sites_in;
@@ -1717,22 +1708,6 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
         }
     }
     LFQ_TRY_HIP(hipMemcpyAsync(d, up.data(), (size_t)o_win, hipMemcpyHostToDevice, ps));
-    LfqSitesArgs A;
-    memset(&A, 0, sizeof(A));
-    A.n_reads = rs->n;
-    A.pos = (const int32_t *)rs->d_pos;
-    A.pmax_end = pmax;
-    A.cigar_off = (const int64_t *)rs->d_coff;
-    A.seq_off = (const int64_t *)rs->d_soff;
-    A.cigar = (const uint32_t *)rs->d_cig;
-    A.seq = rs->d_seq;
-    A.qual = rs->d_qual;
-    A.baq = rs->has_lb ? rs->d_lb : nullptr;
-    A.mapq = rs->d_mapq;
-    A.reverse = rs->d_rev;
-    A.sq = rs->has_sqb ? rs->d_sqb : nullptr;
-    A.ref = rs->d_ref;
-    A.ref_len = rs->ref_len;
     A.n_sites = n;
     A.site_pos = (const int64_t *)(d + o_pos);
     A.min_plp_bq = min_plp_bq;
@@ -1745,16 +1720,16 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
     A.win = (int64_t *)(d + o_win);
     LfqPin<int32_t> h_cnt(c, (size_t)n * 4);
     LFQ_PIN_OK(h_cnt);
-    LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[0], ps));
+    LFQ_TRY(c->sites_t[0].begin(ps));
     LFQ_TRY(lfq_launch_pileup_sites(A, 0, ps));
-    LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[1], ps));
+    LFQ_TRY(c->sites_t[0].end(ps));
     c->sites_times.n_launches = 1;
     LFQ_TRY_HIP(hipMemcpyAsync(h_cnt.data(), A.counts, (size_t)n * 16, hipMemcpyDeviceToHost, ps));
     LFQ_TRY_HIP(hipStreamSynchronize(ps));
     const int32_t *h_cov = h_cnt.data(), *h_nb = h_cov + n, *h_tails = h_nb + n, *h_ev = h_tails + n;
     /* the header of the tracks, assembled here and sent down in one copy: offsets | reference bases | coverage_plp | num_bases */
-    const int64_t t_off = 0, t_ref = t_off + al((n + 1) * 8), t_cov = t_ref + al(n + 16), t_nb = t_cov + al(n * 4 + 16),
-                  t_nt = t_nb + al(n * 4 + 16);
+    const int64_t t_off = 0, t_ref = t_off + lfq_al((n + 1) * 8), t_cov = t_ref + lfq_al(n + 16), t_nb = t_cov + lfq_al(n * 4 + 16),
+                  t_nt = t_nb + lfq_al(n * 4 + 16);
     LfqPin<uint8_t> hdr(c, (size_t)t_nt);
     LFQ_PIN_OK(hdr);
     memset(hdr.data(), 0, (size_t)t_nt);
@@ -1773,7 +1748,7 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
     h_off[n] = (uint64_t)n_obs;
     memcpy(hdr.data() + t_cov, h_cov, (size_t)n * 4);
     memcpy(hdr.data() + t_nb, h_nb, (size_t)n * 4);
-    const int64_t trk = al(n_obs + 32);
+    const int64_t trk = lfq_al(n_obs + 32);
     const int64_t t_bq = t_nt + trk, t_baq = t_bq + trk, t_mq = t_baq + trk, t_sq = t_mq + trk,
                   t_total = t_sq + (rs->has_sqb ? trk : 0);
     LFQ_TRY(grow(&c->d_sites_out, &c->sites_out_bytes, t_total));
@@ -1789,9 +1764,9 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
         A.t_baq = t + t_baq;
         A.t_mq = t + t_mq;
         A.t_sq = rs->has_sqb ? t + t_sq : nullptr;
-        LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[2], ps));
+        LFQ_TRY(c->sites_t[1].begin(ps));
         LFQ_TRY(lfq_launch_pileup_sites(A, 1, ps));
-        LFQ_TRY_HIP(hipEventRecord(c->ev_sites_t[3], ps));
+        LFQ_TRY(c->sites_t[1].end(ps));
         c->sites_times.n_launches = 2;
     }
     c->sites_times.n_obs = n_obs;
@@ -1832,13 +1807,9 @@ int lfq_last_sites_times(lfq_ctx *c, lfq_sites_times *t)
     *t = c->sites_times;
     if (t->n_launches > 0) {
         LFQ_TRY_HIP(hipSetDevice(c->device));
-        LFQ_TRY_HIP(hipEventSynchronize(c->ev_sites_t[t->n_launches > 1 ? 3 : 1]));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->ev_sites_t[0], c->ev_sites_t[1]) == hipSuccess) {
-            t->count_ms = ms;
-        }
-        if (t->n_launches > 1 && hipEventElapsedTime(&ms, c->ev_sites_t[2], c->ev_sites_t[3]) == hipSuccess) {
-            t->scatter_ms = ms;
+        LFQ_TRY(c->sites_t[0].ms(&t->count_ms));
+        if (t->n_launches > 1) {
+            LFQ_TRY(c->sites_t[1].ms(&t->scatter_ms));
         }
     }
     return LFQ_OK;
@@ -2030,14 +2001,13 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
          * kernel leaves as they are): while its kernels are still running they go to another stream and run beside them --
          * the BAQ kernels hold one wavefront per SIMD and 416 of its 512 registers, these kernels need 40. */
         hipStream_t ps = (rs->baq_pending && c->dps && !lfq_knobs().single_stream) ? c->dps : c->stream;
-        (void)readset_pmax(c, rs, ps);      /* (its small upload is waited for on this stream: before the stream itself waits) */
+        (void)readset_pmax(c, rs, ps, true);    /* (its small upload is waited for on this stream: before the stream itself waits) */
         LFQ_TRY(readset_upload_wait(rs, ps));
         if (rs->ev_idq) {
             LFQ_TRY_HIP(hipStreamWaitEvent(ps, rs->ev_idq, 0));
         }
-        auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-        const int64_t o_cnt = 0, o_cur = o_cnt + 9 * al(width * 4), o_off = o_cur + 2 * al(width * 4),
-                      total = o_off + 2 * al(width * 8);
+        const int64_t o_cnt = 0, o_cur = o_cnt + 9 * lfq_al(width * 4), o_off = o_cur + 2 * lfq_al(width * 4),
+                      total = o_off + 2 * lfq_al(width * 8);
         LFQ_TRY(grow(&c->d_tmp[1], &c->tmp_bytes[1], total));
         uint8_t *d = c->d_tmp[1];
         int16_t *d_ne = nullptr;
@@ -2053,57 +2023,25 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
         }
         LfqPlpIndelArgs A;
         memset(&A, 0, sizeof(A));
-        A.n_reads = n;
-        A.pos = (const int32_t *)rs->d_pos;
-        A.cigar_off = (const int64_t *)rs->d_coff;
-        A.seq_off = (const int64_t *)rs->d_soff;
-        A.cigar = (const uint32_t *)rs->d_cig;
-        A.bi = rs->has_bi ? rs->d_bi : nullptr;
-        A.bd = rs->has_bd ? rs->d_bd : nullptr;
-        A.tag_flags = rs->idq_mode ? nullptr : rs->d_fl;        /* lfq_readset_indelqual: every read has both */
-        A.mapq = rs->d_mapq;
-        A.reverse = rs->d_rev;
         A.begin = region_begin;
         A.width = width;
         A.min_plp_idq = min_plp_idq;
         int32_t **cnt[9] = {&A.cov, &A.tails, &A.non_indels, &A.n_ins, &A.n_dels, &A.non_ins_fw, &A.non_del_fw,
                             &A.ne_qsum[0], &A.ne_qsum[1]};
         for (int i = 0; i < 9; i++) {
-            *cnt[i] = (int32_t *)(d + o_cnt + i * al(width * 4));
+            *cnt[i] = (int32_t *)(d + o_cnt + i * lfq_al(width * 4));
         }
         /* the nine per-position counters come back into pinned memory (grow-only): DMA instead of a staged copy */
         int32_t *h[9] = {nullptr};
         {
-            const int64_t need = 9 * al(width * 4);
-            if (need > c->pin2_bytes) {
-                if (c->h_pin2) (void)hipHostFree(c->h_pin2);
-                c->h_pin2 = nullptr;
-                c->pin2_bytes = 0;
-                if (hipHostMalloc((void **)&c->h_pin2, (size_t)need, hipHostMallocDefault) != hipSuccess) {
-                    return LFQ_ERR_NOMEM;
-                }
-                c->pin2_bytes = need;
-            }
+            LFQ_TRY(grow_pinned(&c->h_pin2, &c->pin2_bytes, 9 * lfq_al(width * 4)));
             for (int i = 0; i < 9; i++) {
-                h[i] = (int32_t *)(c->h_pin2 + i * al(width * 4));
+                h[i] = (int32_t *)(c->h_pin2 + i * lfq_al(width * 4));
             }
         }
         if (rc == LFQ_OK) {
-            A.pmax_end = readset_pmax(c, rs, ps);
-            if (!A.pmax_end && !readset_unsorted_ok(c, rs)) {
-                rc = LFQ_ERR_INVALID;       /* not coordinate-sorted: refused like mpileup does (lfq_set_pileup_unsorted) */
-            }
-        }
-        if (rc == LFQ_OK) {
-            /* -d cap: the kept reads only, the same decision as the SNV pileup's (the column lists must agree) */
-            const int32_t *k_idx, *k_pos, *k_pmax;
-            rc = readset_keep_device(c, rs, ps, &k_idx, &k_pos, &k_pmax);
-            if (rc == LFQ_OK && k_idx) {
-                A.n_reads = rs->n_kept;
-                A.read_idx = k_idx;
-                A.pos = k_pos;
-                A.pmax_end = k_pmax;
-            }
+            /* not coordinate-sorted: refused like mpileup does (lfq_set_pileup_unsorted); -d cap: the kept reads only */
+            rc = readset_pileup_view(c, rs, ps, true, &A);
         }
         if (rc == LFQ_OK) {
             rc = A.pmax_end ? lfq_launch_plp_indel_columns(A, 0, ps) : lfq_launch_plp_indel(A, 0, ps);
@@ -2423,9 +2361,9 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
             d_ne = c->d_plp_ne;
             if (rc == LFQ_OK && ne_all > 0) {
                 for (int sd = 0; sd < 2; sd++) {
-                    up(o_off + sd * al(width * 8), pos_off[sd], width * 8);
-                    A.ne_off[sd] = (const int64_t *)(d + o_off + sd * al(width * 8));
-                    A.cursor[sd] = (int32_t *)(d + o_cur + sd * al(width * 4));
+                    up(o_off + sd * lfq_al(width * 8), pos_off[sd], width * 8);
+                    A.ne_off[sd] = (const int64_t *)(d + o_off + sd * lfq_al(width * 8));
+                    A.cursor[sd] = (int32_t *)(d + o_cur + sd * lfq_al(width * 4));
                 }
                 A.ne_q[0] = d_ne;
                 A.ne_mq[0] = d_ne + ne_total[0];
@@ -2652,10 +2590,7 @@ int lfq_readset_plp_summary(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, i
     LFQ_TRY_HIP(hipSetDevice(c->device));
     hipStream_t ps = c->stream;
     LFQ_TRY(readset_upload_wait(rs, ps));
-    const int32_t *pmax = readset_pmax(c, rs, ps);
-    if (!pmax) {
-        return LFQ_ERR_INVALID;             /* the window search needs position-sorted reads (lfq_set_pileup_unsorted does not apply) */
-    }
+    LFQ_TRY(readset_pmax(c, rs, ps, false));    /* the window search needs position-sorted reads (lfq_set_pileup_unsorted does not apply) */
     /* the indel side: the context's current lfq_indel_columns are this region's from here on */
     const lfq_indel_columns *ic = nullptr;
     S.col_pos.resize((size_t)width);
@@ -2673,48 +2608,25 @@ int lfq_readset_plp_summary(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, i
     if (O.ne_qsum[0].size() != (size_t)ncols || O.ne_qsum[1].size() != (size_t)ncols) {
         return LFQ_ERR_INVALID;             /* (cannot happen: sorted reads go to the kernel that sums the qualities) */
     }
-    for (int i = 0; i < 2; i++) {
-        if (!c->ev_sum_t[i]) {
-            LFQ_TRY_HIP(hipEventCreate(&c->ev_sum_t[i]));
-        }
-    }
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
     /* what goes up in one copy: column positions | increment table; what the kernel writes and one copy brings back into pinned
      * memory, where the struct points at it: fw | rv | heads | tails | consensus letter | path */
-    const int64_t o_pos = 0, o_incr = o_pos + al(ncols * 8), o_cnt = o_incr + al(94 * 8), o_rv = o_cnt + al(ncols * 20),
-                  o_heads = o_rv + al(ncols * 20), o_tails = o_heads + al(ncols * 4), o_cons = o_tails + al(ncols * 4),
-                  o_ord = o_cons + al(ncols), total = o_ord + al(ncols);
+    const int64_t o_pos = 0, o_incr = o_pos + lfq_al(ncols * 8), o_cnt = o_incr + lfq_al(94 * 8), o_rv = o_cnt + lfq_al(ncols * 20),
+                  o_heads = o_rv + lfq_al(ncols * 20), o_tails = o_heads + lfq_al(ncols * 4), o_cons = o_tails + lfq_al(ncols * 4),
+                  o_ord = o_cons + lfq_al(ncols), total = o_ord + lfq_al(ncols);
     LFQ_TRY(grow(&c->d_sum, &c->sum_bytes, total));
     uint8_t *d = c->d_sum;
-    if (total - o_cnt > c->h_sum_bytes) {
-        if (c->h_sum) (void)hipHostFree(c->h_sum);
-        c->h_sum = nullptr;
-        c->h_sum_bytes = 0;
-        if (hipHostMalloc((void **)&c->h_sum, (size_t)(total - o_cnt), hipHostMallocDefault) != hipSuccess) {
-            return LFQ_ERR_NOMEM;
-        }
-        c->h_sum_bytes = total - o_cnt;
-    }
+    LFQ_TRY(grow_pinned(&c->h_sum, &c->h_sum_bytes, total - o_cnt));
     const uint8_t *h = c->h_sum - o_cnt;                    /* h + o_x: where the device's d + o_x lands */
-    /* -d cap: the decision both pileups share (before the first copy is queued: nothing below returns with one in flight) */
-    const int32_t *k_idx, *k_pos, *k_pmax;
-    LFQ_TRY(readset_keep_device(c, rs, ps, &k_idx, &k_pos, &k_pmax));
+    /* the reads, with the -d decision both pileups share (the sorted-or-refused answer was needed before the indel side ran, so
+     * readset_pmax is called there; here, before the first copy is queued: nothing below returns with one in flight) */
+    LfqSummaryArgs A;
+    memset(&A, 0, sizeof(A));
+    LFQ_TRY(readset_pileup_view(c, rs, ps, false, &A));
     LfqPin<uint8_t> up(c, (size_t)o_cnt);
     LFQ_PIN_OK(up);
     memcpy(up.data() + o_pos, S.col_pos.data(), (size_t)ncols * 8);
     memcpy(up.data() + o_incr, summary_incr_table(), 94 * 8);
     int rc = hipMemcpyAsync(d, up.data(), (size_t)o_cnt, hipMemcpyHostToDevice, ps) == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
-    LfqSummaryArgs A;
-    memset(&A, 0, sizeof(A));
-    A.n_reads = rs->n;
-    A.pos = (const int32_t *)rs->d_pos;
-    A.pmax_end = pmax;
-    A.cigar_off = (const int64_t *)rs->d_coff;
-    A.seq_off = (const int64_t *)rs->d_soff;
-    A.cigar = (const uint32_t *)rs->d_cig;
-    A.seq = rs->d_seq;
-    A.qual = rs->d_qual;
-    A.reverse = rs->d_rev;
     A.n_cols = ncols;
     A.col_pos = (const int64_t *)(d + o_pos);
     A.min_plp_bq = min_plp_bq;
@@ -2725,19 +2637,13 @@ int lfq_readset_plp_summary(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, i
     A.tails = (int32_t *)(d + o_tails);
     A.cons_nt = d + o_cons;
     A.ordered = d + o_ord;
-    if (k_idx) {                            /* -d cap: the kept reads only */
-        A.n_reads = rs->n_kept;
-        A.read_idx = k_idx;
-        A.pos = k_pos;
-        A.pmax_end = k_pmax;
-    }
-    if (rc == LFQ_OK && hipEventRecord(c->ev_sum_t[0], ps) != hipSuccess) {
-        rc = LFQ_ERR_HIP;
+    if (rc == LFQ_OK) {
+        rc = c->sum_t.begin(ps);
     }
     if (rc == LFQ_OK) {
         rc = lfq_launch_plp_summary(A, ps);
     }
-    if (rc == LFQ_OK && (hipEventRecord(c->ev_sum_t[1], ps) != hipSuccess
+    if (rc == LFQ_OK && (c->sum_t.end(ps) != LFQ_OK
                          || hipMemcpyAsync(c->h_sum, d + o_cnt, (size_t)(total - o_cnt), hipMemcpyDeviceToHost, ps) != hipSuccess)) {
         rc = LFQ_ERR_HIP;
     }
@@ -2807,11 +2713,7 @@ int lfq_last_summary_times(lfq_ctx *c, lfq_summary_times *t)
     *t = c->sum_times;
     if (t->n_launches > 0) {
         LFQ_TRY_HIP(hipSetDevice(c->device));
-        LFQ_TRY_HIP(hipEventSynchronize(c->ev_sum_t[1]));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->ev_sum_t[0], c->ev_sum_t[1]) == hipSuccess) {
-            t->kernel_ms = ms;
-        }
+        LFQ_TRY(c->sum_t.ms(&t->kernel_ms));
     }
     return LFQ_OK;
 }
@@ -2839,19 +2741,6 @@ int lfq_plp_quals_from_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_de
     Q.col_begin = col_begin;
     c->pq_times.n_cols = ncols;
     *out = &Q;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-    auto pinned = [c](int64_t need) {
-        if (need > c->h_pq_bytes) {
-            if (c->h_pq) (void)hipHostFree(c->h_pq);
-            c->h_pq = nullptr;
-            c->h_pq_bytes = 0;
-            if (hipHostMalloc((void **)&c->h_pq, (size_t)need, hipHostMallocDefault) != hipSuccess) {
-                return LFQ_ERR_NOMEM;
-            }
-            c->h_pq_bytes = need;
-        }
-        return LFQ_OK;
-    };
     LFQ_TRY_HIP(hipSetDevice(c->device));
     hipStream_t ps = c->stream;
     /* the range's first and last offset: how large the output is */
@@ -2882,9 +2771,9 @@ int lfq_plp_quals_from_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_de
     const int64_t n_off = 5 * ncols + 1;
     const bool has_baq = tr->baq != nullptr, has_sq = tr->sq != nullptr;
     /* output: nt_off | bq | baq | mq | sq */
-    const int64_t r_off = 0, r_bq = r_off + al(n_off * 8), r_baq = r_bq + al(n_obs), r_mq = r_baq + (has_baq ? al(n_obs) : 0),
-                  r_sq = r_mq + al(n_obs), r_total = r_sq + (has_sq ? al(n_obs) : 0);
-    LFQ_TRY(pinned(r_total));
+    const int64_t r_off = 0, r_bq = r_off + lfq_al(n_off * 8), r_baq = r_bq + lfq_al(n_obs), r_mq = r_baq + (has_baq ? lfq_al(n_obs) : 0),
+                  r_sq = r_mq + lfq_al(n_obs), r_total = r_sq + (has_sq ? lfq_al(n_obs) : 0);
+    LFQ_TRY(grow_pinned(&c->h_pq, &c->h_pq_bytes, r_total));
     uint8_t *h = c->h_pq;
     int64_t *h_off = (int64_t *)(h + r_off);
     Q.nt_off = h_off;
@@ -2899,16 +2788,11 @@ int lfq_plp_quals_from_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_de
         return LFQ_OK;
     }
     /* host tracks: col_off | nt | bq | baq | mq | sq of the range go up in front of the output */
-    const int64_t u_off = 0, u_nt = u_off + al((ncols + 1) * 8), u_bq = u_nt + al(n_obs), u_baq = u_bq + al(n_obs),
-                  u_mq = u_baq + (has_baq ? al(n_obs) : 0), u_sq = u_mq + al(n_obs), u_total = u_sq + (has_sq ? al(n_obs) : 0);
+    const int64_t u_off = 0, u_nt = u_off + lfq_al((ncols + 1) * 8), u_bq = u_nt + lfq_al(n_obs), u_baq = u_bq + lfq_al(n_obs),
+                  u_mq = u_baq + (has_baq ? lfq_al(n_obs) : 0), u_sq = u_mq + lfq_al(n_obs), u_total = u_sq + (has_sq ? lfq_al(n_obs) : 0);
     const int64_t o_out = tracks_on_device ? 0 : u_total;
     LFQ_TRY(grow(&c->d_pq, &c->pq_bytes, o_out + r_total));
     uint8_t *d = c->d_pq;
-    for (int i = 0; i < 2; i++) {
-        if (!c->ev_pq_t[i]) {
-            LFQ_TRY_HIP(hipEventCreate(&c->ev_pq_t[i]));
-        }
-    }
     LfqPlpGroupArgs A;
     memset(&A, 0, sizeof(A));
     A.n_cols = ncols;
@@ -2947,13 +2831,13 @@ int lfq_plp_quals_from_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_de
     A.o_baq = has_baq ? d + o_out + r_baq : nullptr;
     A.o_mq = d + o_out + r_mq;
     A.o_sq = has_sq ? d + o_out + r_sq : nullptr;
-    if (rc == LFQ_OK && hipEventRecord(c->ev_pq_t[0], ps) != hipSuccess) {
-        rc = LFQ_ERR_HIP;
+    if (rc == LFQ_OK) {
+        rc = c->pq_t.begin(ps);
     }
     if (rc == LFQ_OK) {
         rc = lfq_launch_plp_group(A, ps);
     }
-    if (rc == LFQ_OK && (hipEventRecord(c->ev_pq_t[1], ps) != hipSuccess
+    if (rc == LFQ_OK && (c->pq_t.end(ps) != LFQ_OK
                          || hipMemcpyAsync(h, d + o_out, (size_t)r_total, hipMemcpyDeviceToHost, ps) != hipSuccess)) {
         rc = LFQ_ERR_HIP;
     }
@@ -2974,11 +2858,7 @@ int lfq_last_plp_quals_times(lfq_ctx *c, lfq_plp_quals_times *t)
     *t = c->pq_times;
     if (t->n_launches > 0) {
         LFQ_TRY_HIP(hipSetDevice(c->device));
-        LFQ_TRY_HIP(hipEventSynchronize(c->ev_pq_t[1]));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->ev_pq_t[0], c->ev_pq_t[1]) == hipSuccess) {
-            t->kernel_ms = ms;
-        }
+        LFQ_TRY(c->pq_t.ms(&t->kernel_ms));
     }
     return LFQ_OK;
 }
@@ -3025,8 +2905,7 @@ int lfq_readset_source_qual(lfq_ctx *c, lfq_readset *rs, int def_nm_q, int min_b
     }
     const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)c->n_cu * 2));
     const int64_t scratch_cells = max_ops + 1 > LFQ_SRCQ_LDS_CELLS ? max_ops + 1 : 0;
-    auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t o_ign = 0, o_prob = o_ign + (ign ? al(rd->ref_len) : 0), o_st = o_prob + al(n * 8), o_scr = o_st + al(n),
+    const int64_t o_ign = 0, o_prob = o_ign + (ign ? lfq_al(rd->ref_len) : 0), o_st = o_prob + lfq_al(n * 8), o_scr = o_st + lfq_al(n),
                   total = o_scr + (int64_t)n_blocks * 4 * 2 * scratch_cells * 8;
     uint8_t *d = nullptr;
     if (hipMalloc((void **)&d, (size_t)total) != hipSuccess) {
@@ -3044,15 +2923,7 @@ int lfq_readset_source_qual(lfq_ctx *c, lfq_readset *rs, int def_nm_q, int min_b
     if (rc == LFQ_OK) {
         LfqSrcqArgs A;
         memset(&A, 0, sizeof(A));
-        A.n_reads = n;
-        A.pos = (const int32_t *)rs->d_pos;
-        A.cigar_off = (const int64_t *)rs->d_coff;
-        A.seq_off = (const int64_t *)rs->d_soff;
-        A.cigar = (const uint32_t *)rs->d_cig;
-        A.seq = rs->d_seq;
-        A.qual = rs->d_qual;
-        A.ref = (const char *)rs->d_ref;
-        A.ref_len = rd->ref_len;
+        readset_view(rs, &A);
         A.ign = ign ? d + o_ign : nullptr;
         A.nonmatch_qual = def_nm_q;
         A.min_bq = min_bq;
@@ -3128,11 +2999,10 @@ int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset *
     br.n_reads = n;
     br.pos = rs->pos; br.cigar_off = rs->cigar_off; br.cigar = rs->cigar; br.seq_off = rs->seq_off;
     br.seq = rs->seq; br.qual = rs->qual; br.ref = rs->ref; br.ref_len = rs->ref_len;
-    LfqVitResident dv;
+    LfqReadsDev dv;
     memset(&dv, 0, sizeof(dv));
     if (n > 0) {
-        dv.d_seq_off = (const int64_t *)rs->d_soff; dv.d_cigar_off = (const int64_t *)rs->d_coff;
-        dv.d_cigar = (const uint32_t *)rs->d_cig; dv.d_seq = rs->d_seq; dv.d_qual = rs->d_qual; dv.d_ref = rs->d_ref;
+        readset_view(rs, &dv);
     }
     const lfq_viterbi_result *res = nullptr;
     LFQ_TRY(lfq_viterbi_run(c, &br, def_qual, &dv, &res));
@@ -3295,7 +3165,7 @@ int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_rea
     LFQ_TRY(lfq_bam_aux(c, data, data_bytes, first_shift, lfq_is_pinned(data), desc.data(), n, nb, own->flags.data(), &any_bi,
                         &any_bd));
     /* the pinned landing area of the per-base arrays, from the context's cache; the host views of the read set point into it */
-    const size_t stride = (size_t)((nb + 16 + 255) / 256 * 256);
+    const size_t stride = (size_t)lfq_al(nb + 16);
     own->pin_bases = (uint8_t *)rs_cache_take(c, LFQ_RSC_PINBASES, stride * (size_t)(2 + any_bi + any_bd), &own->pin_cap);
     if (!own->pin_bases) {
         return LFQ_ERR_NOMEM;
@@ -3458,9 +3328,7 @@ int lfq_readset_encode_bam(lfq_ctx *c, lfq_readset *rs, const lfq_bam_records *r
     if ((what & LFQ_BAM_PUT_INDELQUAL) && rs->ev_idq) {
         LFQ_TRY_HIP(hipStreamWaitEvent(c->stream, rs->ev_idq, 0));
     }
-    in.d_coff = (const int64_t *)rs->d_coff;
-    in.d_soff = (const int64_t *)rs->d_soff;
-    in.d_cig = (const uint32_t *)rs->d_cig;
+    readset_view(rs, &in.rd);
     in.d_fl = rs->d_fl;
     in.d_lb = (what & LFQ_BAM_PUT_LB) ? rs->d_lb : nullptr;
     in.d_ai = (what & LFQ_BAM_PUT_IDAQ) ? rs->d_ai : nullptr;

@@ -663,7 +663,7 @@ static int vit_scan(LfqViterbiState *S, const lfq_baq_reads *rd, int def_qual, b
 /* ---- the kernels, over the compacted list, in chunks the scratch budget admits: traced states and where each trace ended.
  * res = the device arrays of a resident read set, in the read order of the plan, or null (query and windows come from the
  * plan's host arrays) ---- */
-static int vit_launch(lfq_ctx *c, LfqViterbiState *S, VitPlan &P, int def_qual, const LfqVitResident *res,
+static int vit_launch(lfq_ctx *c, LfqViterbiState *S, VitPlan &P, int def_qual, const LfqReadsDev *res,
                       std::vector<uint8_t> &states, std::vector<LfqVitOut> &outs)
 {
     const int64_t nw = (int64_t)P.work.size(), st_total = P.st_total;
@@ -677,12 +677,11 @@ static int vit_launch(lfq_ctx *c, LfqViterbiState *S, VitPlan &P, int def_qual, 
         emis[2 * qv + 1] = log10(bp / 3.);
     }
     /* one upload: descriptors | tables | sources (resident reads) | query letters | qualities | windows (host reads) */
-    auto al = [](int64_t v) { return (v + 255) / 256 * 256; };
-    const int64_t o_dev = 0, o_tp = al(o_dev + nw * (int64_t)sizeof(LfqVitRead));
-    const int64_t o_em = al(o_tp + (int64_t)P.tps.size() * (int64_t)sizeof(LfqVitTp));
-    const int64_t o_src = al(o_em + (int64_t)sizeof(emis)), o_ql = al(o_src + (int64_t)P.src.size() * (int64_t)sizeof(LfqVitSrc));
-    const int64_t o_qe = al(o_ql + P.q_total), o_win = al(o_qe + P.q_total), o_out = al(o_win + P.win_total);
-    const int64_t in_total = al(o_out + nw * (int64_t)sizeof(LfqVitOut));
+    const int64_t o_dev = 0, o_tp = lfq_al(o_dev + nw * (int64_t)sizeof(LfqVitRead));
+    const int64_t o_em = lfq_al(o_tp + (int64_t)P.tps.size() * (int64_t)sizeof(LfqVitTp));
+    const int64_t o_src = lfq_al(o_em + (int64_t)sizeof(emis)), o_ql = lfq_al(o_src + (int64_t)P.src.size() * (int64_t)sizeof(LfqVitSrc));
+    const int64_t o_qe = lfq_al(o_ql + P.q_total), o_win = lfq_al(o_qe + P.q_total), o_out = lfq_al(o_win + P.win_total);
+    const int64_t in_total = lfq_al(o_out + nw * (int64_t)sizeof(LfqVitOut));
     const int64_t up_total = res ? o_ql : o_out;
     LFQ_TRY(grow(&S->d_in, &S->in_bytes, in_total));
     LFQ_TRY(grow(&S->d_states, &S->states_bytes, st_total));
@@ -749,12 +748,12 @@ static int vit_launch(lfq_ctx *c, LfqViterbiState *S, VitPlan &P, int def_qual, 
         memset(&G, 0, sizeof(G));
         G.reads = A.reads;
         G.src = (const LfqVitSrc *)(S->d_in + o_src);
-        G.seq_off = res->d_seq_off;
-        G.cigar_off = res->d_cigar_off;
-        G.cigar = res->d_cigar;
-        G.seq = res->d_seq;
-        G.qual = res->d_qual;
-        G.ref = res->d_ref;
+        G.seq_off = res->seq_off;
+        G.cigar_off = res->cigar_off;
+        G.cigar = res->cigar;
+        G.seq = res->seq;
+        G.qual = res->qual;
+        G.ref = res->ref;
         G.qletter = S->d_in + o_ql;
         G.qeff = S->d_in + o_qe;
         G.win = S->d_in + o_win;
@@ -889,7 +888,7 @@ static int vit_finish(LfqViterbiState *S, const lfq_baq_reads *rd, const VitPlan
 
 /* lfq_viterbi_batch (res = null), and the realignment of lfq_readset_viterbi: rd = the host arrays the read set was made
  * from, res = its device copies */
-int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *rd, int def_qual, const LfqVitResident *res, const lfq_viterbi_result **out)
+int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *rd, int def_qual, const LfqReadsDev *res, const lfq_viterbi_result **out)
 {
     if (!c || !rd || !out || rd->n_reads < 0 || def_qual > LFQ_VIT_MAXQ) {
         return LFQ_ERR_INVALID;

@@ -291,3 +291,33 @@ def test_readset_baq_large_set_chunked_upload(caller):
         assert pai.tobytes() == ai[a * rl:b * rl].tobytes(), a
         assert pad.tobytes() == ad[a * rl:b * rl].tobytes(), a
         assert pfl[:b - a].tobytes() == fl[a:b].tobytes(), a
+
+
+def test_baq_times_fresh_context_then_one_call(caller):
+    """SnvCaller.baq_times (lfq_last_baq_times): all zero on a context that has run no BAQ (one of its own: the session's has);
+    after ReadSet.baq on 65 reads (one more than a wavefront) the input's read and base counts, at least one launch and a
+    finite, positive kernel time"""
+    import math
+    import lofreq_amd as la
+    from lofreq_amd.pileup import ReadSet
+    rng = np.random.default_rng(11)
+    genome = "".join(rng.choice(list("ACGT"), 400))
+    reads = []
+    for i in range(65):
+        rl = 40 + i % 7
+        pos = int(rng.integers(0, len(genome) - rl))
+        reads.append({"pos0": pos, "cigar": [("M", rl)], "seq": la.encode_seq(genome[pos:pos + rl]),
+                      "qual": np.full(rl, 30, np.uint8), "mapq": 60, "reverse": bool(i & 1)})
+    c = la.SnvCaller(0)
+    try:
+        assert c.baq_times() == {"ms_kernels": 0.0, "n_launches": 0, "n_reads": 0, "n_bases": 0}
+        rs = ReadSet(c, reads, genome.encode())
+        rs.baq()
+        t = c.baq_times()
+        rs.close()
+    finally:
+        c.close()
+    assert t["n_reads"] == 65
+    assert t["n_bases"] == sum(len(r["seq"]) for r in reads)
+    assert t["n_launches"] >= 1
+    assert math.isfinite(t["ms_kernels"]) and t["ms_kernels"] > 0

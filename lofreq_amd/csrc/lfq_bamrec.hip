@@ -46,9 +46,72 @@ __device__ __forceinline__ int64_t bam_find_nul(const uint8_t *d, int64_t p, int
     }
 }
 
-/* ---- aux pass: one lane per read walks the aux fields of its record -----------------------------------------------------
- * Every read stays inside [aux start, rec_end): a field whose header, NUL or payload would lie beyond rec_end ends the walk
- * and marks the batch malformed. */
+/* ---- the aux walk: one field a step ---------------------------------------------------------------------------------------------
+ * What both per-read passes (the decode's aux pass, the encode's plan pass) know of an aux field.  This is the only code that reads
+ * an aux header or decides a field's size, and so the one place that keeps a lane inside its record: a field whose header, NUL or
+ * payload would lie beyond `end` is malformed, decided from the offsets before anything past them is read. */
+struct LfqBamAuxField {
+    uint8_t t0, t1, ty;                 /* the tag's two bytes, the type */
+    int64_t at, size;                   /* the payload: its first byte and its bytes (a string's NUL included) */
+    int64_t zlen;                       /* Z / H: the string's length; every other type: -1 */
+};
+
+/* the field at *p (< end); false: malformed.  Otherwise *p is behind the field */
+__device__ __forceinline__ bool bam_aux_next(const uint8_t *d, int64_t *p_io, int64_t end, LfqBamAuxField *F)
+{
+    int64_t p = *p_io;
+    if (end - p < 3) {
+        return false;
+    }
+    F->t0 = d[p];
+    F->t1 = d[p + 1];
+    const uint8_t ty = F->ty = d[p + 2];
+    p += 3;
+    int64_t size = -1, zlen = -1;
+    switch (ty) {
+    case 'A': case 'c': case 'C':
+        size = 1;
+        break;
+    case 's': case 'S':
+        size = 2;
+        break;
+    case 'i': case 'I': case 'f':
+        size = 4;
+        break;
+    case 'Z': case 'H': {
+        const int64_t q = bam_find_nul(d, p, end);
+        if (q < end) {
+            zlen = q - p;
+            size = zlen + 1;
+        }
+        break;
+    }
+    case 'B':
+        if (end - p >= 5) {
+            const uint8_t sub = d[p];
+            const int64_t cnt = (int64_t)d[p + 1] | ((int64_t)d[p + 2] << 8) | ((int64_t)d[p + 3] << 16) | ((int64_t)d[p + 4] << 24);
+            const int64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
+                               : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+            if (es) {
+                size = 5 + es * cnt;
+            }
+        }
+        break;
+    default:
+        break;
+    }
+    if (size < 0 || size > end - p) {
+        return false;
+    }
+    F->at = p;
+    F->size = size;
+    F->zlen = zlen;
+    *p_io = p + size;
+    return true;
+}
+
+/* ---- aux pass: one lane per read walks the aux fields of its record (bam_aux_next); a malformed field ends the walk and marks
+ * the batch malformed */
 __global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamArgs A)
 {
     const int64_t r = (int64_t)blockIdx.x * LFQ_BAM_AUX_READS + threadIdx.x;
@@ -61,61 +124,22 @@ __global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamAr
         int64_t bi = -1, bd = -1;
         bool seen_bi = false, seen_bd = false;
         while (p < end) {
-            if (end - p < 3) {
+            LfqBamAuxField F;
+            if (!bam_aux_next(d, &p, end, &F)) {
                 bad = true;
                 break;
             }
-            const uint8_t t0 = d[p], t1 = d[p + 1], ty = d[p + 2];
-            p += 3;
-            int64_t size = -1, zlen = -1;
-            switch (ty) {
-            case 'A': case 'c': case 'C':
-                size = 1;
-                break;
-            case 's': case 'S':
-                size = 2;
-                break;
-            case 'i': case 'I': case 'f':
-                size = 4;
-                break;
-            case 'Z': case 'H': {
-                const int64_t q = bam_find_nul(d, p, end);
-                if (q < end) {
-                    zlen = q - p;
-                    size = zlen + 1;
-                }
-                break;
-            }
-            case 'B':
-                if (end - p >= 5) {
-                    const uint8_t sub = d[p];
-                    const int64_t cnt = (int64_t)d[p + 1] | ((int64_t)d[p + 2] << 8) | ((int64_t)d[p + 3] << 16) | ((int64_t)d[p + 4] << 24);
-                    const int64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
-                                       : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-                    if (es) {
-                        size = 5 + es * cnt;
-                    }
-                }
-                break;
-            default:
-                break;
-            }
-            if (size < 0 || size > end - p) {
-                bad = true;
-                break;
-            }
-            if (t0 == 'B' && t1 == 'I' && !seen_bi) {       /* the FIRST field of the tag decides (bam_aux_get) */
+            if (F.t0 == 'B' && F.t1 == 'I' && !seen_bi) {   /* the FIRST field of the tag decides (bam_aux_get) */
                 seen_bi = true;
-                if (ty == 'Z' && zlen >= l) {
-                    bi = p;
+                if (F.ty == 'Z' && F.zlen >= l) {
+                    bi = F.at;
                 }
-            } else if (t0 == 'B' && t1 == 'D' && !seen_bd) {
+            } else if (F.t0 == 'B' && F.t1 == 'D' && !seen_bd) {
                 seen_bd = true;
-                if (ty == 'Z' && zlen >= l) {
-                    bd = p;
+                if (F.ty == 'Z' && F.zlen >= l) {
+                    bd = F.at;
                 }
             }
-            p += size;
         }
         if (bad) {
             bi = bd = -1;
@@ -287,39 +311,49 @@ __global__ __launch_bounds__(LFQ_BAM_BASE_CHUNKS) void lfq_bam_bases_kernel(LfqB
     if (A.bd) b16_store(A.bd + b0, vd);
 }
 
-/* ---- host side of the two launches ---------------------------------------------------------------------------------------- */
+/* ---- host side: what the decode and the encode keep on a context, and the upload both begin with --------------------------- */
 struct LfqBamState {
-    uint8_t *d_buf;                     /* records | descriptors | what the aux pass writes (grow-only) */
-    int64_t d_bytes;
-    uint8_t *h_stage;                   /* pinned staging of records that come in pageable memory (grow-only) */
-    int64_t h_bytes;
-    hipEvent_t ev[8];                   /* around the upload, the aux pass, the base pass, the copies back */
-    LfqBamArgs args;                    /* of the decode in flight between lfq_bam_aux and lfq_bam_bases */
-    lfq_bam_decode_times times;
-    struct LfqBamEncState *enc;         /* lfq_readset_encode_bam: its result and buffers (below; created on first use) */
+    uint8_t *d_buf = nullptr;           /* records | descriptors | what the aux or the plan pass writes (grow-only) */
+    int64_t d_bytes = 0;
+    uint8_t *h_stage = nullptr;         /* pinned staging of records that come in pageable memory (grow-only) */
+    int64_t h_bytes = 0;
+    LfqEvPair up_t = {}, kern_t = {}, down_t = {};      /* around a call's copies down, a kernel, the copies back; each is read
+                                                           (after the call's next synchronise) before it is recorded again */
+    /* lfq_readset_create_from_bam */
+    LfqBamArgs args = {};               /* of the decode in flight between lfq_bam_aux and lfq_bam_bases */
+    lfq_bam_decode_times times = {};
+    /* lfq_readset_encode_bam */
+    uint8_t *d_out = nullptr;           /* offsets | tile table | the blob (grow-only) */
+    int64_t d_out_bytes = 0;
+    uint8_t *h_out = nullptr;           /* the blob on the host, pinned (grow-only) */
+    int64_t h_out_bytes = 0;
+    std::vector<int64_t> data_off, src;
+    std::vector<int32_t> pos;
+    std::vector<uint32_t> n_cigar;
+    uint8_t none[16] = {};              /* `data` of an empty result */
+    lfq_bam_encoded result = {};
+    lfq_bam_encode_times enc_times = {};
 };
 
 static LfqBamState *bam_state(lfq_ctx *c)
 {
     if (!c->bam) {
         c->bam = new LfqBamState();
-        memset(c->bam, 0, sizeof(*c->bam));
     }
     return c->bam;
 }
 
-static void bam_enc_release(struct LfqBamEncState *E);
-
 void lfq_bam_release(lfq_ctx *c)
 {
-    if (c->bam) {
-        bam_enc_release(c->bam->enc);
-        if (c->bam->d_buf) (void)hipFree(c->bam->d_buf);
-        if (c->bam->h_stage) (void)hipHostFree(c->bam->h_stage);
-        for (hipEvent_t e : c->bam->ev) {
-            if (e) (void)hipEventDestroy(e);
+    if (LfqBamState *S = c->bam) {
+        if (S->d_buf) (void)hipFree(S->d_buf);
+        if (S->d_out) (void)hipFree(S->d_out);
+        free_pinned(&S->h_stage, &S->h_bytes);
+        free_pinned(&S->h_out, &S->h_out_bytes);
+        for (LfqEvPair *t : {&S->up_t, &S->kern_t, &S->down_t}) {
+            t->destroy();
         }
-        delete c->bam;
+        delete S;
         c->bam = nullptr;
     }
 }
@@ -327,31 +361,27 @@ void lfq_bam_release(lfq_ctx *c)
 void lfq_bam_times_reset(lfq_ctx *c, int64_t n_reads, int64_t n_bases, int64_t n_data_bytes)
 {
     LfqBamState *S = bam_state(c);
-    memset(&S->times, 0, sizeof(S->times));
+    S->times = {};
     S->times.n_reads = n_reads;
     S->times.n_bases = n_bases;
     S->times.n_data_bytes = n_data_bytes;
 }
 
-static float bam_ms(hipEvent_t a, hipEvent_t b)
+/* the pair's milliseconds on top of *acc: a leg of the encode has two parts, the kernels of both calls are two launches */
+static int bam_add_ms(const LfqEvPair &t, double *acc)
 {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f;
+    double ms = 0.0;
+    LFQ_TRY(t.ms(&ms));
+    *acc += ms;
+    return LFQ_OK;
 }
 
 /* records that come in pageable memory: *data becomes their copy in the pinned staging area */
-static int bam_stage(lfq_ctx *c, LfqBamState *S, const uint8_t **data_io, int64_t data_bytes)
+static int bam_stage(LfqBamState *S, const uint8_t **data_io, int64_t data_bytes)
 {
     const uint8_t *data = *data_io;
-    if (data_bytes > S->h_bytes) {
-        if (S->h_stage) (void)hipHostFree(S->h_stage);
-        S->h_stage = nullptr;
-        S->h_bytes = 0;
-        const int64_t want = std::max<int64_t>(data_bytes + data_bytes / 4, 1 << 16);
-        if (hipHostMalloc((void **)&S->h_stage, (size_t)want, hipHostMallocDefault) != hipSuccess) {
-            return LFQ_ERR_NOMEM;
-        }
-        S->h_bytes = want;
+    if (data_bytes > S->h_bytes) {      /* a quarter over the need: batches of about one size do not allocate again */
+        LFQ_TRY(grow_pinned(&S->h_stage, &S->h_bytes, std::max<int64_t>(data_bytes + data_bytes / 4, 1 << 16)));
     }
     /* (a few threads: one copies at a fraction of what the link takes) */
     const unsigned hw = std::max(1u, lfq_cpu_budget() / (unsigned)std::max(lfq_knobs().local_world_size, 1));
@@ -373,37 +403,42 @@ static int bam_stage(lfq_ctx *c, LfqBamState *S, const uint8_t **data_io, int64_
     return LFQ_OK;
 }
 
+/* the leg both calls begin with, inside up_t: d_buf grown to `total`; the records down, behind first_shift bytes of room so that a
+ * record keeps the alignment it has in the caller's buffer, through the staging area unless they lie in pinned memory; the call's
+ * per-read descriptors down to o_desc; the 256 bytes of the error words at o_err cleared */
+static int bam_upload(lfq_ctx *c, LfqBamState *S, const LfqBamIn &in, int64_t total, int64_t o_desc, const void *desc,
+                      size_t desc_bytes, int64_t o_err)
+{
+    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
+    const uint8_t *data = in.data;
+    if (!in.pinned) {
+        LFQ_TRY(bam_stage(S, &data, in.data_bytes));
+    }
+    hipStream_t st = c->stream;
+    LFQ_TRY(S->up_t.begin(st));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + in.first_shift, data, (size_t)in.data_bytes, hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemsetAsync(S->d_buf + o_err, 0, 256, st));
+    return S->up_t.end(st);
+}
+
+/* ---- host side of the decode's two launches ---------------------------------------------------------------------------------- */
 /* records down, aux pass, its verdict back: flags_out[n], *any_bi / *any_bd; LFQ_ERR_INVALID for a malformed aux field.
- * data[0 .. data_bytes) are the records, first_shift (0 .. 15) bytes of room are left in front of them on the device so that a
- * record keeps the alignment it has in the caller's buffer; desc = seq_off[n + 1] | seq_src[n] | rec_end[n], the last two as
- * offsets from data - first_shift.  Blocks. */
-int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_shift, bool data_pinned, const int64_t *desc,
-                int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi, int *any_bd)
+ * desc = seq_off[n + 1] | seq_src[n] | rec_end[n], the last two as offsets from in.data - in.first_shift.  Blocks. */
+int lfq_bam_aux(lfq_ctx *c, const LfqBamIn &in, const int64_t *desc, int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi,
+                int *any_bd)
 {
     LfqBamState *S = bam_state(c);
     LFQ_TRY_HIP(hipSetDevice(c->device));
-    for (hipEvent_t &e : S->ev) {
-        if (!e) {
-            LFQ_TRY_HIP(hipEventCreate(&e));
-        }
-    }
-    const int64_t o_desc = lfq_al(first_shift + data_bytes + 16), o_bi = o_desc + lfq_al((3 * n + 1) * 8), o_bd = o_bi + lfq_al(n * 8),
-                  o_err = o_bd + lfq_al(n * 8), o_fl = o_err + 256, o_tile = o_fl + lfq_al(n),
+    const int64_t o_desc = lfq_al(in.first_shift + in.data_bytes + 16), o_bi = o_desc + lfq_al((3 * n + 1) * 8),
+                  o_bd = o_bi + lfq_al(n * 8), o_err = o_bd + lfq_al(n * 8), o_fl = o_err + 256, o_tile = o_fl + lfq_al(n),
                   n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), total = o_tile + lfq_al(n_tiles * 8);
-    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
-    if (!data_pinned) {
-        LFQ_TRY(bam_stage(c, S, &data, data_bytes));
-    }
     LfqPin<int32_t> verdict(c, 4);
     LFQ_PIN_OK(verdict);
     LfqPin<uint8_t> fl(c, (size_t)n);
     LFQ_PIN_OK(fl);
+    LFQ_TRY(bam_upload(c, S, in, total, o_desc, desc, (size_t)(3 * n + 1) * 8, o_err));
     hipStream_t st = c->stream;
-    LFQ_TRY_HIP(hipEventRecord(S->ev[0], st));
-    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + first_shift, data, (size_t)data_bytes, hipMemcpyHostToDevice, st));
-    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_desc, desc, (size_t)(3 * n + 1) * 8, hipMemcpyHostToDevice, st));
-    LFQ_TRY_HIP(hipMemsetAsync(S->d_buf + o_err, 0, 256, st));
-    LFQ_TRY_HIP(hipEventRecord(S->ev[1], st));
     LfqBamArgs &A = S->args;
     memset(&A, 0, sizeof(A));
     A.data = S->d_buf;
@@ -417,17 +452,17 @@ int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_s
     A.tile_read = (int64_t *)(S->d_buf + o_tile);
     A.n_reads = n;
     A.n_bases = nb;
-    LFQ_TRY_HIP(hipEventRecord(S->ev[2], st));
+    LFQ_TRY(S->kern_t.begin(st));
     hipLaunchKernelGGL(lfq_bam_aux_kernel, dim3((unsigned)((n + LFQ_BAM_AUX_READS - 1) / LFQ_BAM_AUX_READS)),
                        dim3(LFQ_BAM_AUX_READS), 0, st, A);
     LFQ_TRY_HIP(hipGetLastError());
-    LFQ_TRY_HIP(hipEventRecord(S->ev[3], st));
+    LFQ_TRY(S->kern_t.end(st));
     S->times.n_launches += 1;
     LFQ_TRY_HIP(hipMemcpyAsync(verdict.data(), A.err, 16, hipMemcpyDeviceToHost, st));
     LFQ_TRY_HIP(hipMemcpyAsync(fl.data(), A.flags, (size_t)n, hipMemcpyDeviceToHost, st));
     LFQ_TRY_HIP(hipStreamSynchronize(st));
-    S->times.upload_ms = bam_ms(S->ev[0], S->ev[1]);
-    S->times.kernels_ms = bam_ms(S->ev[2], S->ev[3]);
+    LFQ_TRY(bam_add_ms(S->up_t, &S->times.upload_ms));
+    LFQ_TRY(bam_add_ms(S->kern_t, &S->times.kernels_ms));
     if (verdict[2]) {
         return LFQ_ERR_INVALID;
     }
@@ -452,12 +487,12 @@ int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, ui
     hipStream_t st = c->stream;
     A.seq = d_seq; A.qual = d_qual; A.bi = d_bi; A.bd = d_bd;
     const int64_t per_wg = (int64_t)LFQ_BAM_BASE_CHUNKS * 16;
-    LFQ_TRY_HIP(hipEventRecord(S->ev[4], st));
+    LFQ_TRY(S->kern_t.begin(st));
     hipLaunchKernelGGL(lfq_bam_bases_kernel, dim3((unsigned)((nb + per_wg - 1) / per_wg)), dim3(LFQ_BAM_BASE_CHUNKS), 0, st, A);
     LFQ_TRY_HIP(hipGetLastError());
-    LFQ_TRY_HIP(hipEventRecord(S->ev[5], st));
+    LFQ_TRY(S->kern_t.end(st));
     S->times.n_launches += 1;
-    LFQ_TRY_HIP(hipEventRecord(S->ev[6], st));
+    LFQ_TRY(S->down_t.begin(st));
     LFQ_TRY_HIP(hipMemcpyAsync(h_seq, d_seq, (size_t)nb, hipMemcpyDeviceToHost, st));
     LFQ_TRY_HIP(hipMemcpyAsync(h_qual, d_qual, (size_t)nb, hipMemcpyDeviceToHost, st));
     if (d_bi) {
@@ -466,11 +501,10 @@ int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, ui
     if (d_bd) {
         LFQ_TRY_HIP(hipMemcpyAsync(h_bd, d_bd, (size_t)nb, hipMemcpyDeviceToHost, st));
     }
-    LFQ_TRY_HIP(hipEventRecord(S->ev[7], st));
+    LFQ_TRY(S->down_t.end(st));
     LFQ_TRY_HIP(hipStreamSynchronize(st));
-    S->times.kernels_ms += bam_ms(S->ev[4], S->ev[5]);
-    S->times.download_ms = bam_ms(S->ev[6], S->ev[7]);
-    return LFQ_OK;
+    LFQ_TRY(bam_add_ms(S->kern_t, &S->times.kernels_ms));
+    return bam_add_ms(S->down_t, &S->times.download_ms);
 }
 
 extern "C" int lfq_last_bam_decode_times(lfq_ctx *c, lfq_bam_decode_times *t)
@@ -518,8 +552,8 @@ struct LfqBamEncArgs {
     int32_t uniform;
 };
 
-/* ---- plan pass: the aux walk of lfq_bam_aux_kernel with the reference's deletion and append rules ---------------------------------
- * No read leaves [aux start, rec_end) */
+/* ---- plan pass: one lane per read walks the aux fields of its record (bam_aux_next) under the reference's deletion and append
+ * rules */
 __global__ __launch_bounds__(LFQ_BAM_PLAN_READS) void lfq_bam_plan_kernel(LfqBamEncArgs A)
 {
     const int64_t j = (int64_t)blockIdx.x * LFQ_BAM_PLAN_READS + threadIdx.x;
@@ -546,51 +580,15 @@ __global__ __launch_bounds__(LFQ_BAM_PLAN_READS) void lfq_bam_plan_kernel(LfqBam
         int nk = 0;
         int64_t kept = 0, run = aux0, p = aux0;
         while (p < end) {
-            if (end - p < 3) {
+            const int64_t f0 = p;
+            LfqBamAuxField F;
+            if (!bam_aux_next(d, &p, end, &F)) {
                 bad = true;
                 break;
             }
-            const uint8_t t0 = d[p], t1 = d[p + 1], ty = d[p + 2];
-            p += 3;
-            int64_t size = -1;
-            switch (ty) {
-            case 'A': case 'c': case 'C':
-                size = 1;
-                break;
-            case 's': case 'S':
-                size = 2;
-                break;
-            case 'i': case 'I': case 'f':
-                size = 4;
-                break;
-            case 'Z': case 'H': {
-                const int64_t q = bam_find_nul(d, p, end);
-                if (q < end) {
-                    size = q - p + 1;
-                }
-                break;
-            }
-            case 'B':
-                if (end - p >= 5) {
-                    const uint8_t sub = d[p];
-                    const int64_t cnt = (int64_t)d[p + 1] | ((int64_t)d[p + 2] << 8) | ((int64_t)d[p + 3] << 16) | ((int64_t)d[p + 4] << 24);
-                    const int64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
-                                       : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-                    if (es) {
-                        size = 5 + es * cnt;
-                    }
-                }
-                break;
-            default:
-                break;
-            }
-            if (size < 0 || size > end - p) {
-                bad = true;
-                break;
-            }
-            const int64_t f0 = p - 3, f1 = p + size;
+            const int64_t f1 = p;
             int id = -1;
-            switch (((uint32_t)t0 << 8) | t1) {
+            switch (((uint32_t)F.t0 << 8) | F.t1) {
             case ('N' << 8) | 'M': id = 0; break;
             case ('M' << 8) | 'C': id = 1; break;
             case ('M' << 8) | 'D': id = 2; break;
@@ -613,7 +611,7 @@ __global__ __launch_bounds__(LFQ_BAM_PLAN_READS) void lfq_bam_plan_kernel(LfqBam
                     if (alnq) {                             /* bam_md_ext.c:297-314 */
                         seen |= 1u << id;
                         const bool selected = id == 4 ? put_lb : put_idaq;
-                        if (!keep_existing && selected && ty == 'Z') {
+                        if (!keep_existing && selected && F.ty == 'Z') {
                             del = true;
                         } else {
                             present |= 1u << (id - 4);
@@ -633,7 +631,6 @@ __global__ __launch_bounds__(LFQ_BAM_PLAN_READS) void lfq_bam_plan_kernel(LfqBam
                 }
                 run = f1;
             }
-            p = f1;
         }
         uint32_t app = 0;
         if (bad) {
@@ -787,92 +784,50 @@ __global__ __launch_bounds__(LFQ_BAM_COPY_CHUNKS) void lfq_bam_copy_kernel(LfqBa
     b16_store(A.out + b0, acc);
 }
 
-/* ---- host side --------------------------------------------------------------------------------------------------------------------- */
-struct LfqBamEncState {
-    uint8_t *d_out = nullptr;           /* offsets | tile table | the blob (grow-only) */
-    int64_t d_out_bytes = 0;
-    uint8_t *h_out = nullptr;           /* the blob on the host, pinned (grow-only) */
-    int64_t h_out_bytes = 0;
-    hipEvent_t ev[8] = {};              /* around the upload, the plan pass, the offsets' way down, the copy pass, the blob's way back */
-    std::vector<int64_t> data_off, src;
-    std::vector<int32_t> pos;
-    std::vector<uint32_t> n_cigar;
-    uint8_t none[16] = {};              /* `data` of an empty result */
-    lfq_bam_encoded result = {};
-    lfq_bam_encode_times times = {};
-};
-
-static void bam_enc_release(LfqBamEncState *E)
+/* ---- host side of the encode's two launches ------------------------------------------------------------------------------------------ */
+/* the context's result: n records in `data`, beside them what the state's vectors hold */
+static int bam_publish(LfqBamState *S, int64_t n, const uint8_t *data, const lfq_bam_encoded **out)
 {
-    if (E) {
-        if (E->d_out) (void)hipFree(E->d_out);
-        if (E->h_out) (void)hipHostFree(E->h_out);
-        for (hipEvent_t e : E->ev) {
-            if (e) (void)hipEventDestroy(e);
-        }
-        delete E;
-    }
-}
-
-static LfqBamEncState *bam_enc_state(lfq_ctx *c)
-{
-    LfqBamState *S = bam_state(c);
-    if (!S->enc) {
-        S->enc = new LfqBamEncState();
-    }
-    return S->enc;
+    S->result.n_reads = n;
+    S->result.data = data;
+    S->result.data_off = S->data_off.data();
+    S->result.src = S->src.data();
+    S->result.pos = S->pos.data();
+    S->result.n_cigar = S->n_cigar.data();
+    *out = &S->result;
+    return LFQ_OK;
 }
 
 int lfq_bam_encode_empty(lfq_ctx *c, const lfq_bam_encoded **out)
 {
-    LfqBamEncState *E = bam_enc_state(c);
-    memset(&E->times, 0, sizeof(E->times));
-    E->data_off.assign(1, 0);
-    E->src.assign(1, 0);
-    E->pos.assign(1, 0);
-    E->n_cigar.assign(1, 0);
-    E->result.n_reads = 0;
-    E->result.data = E->none;
-    E->result.data_off = E->data_off.data();
-    E->result.src = E->src.data();
-    E->result.pos = E->pos.data();
-    E->result.n_cigar = E->n_cigar.data();
-    *out = &E->result;
-    return LFQ_OK;
+    LfqBamState *S = bam_state(c);
+    S->enc_times = {};
+    S->data_off.assign(1, 0);
+    S->src.assign(1, 0);
+    S->pos.assign(1, 0);
+    S->n_cigar.assign(1, 0);
+    return bam_publish(S, 0, S->none, out);
 }
 
 /* records down, plan pass, lengths back, offsets down, copy pass, blob back.  Blocks. */
 int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **out)
 {
     LfqBamState *S = bam_state(c);
-    LfqBamEncState *E = bam_enc_state(c);
     const int64_t n = in->n;
     LFQ_TRY_HIP(hipSetDevice(c->device));
-    for (hipEvent_t &e : E->ev) {
-        if (!e) {
-            LFQ_TRY_HIP(hipEventCreate(&e));
-        }
-    }
-    memset(&E->times, 0, sizeof(E->times));
-    E->times.n_reads = n;
-    E->times.n_in_bytes = in->data_bytes;
-    const int64_t o_reads = lfq_al(in->first_shift + in->data_bytes + 16), o_plan = o_reads + lfq_al(n * (int64_t)sizeof(LfqBamRead)),
-                  o_len = o_plan + lfq_al(n * (int64_t)sizeof(LfqBamPlan)), o_err = o_len + lfq_al(n * 8), total = o_err + 256;
-    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
-    const uint8_t *data = in->data;
-    if (!in->data_pinned) {
-        LFQ_TRY(bam_stage(c, S, &data, in->data_bytes));
-    }
+    lfq_bam_encode_times &T = S->enc_times;
+    T = {};
+    T.n_reads = n;
+    T.n_in_bytes = in->recs.data_bytes;
+    const int64_t o_reads = lfq_al(in->recs.first_shift + in->recs.data_bytes + 16),
+                  o_plan = o_reads + lfq_al(n * (int64_t)sizeof(LfqBamRead)), o_len = o_plan + lfq_al(n * (int64_t)sizeof(LfqBamPlan)),
+                  o_err = o_len + lfq_al(n * 8), total = o_err + 256;
     LfqPin<int32_t> verdict(c, 4);
     LFQ_PIN_OK(verdict);
     LfqPin<int64_t> lens(c, (size_t)n);
     LFQ_PIN_OK(lens);
+    LFQ_TRY(bam_upload(c, S, in->recs, total, o_reads, in->reads, (size_t)n * sizeof(LfqBamRead), o_err));
     hipStream_t st = c->stream;
-    LFQ_TRY_HIP(hipEventRecord(E->ev[0], st));
-    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + in->first_shift, data, (size_t)in->data_bytes, hipMemcpyHostToDevice, st));
-    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_reads, in->reads, (size_t)n * sizeof(LfqBamRead), hipMemcpyHostToDevice, st));
-    LFQ_TRY_HIP(hipMemsetAsync(S->d_buf + o_err, 0, 256, st));
-    LFQ_TRY_HIP(hipEventRecord(E->ev[1], st));
     LfqBamEncArgs A;
     memset(&A, 0, sizeof(A));
     A.data = S->d_buf;
@@ -885,81 +840,69 @@ int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **ou
     A.n_reads = n;
     A.what = in->what;
     A.uniform = in->uniform ? 1 : 0;
-    LFQ_TRY_HIP(hipEventRecord(E->ev[2], st));
+    LFQ_TRY(S->kern_t.begin(st));
     hipLaunchKernelGGL(lfq_bam_plan_kernel, dim3((unsigned)((n + LFQ_BAM_PLAN_READS - 1) / LFQ_BAM_PLAN_READS)),
                        dim3(LFQ_BAM_PLAN_READS), 0, st, A);
     LFQ_TRY_HIP(hipGetLastError());
-    LFQ_TRY_HIP(hipEventRecord(E->ev[3], st));
-    E->times.n_launches += 1;
+    LFQ_TRY(S->kern_t.end(st));
+    T.n_launches += 1;
     LFQ_TRY_HIP(hipMemcpyAsync(verdict.data(), A.err, 16, hipMemcpyDeviceToHost, st));
     LFQ_TRY_HIP(hipMemcpyAsync(lens.data(), A.out_len, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     LFQ_TRY_HIP(hipStreamSynchronize(st));
-    E->times.upload_ms = bam_ms(E->ev[0], E->ev[1]);
-    E->times.kernels_ms = bam_ms(E->ev[2], E->ev[3]);
+    LFQ_TRY(bam_add_ms(S->up_t, &T.upload_ms));
+    LFQ_TRY(bam_add_ms(S->kern_t, &T.kernels_ms));
     if (verdict[0]) {
         return LFQ_ERR_INVALID;
     }
     /* offsets in read-set order, and for every tile of the copy pass the record that holds its first byte */
     const int64_t tile = (int64_t)LFQ_BAM_COPY_CHUNKS * 16;
-    E->data_off.resize((size_t)n + 1);
-    E->data_off[0] = 0;
+    S->data_off.resize((size_t)n + 1);
+    S->data_off[0] = 0;
     for (int64_t j = 0; j < n; j++) {
-        E->data_off[(size_t)j + 1] = E->data_off[(size_t)j] + lens[(size_t)j];
+        S->data_off[(size_t)j + 1] = S->data_off[(size_t)j] + lens[(size_t)j];
     }
-    const int64_t n_out = E->data_off[(size_t)n], n_tiles = (n_out + tile - 1) / tile;
+    const int64_t n_out = S->data_off[(size_t)n], n_tiles = (n_out + tile - 1) / tile;
     LfqPin<int64_t> down(c, (size_t)(n + 1 + n_tiles));
     LFQ_PIN_OK(down);
-    memcpy(down.data(), E->data_off.data(), (size_t)(n + 1) * 8);
+    memcpy(down.data(), S->data_off.data(), (size_t)(n + 1) * 8);
     for (int64_t t = 0, j = 0; t < n_tiles; t++) {
-        while (E->data_off[(size_t)j + 1] <= t * tile) {    /* (t * tile < n_out = data_off[n]: j stays below n) */
+        while (S->data_off[(size_t)j + 1] <= t * tile) {    /* (t * tile < n_out = data_off[n]: j stays below n) */
             j++;
         }
         down[(size_t)(n + 1 + t)] = j;
     }
     const int64_t o_off = 0, o_tile = lfq_al((n + 1) * 8), o_blob = o_tile + lfq_al(n_tiles * 8), out_total = o_blob + lfq_al(n_out + 16);
-    LFQ_TRY(grow(&E->d_out, &E->d_out_bytes, out_total));
-    if (n_out + 16 > E->h_out_bytes) {
-        if (E->h_out) (void)hipHostFree(E->h_out);
-        E->h_out = nullptr;
-        E->h_out_bytes = 0;
-        const int64_t want = std::max<int64_t>(n_out + n_out / 4 + 16, 1 << 16);
-        if (hipHostMalloc((void **)&E->h_out, (size_t)want, hipHostMallocDefault) != hipSuccess) {
-            return LFQ_ERR_NOMEM;
-        }
-        E->h_out_bytes = want;
+    LFQ_TRY(grow(&S->d_out, &S->d_out_bytes, out_total));
+    if (n_out + 16 > S->h_out_bytes) {  /* a quarter over the need, as the staging area */
+        LFQ_TRY(grow_pinned(&S->h_out, &S->h_out_bytes, std::max<int64_t>(n_out + n_out / 4 + 16, 1 << 16)));
     }
     if (n_out > 0) {
-        A.out_off = (const int64_t *)(E->d_out + o_off);
-        A.tile_rec = (const int64_t *)(E->d_out + o_tile);
-        A.out = E->d_out + o_blob;
+        A.out_off = (const int64_t *)(S->d_out + o_off);
+        A.tile_rec = (const int64_t *)(S->d_out + o_tile);
+        A.out = S->d_out + o_blob;
         A.n_out = n_out;
-        LFQ_TRY_HIP(hipEventRecord(E->ev[4], st));
-        LFQ_TRY_HIP(hipMemcpyAsync(E->d_out + o_off, down.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-        LFQ_TRY_HIP(hipMemcpyAsync(E->d_out + o_tile, down.data() + n + 1, (size_t)n_tiles * 8, hipMemcpyHostToDevice, st));
-        LFQ_TRY_HIP(hipEventRecord(E->ev[5], st));
+        LFQ_TRY(S->up_t.begin(st));
+        LFQ_TRY_HIP(hipMemcpyAsync(S->d_out + o_off, down.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+        LFQ_TRY_HIP(hipMemcpyAsync(S->d_out + o_tile, down.data() + n + 1, (size_t)n_tiles * 8, hipMemcpyHostToDevice, st));
+        LFQ_TRY(S->up_t.end(st));
+        LFQ_TRY(S->kern_t.begin(st));
         hipLaunchKernelGGL(lfq_bam_copy_kernel, dim3((unsigned)n_tiles), dim3(LFQ_BAM_COPY_CHUNKS), 0, st, A);
         LFQ_TRY_HIP(hipGetLastError());
-        LFQ_TRY_HIP(hipEventRecord(E->ev[6], st));
-        E->times.n_launches += 1;
-        LFQ_TRY_HIP(hipMemcpyAsync(E->h_out, A.out, (size_t)n_out, hipMemcpyDeviceToHost, st));
-        LFQ_TRY_HIP(hipEventRecord(E->ev[7], st));
+        LFQ_TRY(S->kern_t.end(st));
+        T.n_launches += 1;
+        LFQ_TRY(S->down_t.begin(st));
+        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out, A.out, (size_t)n_out, hipMemcpyDeviceToHost, st));
+        LFQ_TRY(S->down_t.end(st));
         LFQ_TRY_HIP(hipStreamSynchronize(st));
-        E->times.upload_ms += bam_ms(E->ev[4], E->ev[5]);
-        E->times.kernels_ms += bam_ms(E->ev[5], E->ev[6]);
-        E->times.download_ms = bam_ms(E->ev[6], E->ev[7]);
+        LFQ_TRY(bam_add_ms(S->up_t, &T.upload_ms));
+        LFQ_TRY(bam_add_ms(S->kern_t, &T.kernels_ms));
+        LFQ_TRY(bam_add_ms(S->down_t, &T.download_ms));
     }
-    E->times.n_out_bytes = n_out;
-    E->src.assign(in->src, in->src + n);
-    E->pos.assign(in->pos, in->pos + n);
-    E->n_cigar.assign(in->n_cigar, in->n_cigar + n);
-    E->result.n_reads = n;
-    E->result.data = E->h_out;
-    E->result.data_off = E->data_off.data();
-    E->result.src = E->src.data();
-    E->result.pos = E->pos.data();
-    E->result.n_cigar = E->n_cigar.data();
-    *out = &E->result;
-    return LFQ_OK;
+    T.n_out_bytes = n_out;
+    S->src.assign(in->src, in->src + n);
+    S->pos.assign(in->pos, in->pos + n);
+    S->n_cigar.assign(in->n_cigar, in->n_cigar + n);
+    return bam_publish(S, n, S->h_out, out);
 }
 
 extern "C" int lfq_last_bam_encode_times(lfq_ctx *c, lfq_bam_encode_times *t)
@@ -967,6 +910,6 @@ extern "C" int lfq_last_bam_encode_times(lfq_ctx *c, lfq_bam_encode_times *t)
     if (!c || !t) {
         return LFQ_ERR_INVALID;
     }
-    *t = bam_enc_state(c)->times;
+    *t = bam_state(c)->enc_times;
     return LFQ_OK;
 }

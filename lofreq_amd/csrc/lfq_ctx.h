@@ -545,16 +545,24 @@ int lfq_viterbi_run(lfq_ctx *c, const lfq_baq_reads *reads, int def_qual, const 
 /* dst[k][new order] = src[k][old order] for up to four per-base arrays; returns when the kernel is done */
 int lfq_viterbi_permute(lfq_ctx *c, int64_t n_reads, int64_t n_bases, const int64_t *d_new_off, const int64_t *old_start,
                         int n_arrays, const uint8_t *const *src, uint8_t *const *dst);
-/* lfq_bamrec.hip, for lfq_readset_create_from_bam (lfq_readset.hip): upload + aux pass, then the base pass into a read set's
- * device arrays and the copies back; both block */
+/* lfq_bamrec.hip.  The records of an lfq_bam_records as both calls send them down (lfq_readset.hip builds it once per call) */
+struct LfqBamIn {
+    const uint8_t *data;                /* the first record's first byte */
+    int64_t data_bytes;                 /* ... to the last record's end */
+    int first_shift;                    /* data & 15: the room in front of the records on the device, so that a record keeps the
+                                           alignment it has in the caller's memory */
+    bool pinned;                        /* data lies in pinned host memory: no staging copy */
+};
+/* for lfq_readset_create_from_bam (lfq_readset.hip): upload + aux pass, then the base pass into a read set's device arrays and the
+ * copies back; both block */
 void lfq_bam_release(lfq_ctx *c);
 void lfq_bam_times_reset(lfq_ctx *c, int64_t n_reads, int64_t n_bases, int64_t n_data_bytes);
-int lfq_bam_aux(lfq_ctx *c, const uint8_t *data, int64_t data_bytes, int first_shift, bool data_pinned, const int64_t *desc,
-                int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi, int *any_bd);
+int lfq_bam_aux(lfq_ctx *c, const LfqBamIn &in, const int64_t *desc, int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi,
+                int *any_bd);
 int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, uint8_t *d_bd, uint8_t *h_seq, uint8_t *h_qual,
                   uint8_t *h_bi, uint8_t *h_bd);
-/* lfq_bamrec.hip, for lfq_readset_encode_bam (lfq_readset.hip): the records rewritten on the device.  One LfqBamRead per read of
- * the read set, in its order; rec / end are offsets from data - first_shift, as for the decode */
+/* for lfq_readset_encode_bam (lfq_readset.hip): the records rewritten on the device.  One LfqBamRead per read of the read set, in
+ * its order; rec / end are offsets from data - first_shift, as for the decode */
 struct LfqBamRead {
     int64_t rec, end;                   /* the read's record: its first byte (read_name) and one past its last */
     int32_t l_qseq;
@@ -563,10 +571,7 @@ struct LfqBamRead {
     uint32_t pad_;
 };
 struct LfqBamEncIn {
-    const uint8_t *data;
-    int64_t data_bytes;
-    int first_shift;
-    bool data_pinned;
+    LfqBamIn recs;
     const LfqBamRead *reads;            /* [n] */
     int64_t n;
     unsigned what;                      /* LFQ_BAM_* */

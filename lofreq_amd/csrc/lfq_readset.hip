@@ -3093,6 +3093,40 @@ int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset *
     return LFQ_OK;
 }
 
+/* What both BAM entries refuse of an lfq_bam_records before a device is touched (include/lofreq_amd.h): n_reads < 0, a null
+ * per-read array, and per record decreasing offsets, a negative length or fewer bytes than its fixed part.  Each entry's own:
+ * the decode needs `ref`, the encode refuses a record of more than max_record bytes. */
+static int bam_records_check(const lfq_bam_records *recs, bool need_ref, int64_t max_record)
+{
+    const int64_t n = recs->n_reads;
+    if (n < 0 || (n > 0 && (!recs->data || !recs->data_off || !recs->pos || !recs->flag || !recs->mapq || !recs->l_qname
+                            || !recs->n_cigar || !recs->l_qseq || (need_ref && !recs->ref)))) {
+        return LFQ_ERR_INVALID;
+    }
+    for (int64_t r = 0; r < n; r++) {
+        const int64_t o0 = recs->data_off[r], o1 = recs->data_off[r + 1], l = recs->l_qseq[r];
+        if (o1 < o0 || o1 - o0 > max_record || l < 0
+            || o1 - o0 < (int64_t)recs->l_qname[r] + 4 * (int64_t)recs->n_cigar[r] + (l + 1) / 2 + l) {
+            return LFQ_ERR_INVALID;
+        }
+    }
+    return LFQ_OK;
+}
+
+/* the records of a checked lfq_bam_records as they go down: byte data_off[r] of recs->data lies at data_off[r] - data_off[0] +
+ * first_shift of the device buffer.  (After hipSetDevice: lfq_is_pinned asks the runtime.) */
+static LfqBamIn bam_records_in(const lfq_bam_records *recs)
+{
+    LfqBamIn in = {nullptr, 0, 0, true};
+    if (recs->n_reads > 0) {
+        in.data = recs->data + recs->data_off[0];
+        in.data_bytes = recs->data_off[recs->n_reads] - recs->data_off[0];
+        in.first_shift = (int)((uintptr_t)in.data & 15);
+        in.pinned = lfq_is_pinned(in.data);
+    }
+    return in;
+}
+
 /* The read set of BAM records as they lie in memory (bam1_t.data): what lfq_region_add_read's loop and lfq_readset_create build
  * from them, with the per-base work -- nibbles -> base codes, qualities, the BI / BD strings found among the aux fields -- done
  * by the two launches of lfq_bamrec.hip.  The host reads per READ only: descriptor checks, prefix sums, the CIGAR words.  *out
@@ -3100,35 +3134,28 @@ int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset *
 int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_readset **out)
 {
     if (out) *out = nullptr;
-    if (!c || !recs || !out || recs->n_reads < 0) {
+    if (!c || !recs || !out) {
         return LFQ_ERR_INVALID;
     }
+    LFQ_TRY(bam_records_check(recs, true, INT64_MAX));
     const int64_t n = recs->n_reads;
-    if (n > 0 && (!recs->data || !recs->data_off || !recs->pos || !recs->flag || !recs->mapq || !recs->l_qname || !recs->n_cigar
-                  || !recs->l_qseq || !recs->ref)) {
-        return LFQ_ERR_INVALID;
-    }
     std::unique_ptr<LfqReadsetOwned> own(new LfqReadsetOwned());
     own->cigar_off.resize((size_t)n + 1);
     own->seq_off.resize((size_t)n + 1);
     own->cigar_off[0] = own->seq_off[0] = 0;
     for (int64_t r = 0; r < n; r++) {
-        const int64_t o0 = recs->data_off[r], o1 = recs->data_off[r + 1], l = recs->l_qseq[r];
-        if (o1 < o0 || l < 0 || o1 - o0 < (int64_t)recs->l_qname[r] + 4 * (int64_t)recs->n_cigar[r] + (l + 1) / 2 + l) {
-            return LFQ_ERR_INVALID;
-        }
         own->cigar_off[(size_t)r + 1] = own->cigar_off[(size_t)r] + recs->n_cigar[r];
-        own->seq_off[(size_t)r + 1] = own->seq_off[(size_t)r] + l;
+        own->seq_off[(size_t)r + 1] = own->seq_off[(size_t)r] + recs->l_qseq[r];
     }
-    const int64_t nb = own->seq_off[(size_t)n], first = n > 0 ? recs->data_off[0] : 0,
-                  data_bytes = n > 0 ? recs->data_off[n] - first : 0;
+    const int64_t nb = own->seq_off[(size_t)n];
     own->pos.resize((size_t)std::max<int64_t>(n, 1));
     own->mapq.resize((size_t)std::max<int64_t>(n, 1));
     own->reverse.resize((size_t)std::max<int64_t>(n, 1));
     own->flags.resize((size_t)std::max<int64_t>(n, 1));
     own->cigar.resize((size_t)own->cigar_off[(size_t)n] + 1);
     LFQ_TRY_HIP(hipSetDevice(c->device));
-    lfq_bam_times_reset(c, n, nb, data_bytes);
+    const LfqBamIn in = bam_records_in(recs);
+    lfq_bam_times_reset(c, n, nb, in.data_bytes);
     lfq_pileup_reads pr;
     memset(&pr, 0, sizeof(pr));
     pr.n_reads = n;
@@ -3140,9 +3167,7 @@ int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_rea
         *out = es;
         return LFQ_OK;
     }
-    /* device offsets: the records keep the alignment they have in the caller's memory */
-    const uint8_t *data = recs->data + first;
-    const int first_shift = (int)((uintptr_t)data & 15);
+    const int64_t first = recs->data_off[0];
     LfqPin<int64_t> desc(c, (size_t)(3 * n + 1));       /* seq_off[n + 1] | seq_src[n] | rec_end[n] */
     LFQ_PIN_OK(desc);
     memcpy(desc.data(), own->seq_off.data(), (size_t)(n + 1) * sizeof(int64_t));
@@ -3155,15 +3180,14 @@ int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_rea
             o->mapq[(size_t)r] = recs->mapq[r];
             o->reverse[(size_t)r] = (uint8_t)((recs->flag[r] >> 4) & 1);
             if (nc > 0) {
-                memcpy(o->cigar.data() + o->cigar_off[(size_t)r], data + at, (size_t)nc * 4);
+                memcpy(o->cigar.data() + o->cigar_off[(size_t)r], in.data + at, (size_t)nc * 4);
             }
-            seq_src[r] = first_shift + at + 4 * nc;
-            rec_end[r] = first_shift + recs->data_off[r + 1] - first;
+            seq_src[r] = in.first_shift + at + 4 * nc;
+            rec_end[r] = in.first_shift + recs->data_off[r + 1] - first;
         }
     });
     int any_bi = 0, any_bd = 0;
-    LFQ_TRY(lfq_bam_aux(c, data, data_bytes, first_shift, lfq_is_pinned(data), desc.data(), n, nb, own->flags.data(), &any_bi,
-                        &any_bd));
+    LFQ_TRY(lfq_bam_aux(c, in, desc.data(), n, nb, own->flags.data(), &any_bi, &any_bd));
     /* the pinned landing area of the per-base arrays, from the context's cache; the host views of the read set point into it */
     const size_t stride = (size_t)lfq_al(nb + 16);
     own->pin_bases = (uint8_t *)rs_cache_take(c, LFQ_RSC_PINBASES, stride * (size_t)(2 + any_bi + any_bd), &own->pin_cap);
@@ -3245,18 +3269,8 @@ int lfq_readset_encode_bam(lfq_ctx *c, lfq_readset *rs, const lfq_bam_records *r
     if (what == 0 || (what & ~known) || ((what & LFQ_BAM_KEEP_EXISTING) && !(what & (LFQ_BAM_PUT_LB | LFQ_BAM_PUT_IDAQ)))) {
         return LFQ_ERR_INVALID;
     }
+    LFQ_TRY(bam_records_check(recs, false, INT32_MAX));     /* (the plan's ranges are int32 offsets in a record) */
     const int64_t n = recs->n_reads;
-    if (n < 0 || (n > 0 && (!recs->data || !recs->data_off || !recs->pos || !recs->flag || !recs->mapq || !recs->l_qname
-                            || !recs->n_cigar || !recs->l_qseq))) {
-        return LFQ_ERR_INVALID;
-    }
-    for (int64_t r = 0; r < n; r++) {
-        const int64_t o0 = recs->data_off[r], o1 = recs->data_off[r + 1], l = recs->l_qseq[r];
-        if (o1 < o0 || o1 - o0 > INT32_MAX || l < 0
-            || o1 - o0 < (int64_t)recs->l_qname[r] + 4 * (int64_t)recs->n_cigar[r] + (l + 1) / 2 + l) {
-            return LFQ_ERR_INVALID;
-        }
-    }
     if (rs->c != c || rs->n != n) {
         return LFQ_ERR_INVALID;
     }
@@ -3281,18 +3295,14 @@ int lfq_readset_encode_bam(lfq_ctx *c, lfq_readset *rs, const lfq_bam_records *r
     if (n == 0) {
         return lfq_bam_encode_empty(c, out);
     }
-    const int64_t first = recs->data_off[0];
-    const uint8_t *data = recs->data + first;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
     LfqBamEncIn in;
     memset(&in, 0, sizeof(in));
-    in.data = data;
-    in.data_bytes = recs->data_off[n] - first;
-    in.first_shift = (int)((uintptr_t)data & 15);       /* the records keep the alignment they have in the caller's memory */
+    in.recs = bam_records_in(recs);
     in.n = n;
     in.what = what;
     in.uniform = rs->idq_mode == LFQ_IDQ_UNIFORM;
-    LFQ_TRY_HIP(hipSetDevice(c->device));
-    in.data_pinned = lfq_is_pinned(data);
+    const int64_t first = recs->data_off[0];
     LfqPin<LfqBamRead> reads(c, (size_t)n);
     LFQ_PIN_OK(reads);
     std::vector<int64_t> src_v((size_t)n);
@@ -3304,8 +3314,8 @@ int lfq_readset_encode_bam(lfq_ctx *c, lfq_readset *rs, const lfq_bam_records *r
         for (int64_t j = j0; j < j1; j++) {
             const int64_t s = src ? src[j] : j;
             LfqBamRead &R = rd[j];
-            R.rec = in.first_shift + recs->data_off[s] - first;
-            R.end = in.first_shift + recs->data_off[s + 1] - first;
+            R.rec = in.recs.first_shift + recs->data_off[s] - first;
+            R.end = in.recs.first_shift + recs->data_off[s + 1] - first;
             R.l_qseq = recs->l_qseq[s];
             R.n_cigar = recs->n_cigar[s];
             R.l_qname = recs->l_qname[s];

@@ -46,6 +46,7 @@ extern "C" {
 /* (10 still: lfq_readset_plp_summary, lfq_format_plp_summary, lfq_last_summary_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_plp_quals_from_tracks, lfq_format_plp_quals, lfq_format_plp_indel_quals, lfq_set_indel_arrays_all_columns, lfq_last_plp_quals_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_readset_create_from_bam, lfq_readset_fetch_bases, lfq_last_bam_decode_times are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_readset_create_from_bam_tags, lfq_readset_fetch_stored_tags, lfq_readset_baq_fill, lfq_last_baq_fill_stats likewise.) */
 /* (10 still: lfq_readset_encode_bam, lfq_last_bam_encode_times are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
@@ -570,7 +571,7 @@ int lfq_readset_viterbi(lfq_ctx *ctx, lfq_readset *rs, int def_qual, lfq_readset
  *   qualities   copied as they are, 0xff included;
  *   BI / BD     from the FIRST aux field with that tag, and only if its type is Z, its string has at least l_qseq bytes before the
  *               NUL and the NUL lies inside the record; otherwise the read has no such tag (tag_flags bit 0 / 1 clear, bytes '!').
- *               The read set has a BI (BD) array exactly when at least one read has the tag.  lb / ai / ad / sq tags are not read;
+ *               The read set has a BI (BD) array exactly when at least one read has the tag.  lb / ai / ad / sq tags are not read (lb / ai / ad: lfq_readset_create_from_bam_tags below);
  *   reverse     flag >> 4 & 1; mapq as given.
  * Ownership: *out owns host copies of everything its host-side steps read (positions, offsets, CIGARs, mapq, strand, flags, and the
  * per-base arrays, which come back from the device into pinned memory); after the call it depends neither on recs->data nor on the
@@ -612,6 +613,58 @@ typedef struct lfq_bam_decode_times {
     int n_launches;
 } lfq_bam_decode_times;
 int lfq_last_bam_decode_times(lfq_ctx *ctx, lfq_bam_decode_times *t);
+
+/* The decode above that also KEEPS the alignment qualities a record already carries, for lfq_readset_baq_fill below: what
+ * `lofreq call` does with a BAM that went through `lofreq alnqual` (bam_prob_realn_core_ext under baq_flag = 1, plp.c:667-683).
+ *   read_tags   LFQ_BAM_READ_LB: the first lb field of every record; LFQ_BAM_READ_IDAQ: the first ai and the first ad field.
+ *               0: lfq_readset_create_from_bam in every observable way.  An unknown bit: LFQ_ERR_INVALID before a device is touched.
+ * For a selected tag the FIRST aux field with that tag decides (bam_aux_get, as for BI / BD): no such field -- the read has no
+ * stored tag; a field of type Z with at least l_qseq bytes before its NUL -- its first l_qseq bytes are the read's stored tag (the
+ * pileup indexes the string with qpos).  A first field of another type or with a shorter string: LFQ_ERR_INVALID from the decode,
+ * *out = NULL, the context stays usable -- the reference counts such a field as present and reads past it (plp.c:865-897), so
+ * there is no defined result to reproduce.  A malformed aux block is refused as by the plain decode, and no device read leaves a
+ * record by more than that decode allows.
+ * The stored strings wait on the device, in side arrays of the read set; until lfq_readset_baq_fill nothing sees them but
+ * lfq_readset_fetch_stored_tags: lfq_readset_fetch_tags, the pileups and lfq_readset_baq (which recomputes every read, as always)
+ * behave as on any fresh read set.  lfq_readset_viterbi on a read set of which a read has a stored tag is LFQ_ERR_INVALID: the
+ * tags depend on the alignment, as its other refusals do. */
+#define LFQ_BAM_READ_LB   1   /* keep the first lb field of every record */
+#define LFQ_BAM_READ_IDAQ 2   /* keep the first ai and the first ad field */
+int lfq_readset_create_from_bam_tags(lfq_ctx *ctx, const lfq_bam_records *recs, unsigned read_tags, lfq_readset **out);
+/* the stored tags, from the device: per-base arrays in the seq_off layout ('!' throughout for a read without the tag), and one
+ * byte per read: bit 0 / 1 / 2 = lb / ai / ad stored.  NULL = not wanted.  Any read set (one without stored tags: '!' and 0). */
+int lfq_readset_fetch_stored_tags(lfq_ctx *ctx, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out,
+                                  uint8_t *stored_flags_out);
+/* lfq_readset_baq that runs the HMM only where a tag is missing: bam_prob_realn_core_ext under baq_flag = 1 (redo_baq: 2, `lofreq
+ * call -D`) and idaq_flag = want_idaq.  For read r let S_lb, S_ai, S_ad be its stored bits -- S_lb counts as 0 under redo_baq, S_ai
+ * and S_ad as 0 without want_idaq or on a read set decoded without LFQ_BAM_READ_IDAQ -- and has_ins / has_del whether its CIGAR has
+ * an I / D operation:
+ *   need_r = !S_lb || (want_idaq && ((has_del && !S_ad) || (has_ins && !S_ai)))          (bam_md_ext.c:352-366)
+ * (without want_idaq the reference may still run the HMM for a read with S_lb; nothing of that run is used).  The HMM runs for
+ * the reads with need_r only; it is lfq_readset_baq's: same kernels, same routes, same bytes.  The resident result:
+ *   lb        the stored bytes if S_lb, else the computed ones (:409, :472: an existing tag is never replaced);
+ *   ai (ad)   with want_idaq: the stored bytes if S_ai (S_ad); otherwise the computed ones if need_r and the kernel wrote the tag
+ *             for the read, else absent ('~' bytes, flag clear).  The reference appends a computed duplicate behind a stored ai /
+ *             ad (:241-246); the pileup reads the first field, so the stored one wins here too.
+ * tag_flags bits 2 / 3 of a read mean "stored or computed".  Afterwards the read set cannot be told, by the pileups,
+ * lfq_readset_fetch_tags, source quality or the calls, from one that was given these arrays.  (redo_baq with TWO lb fields in a
+ * record: the reference deletes the first and then reads the second; here the read counts as having none.  Records that
+ * `lofreq alnqual` wrote have one.)
+ * No read needs the HMM: no HMM kernel is launched and lfq_last_baq_times is left as it was.  A read set without stored tags: the
+ * call is lfq_readset_baq.  Returns when its work is queued, like lfq_readset_baq.
+ * LFQ_ERR_INVALID: a second fill or BAQ pass that newly wants ai / ad (as lfq_readset_baq).  After a fill that merged stored tags,
+ * lfq_readset_encode_bam with LFQ_BAM_PUT_LB / LFQ_BAM_PUT_IDAQ is LFQ_ERR_INVALID: `lofreq alnqual` appends COMPUTED duplicates
+ * there, which a filled read set no longer holds -- alnqual on the device stays the full recompute (lfq_readset_baq). */
+int lfq_readset_baq_fill(lfq_ctx *ctx, lfq_readset *rs, int baq_extended, int want_idaq, int redo_baq);
+/* the context's last lfq_readset_baq_fill (waits for its kernels): n_stored_* count the reads whose stored tag was taken (after
+ * redo_baq / want_idaq); n_hmm_launches and ms_hmm are lfq_last_baq_times' figures of the call, 0 when no read needed the HMM;
+ * ms_merge: the merge pass */
+typedef struct lfq_baq_fill_stats {
+    int64_t n_reads, n_need_hmm, n_stored_lb, n_stored_ai, n_stored_ad;
+    int32_t n_hmm_launches, pad;
+    float ms_hmm, ms_merge;
+} lfq_baq_fill_stats;
+int lfq_last_baq_fill_stats(lfq_ctx *ctx, lfq_baq_fill_stats *s);
 
 /* The way back: the results of a read set's steps WRITTEN INTO THE BYTES OF BAM RECORDS on the device -- what `lofreq viterbi`,
  * `lofreq alnqual` and `lofreq indelqual` do to a record with bam_aux_get / bam_aux_del / bam_aux_append and replace_cigar -- so

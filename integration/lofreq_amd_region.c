@@ -77,6 +77,7 @@ struct lfq_region {
     int max_depth_set;              /* lfq_region_set_max_depth was called: close takes the cap off the context again */
     lfq_indelqual_conf idq;         /* lfq_region_set_indelqual; mode 0 = off (the default) */
     int vit_on, vit_def_qual;       /* lfq_region_set_viterbi; off by default */
+    int reuse_tags;                 /* lfq_region_set_reuse_tags; 0 by default */
     lfq_region_emit_fn emit_summary; /* lfq_region_set_summary; NULL = off (the default) */
     void *summary_user;
     /* outputs, grown on demand */
@@ -190,11 +191,20 @@ int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_nu
 
 int lfq_region_set_viterbi(lfq_region *r, int on, int def_qual)
 {
-    if (!r || r->open || r->buf[0].started || r->buf[1].started || (on && def_qual > 93)) {
+    if (!r || r->open || r->buf[0].started || r->buf[1].started || (on && def_qual > 93) || (on && r->reuse_tags)) {
         return LFQ_ERR_INVALID;
     }
     r->vit_on = on != 0;
     r->vit_def_qual = def_qual;
+    return LFQ_OK;
+}
+
+int lfq_region_set_reuse_tags(lfq_region *r, int mode)
+{
+    if (!r || r->open || r->buf[0].started || r->buf[1].started || mode < 0 || mode > 2 || (mode && r->vit_on)) {
+        return LFQ_ERR_INVALID;
+    }
+    r->reuse_tags = mode;
     return LFQ_OK;
 }
 
@@ -252,7 +262,8 @@ int lfq_region_add_read(lfq_region *r, int32_t pos, int flag, int mapq, int n_ci
     static const uint8_t nt16_int[16] = {5, 0, 1, 6, 2, 7, 8, 9, 3, 10, 11, 12, 13, 14, 15, 4};
     reg_buf *b;
     int i;
-    if (!r || !r->open || n_cigar < 0 || l_qseq < 0 || (n_cigar > 0 && !cigar) || (l_qseq > 0 && (!seq4 || !qual))) {
+    if (!r || !r->open || n_cigar < 0 || l_qseq < 0 || (n_cigar > 0 && !cigar) || (l_qseq > 0 && (!seq4 || !qual))
+        || r->reuse_tags) {                     /* (lfq_region_set_reuse_tags: the tags come with records only) */
         return LFQ_ERR_INVALID;
     }
     /* plp.c:706-720 */
@@ -377,7 +388,11 @@ static int region_readset_from_records(lfq_region *r, reg_buf *b)
     rc_.l_qseq = (const int32_t *)b->rec_lqseq.p;
     rc_.ref = b->ref;
     rc_.ref_len = b->ref_len;
-    rc = lfq_readset_create_from_bam(r->ctx, &rc_, &b->rs);
+    if (r->reuse_tags) {
+        rc = lfq_readset_create_from_bam_tags(r->ctx, &rc_, LFQ_BAM_READ_LB | (r->o.use_idaq ? LFQ_BAM_READ_IDAQ : 0), &b->rs);
+    } else {
+        rc = lfq_readset_create_from_bam(r->ctx, &rc_, &b->rs);
+    }
     if (rc == LFQ_OK) {
         rc = lfq_readset_fetch_bases(r->ctx, b->rs, NULL, NULL, NULL, NULL, (uint8_t *)b->flags.p);
         if (rc != LFQ_OK) {
@@ -437,7 +452,11 @@ static int region_start(lfq_region *r, reg_buf *b)
         }
     }
     if (r->o.use_baq || r->o.use_idaq) {                                /* plp.c:667-683 */
-        rc = lfq_readset_baq(r->ctx, b->rs, r->o.baq_extended, r->o.use_idaq ? 1 : 0);
+        if (r->reuse_tags && b->fed_by == 2) {                          /* baq_flag 1, or 2 under -D (plp.c:676-678) */
+            rc = lfq_readset_baq_fill(r->ctx, b->rs, r->o.baq_extended, r->o.use_idaq ? 1 : 0, r->reuse_tags == 2);
+        } else {
+            rc = lfq_readset_baq(r->ctx, b->rs, r->o.baq_extended, r->o.use_idaq ? 1 : 0);
+        }
         if (rc != LFQ_OK) {
             /* the read set waits for its queued copies before it goes: the caller may refill this buffer's arrays */
             lfq_readset_destroy(b->rs);

@@ -78,6 +78,17 @@ int lfq_region_set_indelqual(lfq_region *r, const lfq_indelqual_conf *conf_or_nu
  * LFQ_ERR_INVALID, as is a read with a quality above 93 that would be realigned (from lfq_region_end).  Same calling rule as
  * lfq_region_set_indelqual: after lfq_region_open, before the first lfq_region_begin.  Not a field of lfq_region_opts. */
 int lfq_region_set_viterbi(lfq_region *r, int on, int def_qual);
+/* The lb / ai / ad tags the records already carry (opt-in; default mode 0), for regions fed by lfq_region_add_record:
+ *   0   every read's alignment qualities are recomputed, whatever tags its record has (the behaviour without this call);
+ *   1   `lofreq call`'s default: the first lb field of a record -- and, with use_idaq, its first ai and ad field -- is kept, and the
+ *       HMM runs only for the reads that lack one (lfq_readset_create_from_bam_tags + lfq_readset_baq_fill);
+ *   2   `lofreq call -D`: as 1, but a stored lb is recomputed; stored ai / ad still win.
+ * A BAM that went through `lofreq alnqual` gives the reference's VCF under mode 1 and launches no HMM kernel at all.  A record
+ * whose first lb / ai / ad field is no Z string of at least l_qseq bytes fails its region (LFQ_ERR_INVALID from lfq_region_end).
+ * Under a non-zero mode lfq_region_add_read is LFQ_ERR_INVALID (it has no tags to hand over), and so is the mode together with
+ * lfq_region_set_viterbi (the tags belong to the alignment the records came with), from whichever call comes second.  Same calling
+ * rule as lfq_region_set_indelqual.  Not a field of lfq_region_opts. */
+int lfq_region_set_reuse_tags(lfq_region *r, int mode);
 /* `lofreq call --plp-summary-only` / `lofreq plpsummary` beside the calls (opt-in; default off): with a callback, every region
  * also emits the header line of plp_summary (lofreq_call.c:445-459) of each of its columns, in column order, BEFORE the region's
  * VCF lines -- one lfq_readset_plp_summary call per region, which runs the indel pileup of the region whether or not indels are

@@ -147,6 +147,13 @@ class BamDecodeTimes(C.Structure):
 
 LFQ_BAM_PUT_ALIGNMENT, LFQ_BAM_DROP_ALN_TAGS, LFQ_BAM_PUT_LB, LFQ_BAM_PUT_IDAQ = 1, 2, 4, 8
 LFQ_BAM_KEEP_EXISTING, LFQ_BAM_PUT_INDELQUAL = 16, 32
+LFQ_BAM_READ_LB, LFQ_BAM_READ_IDAQ = 1, 2
+
+
+class BaqFillStats(C.Structure):
+    """lfq_baq_fill_stats"""
+    _fields_ = [(n, C.c_int64) for n in ("n_reads", "n_need_hmm", "n_stored_lb", "n_stored_ai", "n_stored_ad")] + [
+        ("n_hmm_launches", C.c_int32), ("pad", C.c_int32), ("ms_hmm", C.c_float), ("ms_merge", C.c_float)]
 
 
 class BamEncoded(C.Structure):
@@ -220,6 +227,7 @@ EXPORTS = [
     "lfq_set_max_depth", "lfq_readset_kept_reads", "lfq_viterbi_batch", "lfq_last_viterbi_times",
     "lfq_readset_viterbi",
     "lfq_readset_create_from_bam", "lfq_readset_fetch_bases", "lfq_last_bam_decode_times",
+    "lfq_readset_create_from_bam_tags", "lfq_readset_fetch_stored_tags", "lfq_readset_baq_fill", "lfq_last_baq_fill_stats",
     "lfq_readset_encode_bam", "lfq_last_bam_encode_times",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
@@ -353,6 +361,10 @@ def load():
     L.lfq_readset_create.argtypes = [vp, C.POINTER(PileupReads), C.POINTER(PileupIndelTags), C.POINTER(vp)]
     L.lfq_readset_create_from_bam.argtypes = [vp, C.POINTER(BamRecords), C.POINTER(vp)]
     L.lfq_readset_fetch_bases.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lfq_readset_create_from_bam_tags.argtypes = [vp, C.POINTER(BamRecords), C.c_uint, C.POINTER(vp)]
+    L.lfq_readset_fetch_stored_tags.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lfq_readset_baq_fill.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+    L.lfq_last_baq_fill_stats.argtypes = [vp, C.POINTER(BaqFillStats)]
     L.lfq_last_bam_decode_times.argtypes = [vp, C.POINTER(BamDecodeTimes)]
     L.lfq_readset_encode_bam.argtypes = [vp, vp, C.POINTER(BamRecords), vp, C.c_uint, C.POINTER(C.POINTER(BamEncoded))]
     L.lfq_last_bam_encode_times.argtypes = [vp, C.POINTER(BamEncodeTimes)]

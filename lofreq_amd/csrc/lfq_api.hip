@@ -470,7 +470,7 @@ void lfq_destroy(lfq_ctx *c)
         for (int i = 0; i < 5; i++) {
             if (c->d_tmp[i]) (void)hipFree(c->d_tmp[i]);
         }
-        for (int k = 0; k < 8; k++) {                   /* 4 = LFQ_RSC_PINFL, 7 = LFQ_RSC_PINBASES: pinned host memory */
+        for (int k = 0; k < 9; k++) {                   /* 4 = LFQ_RSC_PINFL, 7 = LFQ_RSC_PINBASES: pinned host memory */
             if (c->rs_cache[k].p) (void)(k == 4 || k == 7 ? hipHostFree(c->rs_cache[k].p) : hipFree(c->rs_cache[k].p));
         }
         if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
@@ -484,7 +484,7 @@ void lfq_destroy(lfq_ctx *c)
         for (int i = 0; i < LFQ_PIN_SLOTS; i++) {
             if (c->pin_pool[i].p) (void)hipHostFree(c->pin_pool[i].p);
         }
-        for (LfqEvPair *t : {&c->baq_t, &c->idq_t, &c->sites_t[0], &c->sites_t[1], &c->sum_t, &c->pq_t}) {
+        for (LfqEvPair *t : {&c->baq_t, &c->fill_t, &c->idq_t, &c->sites_t[0], &c->sites_t[1], &c->sum_t, &c->pq_t}) {
             t->destroy();
         }
         if (c->d_detlim) (void)hipFree(c->d_detlim);

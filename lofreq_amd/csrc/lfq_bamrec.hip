@@ -1,7 +1,9 @@
 /*
  * lfq_bamrec.hip -- BAM records decoded on the device (lfq_readset_create_from_bam): the bytes of the records go
  * down as they lie in bam1_t.data, an aux pass finds BI / BD per read, a base pass writes the per-base arrays of the read set.
- * The host side that builds the read set around these two launches is in lfq_readset.hip.  Further down, the way back
+ * The host side that builds the read set around these two launches is in lfq_readset.hip.  For lfq_readset_create_from_bam_tags the
+ * aux pass also notes the first lb / ai / ad field, a stored-tag pass lays those strings out per base, and lfq_readset_baq_fill's merge
+ * pass puts them over what the HMM kernels computed.  Further down, the way back
  * (lfq_readset_encode_bam): the records rewritten with a read set's results, a plan pass per read and a copy pass per 16 output bytes.
  */
 #include "lfq_ctx.h"
@@ -16,11 +18,16 @@ struct LfqBamArgs {
     const int64_t *rec_end;             /* [n] offset in `data` one past the read's record */
     int64_t *bi_src, *bd_src;           /* [n] offset of the BI / BD string the read counts as having, or -1 (written by the aux pass) */
     uint8_t *flags;                     /* [n] bit 0: BI, bit 1: BD */
-    int32_t *err;                       /* [0]: a read has BI, [1]: a read has BD, [2]: a malformed aux field */
+    int32_t *err;                       /* [0]: a read has BI, [1]: a read has BD, [2]: a malformed aux field, [3]: see `stored` */
     int64_t *tile_read;                 /* [workgroups of the base pass] the read that holds the first base of the workgroup's tile
                                            (written by the aux pass) */
     int64_t n_reads, n_bases;
     uint8_t *seq, *qual, *bi, *bd;      /* the read set's per-base arrays (16-byte aligned, 16 bytes of slack); bi / bd may be null */
+    /* lfq_readset_create_from_bam_tags: the first lb / ai / ad field of a read, in that order */
+    uint32_t read_tags;                 /* LFQ_BAM_READ_*: the tags the aux pass looks for (0: none, and nothing below is touched) */
+    int64_t *st_src[3];                 /* [n] offset of the string the read has stored, or -1 (written by the aux pass) */
+    uint8_t *stored;                    /* [n] bit 0 / 1 / 2: lb / ai / ad stored; err[3]: a first field that cannot be used */
+    uint8_t *st_dst[3];                 /* stored-tag pass: the per-base side arrays, laid out as bi / bd; null = no read has the tag */
 };
 
 /* the first NUL of [p, end), or a value >= end: four bytes a load, as the aligned dwords that hold them (BI / BD strings are most
@@ -115,7 +122,7 @@ __device__ __forceinline__ bool bam_aux_next(const uint8_t *d, int64_t *p_io, in
 __global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamArgs A)
 {
     const int64_t r = (int64_t)blockIdx.x * LFQ_BAM_AUX_READS + threadIdx.x;
-    bool bad = false, has_bi = false, has_bd = false;
+    bool bad = false, has_bi = false, has_bd = false, unusable = false;
     if (r < A.n_reads) {
         const uint8_t *d = A.data;
         const int64_t l = A.seq_off[r + 1] - A.seq_off[r];
@@ -123,6 +130,8 @@ __global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamAr
         int64_t p = A.seq_src[r] + (l + 1) / 2 + l;
         int64_t bi = -1, bd = -1;
         bool seen_bi = false, seen_bd = false;
+        int64_t st[3] = {-1, -1, -1};
+        uint32_t seen_st = 0;
         while (p < end) {
             LfqBamAuxField F;
             if (!bam_aux_next(d, &p, end, &F)) {
@@ -139,10 +148,28 @@ __global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamAr
                 if (F.ty == 'Z' && F.zlen >= l) {
                     bd = F.at;
                 }
+            } else if (A.read_tags) {                       /* lb / ai / ad: the first field again, but one that must be usable */
+                const int t = (F.t0 == 'l' && F.t1 == 'b') ? 0 : (F.t0 == 'a' && F.t1 == 'i') ? 1 : (F.t0 == 'a' && F.t1 == 'd') ? 2 : -1;
+                const uint32_t wanted = (A.read_tags & LFQ_BAM_READ_LB ? 1u : 0u) | (A.read_tags & LFQ_BAM_READ_IDAQ ? 6u : 0u);
+                if (t >= 0 && ((wanted >> t) & 1u) && !((seen_st >> t) & 1u)) {
+                    seen_st |= 1u << t;
+                    if (F.ty == 'Z' && F.zlen >= l) {
+                        st[t] = F.at;
+                    } else {
+                        unusable = true;
+                    }
+                }
             }
         }
         if (bad) {
             bi = bd = -1;
+            st[0] = st[1] = st[2] = -1;
+        }
+        if (A.read_tags) {
+            A.st_src[0][r] = st[0];
+            A.st_src[1][r] = st[1];
+            A.st_src[2][r] = st[2];
+            A.stored[r] = (uint8_t)((st[0] >= 0 ? 1 : 0) | (st[1] >= 0 ? 2 : 0) | (st[2] >= 0 ? 4 : 0));
         }
         has_bi = bi >= 0;
         has_bd = bd >= 0;
@@ -155,11 +182,12 @@ __global__ __launch_bounds__(LFQ_BAM_AUX_READS) void lfq_bam_aux_kernel(LfqBamAr
         A.bd_src[r] = bd;
         A.flags[r] = (uint8_t)((has_bi ? 1 : 0) | (has_bd ? 2 : 0));
     }
-    const bool any_bi = __any(has_bi), any_bd = __any(has_bd), any_bad = __any(bad);
+    const bool any_bi = __any(has_bi), any_bd = __any(has_bd), any_bad = __any(bad), any_unusable = __any(unusable);
     if ((threadIdx.x & 63) == 0) {
         if (any_bi) atomicOr(&A.err[0], 1);
         if (any_bd) atomicOr(&A.err[1], 1);
         if (any_bad) atomicOr(&A.err[2], 1);
+        if (any_unusable) atomicOr(&A.err[3], 1);
     }
 }
 
@@ -311,6 +339,108 @@ __global__ __launch_bounds__(LFQ_BAM_BASE_CHUNKS) void lfq_bam_bases_kernel(LfqB
     if (A.bd) b16_store(A.bd + b0, vd);
 }
 
+/* ---- stored-tag pass: the base pass's sibling for the first lb / ai / ad strings, same tiles, same chunks; a read without the tag
+ * holds '!' throughout */
+__global__ __launch_bounds__(LFQ_BAM_BASE_CHUNKS) void lfq_bam_stored_kernel(LfqBamArgs A)
+{
+    const int64_t tile0 = (int64_t)blockIdx.x * LFQ_BAM_BASE_CHUNKS * 16;
+    const int64_t b0 = tile0 + (int64_t)threadIdx.x * 16;
+    if (b0 >= A.n_bases) {
+        return;
+    }
+    const int64_t r_lo = A.tile_read[blockIdx.x], r_hi = blockIdx.x + 1 < gridDim.x ? A.tile_read[blockIdx.x + 1] : A.n_reads - 1;
+    const int total = (int)min((int64_t)16, A.n_bases - b0);
+    int64_t r = bam_read_of_base(A.seq_off, r_lo, r_hi, b0);
+    LfqB16 v[3];
+    v[0].lo = v[0].hi = v[1].lo = v[1].hi = v[2].lo = v[2].hi = 0;
+    int j = 0;
+    while (j < total) {
+        const int64_t b = b0 + j;
+        while (A.seq_off[r + 1] <= b) {
+            r++;
+        }
+        const int64_t so = A.seq_off[r], e = A.seq_off[r + 1], i0 = b - so;
+        const int cnt = (int)min(e - b, (int64_t)(total - j));
+        LfqB16 none = b16_mask(cnt);
+        none.lo &= 0x2121212121212121ull;
+        none.hi &= 0x2121212121212121ull;
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            if (A.st_dst[t]) {
+                const int64_t s = A.st_src[t][r];
+                const LfqB16 pt = b16_shl_bytes(s >= 0 ? b16_fetch(A.data, s + i0, cnt) : none, j);
+                v[t].lo |= pt.lo; v[t].hi |= pt.hi;
+            }
+        }
+        j += cnt;
+    }
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        if (A.st_dst[t]) b16_store(A.st_dst[t] + b0, v[t]);
+    }
+}
+
+/* ---- merge pass (lfq_readset_baq_fill): per read and tag the stored bytes replace the computed ones.  One lane owns one 16-byte
+ * chunk of the destination arrays and rewrites it under a byte mask built from the reads it spans -- neighbouring reads of a chunk
+ * differ in what they have stored -- so there are no byte stores and no two lanes write one chunk.  take[r] bit t: read r takes
+ * its stored tag t (lb, ai, ad). */
+struct LfqBamMergeArgs {
+    const int64_t *seq_off;             /* [n + 1] the read set's */
+    const uint8_t *take;                /* [n] */
+    const uint8_t *src[3];              /* the stored side arrays; null = the tag is not merged */
+    uint8_t *dst[3];                    /* the read set's lb, ai, ad (16-byte aligned, 16 bytes of slack) */
+    uint8_t *tagfl;                     /* [n] bit 0 / 1: the read has ai / ad (null: no ai / ad in this fill) */
+    int64_t n_reads, n_bases;
+};
+
+__global__ __launch_bounds__(LFQ_BAM_BASE_CHUNKS) void lfq_bam_merge_kernel(LfqBamMergeArgs A)
+{
+    const int64_t b0 = ((int64_t)blockIdx.x * LFQ_BAM_BASE_CHUNKS + threadIdx.x) * 16;
+    if (b0 >= A.n_bases) {
+        return;
+    }
+    const int total = (int)min((int64_t)16, A.n_bases - b0);
+    int64_t r = bam_read_of_base(A.seq_off, 0, A.n_reads - 1, b0);
+    LfqB16 m[3];
+    m[0].lo = m[0].hi = m[1].lo = m[1].hi = m[2].lo = m[2].hi = 0;
+    int j = 0;
+    while (j < total) {
+        const int64_t b = b0 + j;
+        while (A.seq_off[r + 1] <= b) {
+            r++;
+        }
+        const int cnt = (int)min(A.seq_off[r + 1] - b, (int64_t)(total - j));
+        const uint32_t tk = A.take[r];
+        const LfqB16 mr = b16_shl_bytes(b16_mask(cnt), j);
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            if ((tk >> t) & 1u) {
+                m[t].lo |= mr.lo; m[t].hi |= mr.hi;
+            }
+        }
+        j += cnt;
+    }
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        if (A.src[t] && (m[t].lo | m[t].hi)) {
+            const uint4 s = *(const uint4 *)(A.src[t] + b0), d = *(const uint4 *)(A.dst[t] + b0);
+            LfqB16 o;
+            o.lo = ((((uint64_t)d.y << 32) | d.x) & ~m[t].lo) | ((((uint64_t)s.y << 32) | s.x) & m[t].lo);
+            o.hi = ((((uint64_t)d.w << 32) | d.z) & ~m[t].hi) | ((((uint64_t)s.w << 32) | s.z) & m[t].hi);
+            b16_store(A.dst[t] + b0, o);
+        }
+    }
+}
+
+/* the stored ai / ad bits join what the BAQ kernels wrote, in front of lfq_launch_flag_merge */
+__global__ __launch_bounds__(256) void lfq_bam_merge_flags_kernel(uint8_t *tagfl, const uint8_t *take, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        tagfl[i] = (uint8_t)(tagfl[i] | ((take[i] >> 1) & 3u));
+    }
+}
+
 /* ---- host side: what the decode and the encode keep on a context, and the upload both begin with --------------------------- */
 struct LfqBamState {
     uint8_t *d_buf = nullptr;           /* records | descriptors | what the aux or the plan pass writes (grow-only) */
@@ -426,17 +556,21 @@ static int bam_upload(lfq_ctx *c, LfqBamState *S, const LfqBamIn &in, int64_t to
 /* records down, aux pass, its verdict back: flags_out[n], *any_bi / *any_bd; LFQ_ERR_INVALID for a malformed aux field.
  * desc = seq_off[n + 1] | seq_src[n] | rec_end[n], the last two as offsets from in.data - in.first_shift.  Blocks. */
 int lfq_bam_aux(lfq_ctx *c, const LfqBamIn &in, const int64_t *desc, int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi,
-                int *any_bd)
+                int *any_bd, unsigned read_tags, uint8_t *stored_out)
 {
     LfqBamState *S = bam_state(c);
     LFQ_TRY_HIP(hipSetDevice(c->device));
+    /* (read_tags: three more offset arrays and the stored bits behind the tile table) */
     const int64_t o_desc = lfq_al(in.first_shift + in.data_bytes + 16), o_bi = o_desc + lfq_al((3 * n + 1) * 8),
                   o_bd = o_bi + lfq_al(n * 8), o_err = o_bd + lfq_al(n * 8), o_fl = o_err + 256, o_tile = o_fl + lfq_al(n),
-                  n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), total = o_tile + lfq_al(n_tiles * 8);
+                  n_tiles = (nb + LFQ_BAM_BASE_CHUNKS * 16 - 1) / (LFQ_BAM_BASE_CHUNKS * 16), o_st = o_tile + lfq_al(n_tiles * 8),
+                  o_sfl = o_st + (read_tags ? 3 * lfq_al(n * 8) : 0), total = o_sfl + (read_tags ? lfq_al(n) : 0);
     LfqPin<int32_t> verdict(c, 4);
     LFQ_PIN_OK(verdict);
     LfqPin<uint8_t> fl(c, (size_t)n);
     LFQ_PIN_OK(fl);
+    LfqPin<uint8_t> sfl(c, (size_t)n);
+    LFQ_PIN_OK(sfl);
     LFQ_TRY(bam_upload(c, S, in, total, o_desc, desc, (size_t)(3 * n + 1) * 8, o_err));
     hipStream_t st = c->stream;
     LfqBamArgs &A = S->args;
@@ -452,6 +586,13 @@ int lfq_bam_aux(lfq_ctx *c, const LfqBamIn &in, const int64_t *desc, int64_t n, 
     A.tile_read = (int64_t *)(S->d_buf + o_tile);
     A.n_reads = n;
     A.n_bases = nb;
+    A.read_tags = read_tags;
+    if (read_tags) {
+        for (int t = 0; t < 3; t++) {
+            A.st_src[t] = (int64_t *)(S->d_buf + o_st + t * lfq_al(n * 8));
+        }
+        A.stored = S->d_buf + o_sfl;
+    }
     LFQ_TRY(S->kern_t.begin(st));
     hipLaunchKernelGGL(lfq_bam_aux_kernel, dim3((unsigned)((n + LFQ_BAM_AUX_READS - 1) / LFQ_BAM_AUX_READS)),
                        dim3(LFQ_BAM_AUX_READS), 0, st, A);
@@ -460,13 +601,19 @@ int lfq_bam_aux(lfq_ctx *c, const LfqBamIn &in, const int64_t *desc, int64_t n, 
     S->times.n_launches += 1;
     LFQ_TRY_HIP(hipMemcpyAsync(verdict.data(), A.err, 16, hipMemcpyDeviceToHost, st));
     LFQ_TRY_HIP(hipMemcpyAsync(fl.data(), A.flags, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (read_tags) {
+        LFQ_TRY_HIP(hipMemcpyAsync(sfl.data(), A.stored, (size_t)n, hipMemcpyDeviceToHost, st));
+    }
     LFQ_TRY_HIP(hipStreamSynchronize(st));
     LFQ_TRY(bam_add_ms(S->up_t, &S->times.upload_ms));
     LFQ_TRY(bam_add_ms(S->kern_t, &S->times.kernels_ms));
-    if (verdict[2]) {
+    if (verdict[2] || verdict[3]) {     /* malformed, or a first lb / ai / ad field that is no string of l_qseq bytes */
         return LFQ_ERR_INVALID;
     }
     memcpy(flags_out, fl.data(), (size_t)n);
+    if (read_tags) {
+        memcpy(stored_out, sfl.data(), (size_t)n);
+    }
     *any_bi = verdict[0] != 0;
     *any_bd = verdict[1] != 0;
     return LFQ_OK;
@@ -505,6 +652,62 @@ int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, ui
     LFQ_TRY_HIP(hipStreamSynchronize(st));
     LFQ_TRY(bam_add_ms(S->kern_t, &S->times.kernels_ms));
     return bam_add_ms(S->down_t, &S->times.download_ms);
+}
+
+/* stored-tag pass of the decode lfq_bam_aux began.  Blocks (the records below it are the context's until the next decode). */
+int lfq_bam_stored(lfq_ctx *c, uint8_t *const d_dst[3])
+{
+    LfqBamState *S = bam_state(c);
+    LfqBamArgs A = S->args;
+    const int64_t nb = A.n_bases;
+    if (nb <= 0 || !A.read_tags || (!d_dst[0] && !d_dst[1] && !d_dst[2])) {
+        return LFQ_OK;
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    for (int t = 0; t < 3; t++) {
+        A.st_dst[t] = d_dst[t];
+    }
+    const int64_t per_wg = (int64_t)LFQ_BAM_BASE_CHUNKS * 16;
+    LFQ_TRY(S->kern_t.begin(st));
+    hipLaunchKernelGGL(lfq_bam_stored_kernel, dim3((unsigned)((nb + per_wg - 1) / per_wg)), dim3(LFQ_BAM_BASE_CHUNKS), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY(S->kern_t.end(st));
+    S->times.n_launches += 1;
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    return bam_add_ms(S->kern_t, &S->times.kernels_ms);
+}
+
+/* merge pass of lfq_readset_baq_fill, queued on `st` */
+int lfq_bam_merge(const int64_t *d_seq_off, const uint8_t *d_take, const uint8_t *const d_src[3], uint8_t *const d_dst[3],
+                  uint8_t *d_tagfl, int64_t n, int64_t nb, hipStream_t st)
+{
+    if (n <= 0) {
+        return LFQ_OK;
+    }
+    LfqBamMergeArgs M;
+    memset(&M, 0, sizeof(M));
+    M.seq_off = d_seq_off;
+    M.take = d_take;
+    bool any = false;
+    for (int t = 0; t < 3; t++) {
+        M.src[t] = d_dst[t] ? d_src[t] : nullptr;
+        M.dst[t] = d_dst[t];
+        any = any || M.src[t];
+    }
+    M.tagfl = d_tagfl;
+    M.n_reads = n;
+    M.n_bases = nb;
+    const int64_t per_wg = (int64_t)LFQ_BAM_BASE_CHUNKS * 16;
+    if (any && nb > 0) {
+        hipLaunchKernelGGL(lfq_bam_merge_kernel, dim3((unsigned)((nb + per_wg - 1) / per_wg)), dim3(LFQ_BAM_BASE_CHUNKS), 0, st, M);
+        LFQ_TRY_HIP(hipGetLastError());
+    }
+    if (d_tagfl) {
+        hipLaunchKernelGGL(lfq_bam_merge_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_tagfl, d_take, n);
+        LFQ_TRY_HIP(hipGetLastError());
+    }
+    return LFQ_OK;
 }
 
 extern "C" int lfq_last_bam_decode_times(lfq_ctx *c, lfq_bam_decode_times *t)

@@ -365,7 +365,7 @@ struct lfq_ctx {
     /* the allocations of the read set destroyed last (reads, tags, read ends, tag flags, pinned flags): the next
      * lfq_readset_create / _baq takes them over when they are large enough -- a worker goes from region to region, and
      * hipMalloc + hipFree of 2 GB per region are milliseconds and a device synchronisation each */
-    struct { void *p; size_t cap; } rs_cache[8];
+    struct { void *p; size_t cap; } rs_cache[9];
     int priv_stream_on;
     hipStream_t priv_stream;         /* lfq_set_private_stream: this context's own launch stream (null = the device's shared one) */
     hipStream_t up_stream;           /* lfq_readset_create's uploads and the staging copies of host tracks (created on first use) */
@@ -387,6 +387,9 @@ struct lfq_ctx {
     LfqEvPair baq_t;                 /* around the BAQ kernels of the last lfq_readset_baq / lfq_baq_batch call */
     int32_t baq_launches;            /* kernel launches between them on the context's stream */
     int64_t baq_reads, baq_bases;    /* reads / bases of that call */
+    LfqEvPair fill_t;                /* around the merge pass of the last lfq_readset_baq_fill call */
+    lfq_baq_fill_stats fill_stats;   /* counts and launches of that call (the ms: from the events, when asked for) */
+    int fill_hmm, fill_merge;        /* that call ran the HMM (ms_hmm comes from baq_t) / the merge pass */
     LfqEvPair idq_t;                 /* around the kernels of the last lfq_readset_indelqual / lfq_indelqual_batch call */
     lfq_indelqual_times idq_times;   /* launches, reads and bases of that call (ms_kernels: from the events, when asked for) */
     int batch_gate;                  /* lfq_set_batch_gate: what this context's next count kernel waits for (LFQ_GATE_*) */
@@ -558,9 +561,15 @@ struct LfqBamIn {
 void lfq_bam_release(lfq_ctx *c);
 void lfq_bam_times_reset(lfq_ctx *c, int64_t n_reads, int64_t n_bases, int64_t n_data_bytes);
 int lfq_bam_aux(lfq_ctx *c, const LfqBamIn &in, const int64_t *desc, int64_t n, int64_t nb, uint8_t *flags_out, int *any_bi,
-                int *any_bd);
+                int *any_bd, unsigned read_tags, uint8_t *stored_out);
 int lfq_bam_bases(lfq_ctx *c, uint8_t *d_seq, uint8_t *d_qual, uint8_t *d_bi, uint8_t *d_bd, uint8_t *h_seq, uint8_t *h_qual,
                   uint8_t *h_bi, uint8_t *h_bd);
+/* for lfq_readset_create_from_bam_tags / lfq_readset_baq_fill (lfq_readset.hip): the stored-tag pass of the decode in flight into
+ * the side arrays (null: no read has the tag; blocks), and the merge pass queued on `st`: per read r and tag t (lb, ai, ad) with bit
+ * t of d_take[r], the bytes of src[t] replace those of dst[t]; with d_tagfl the ai / ad bits are ORed into it */
+int lfq_bam_stored(lfq_ctx *c, uint8_t *const d_dst[3]);
+int lfq_bam_merge(const int64_t *d_seq_off, const uint8_t *d_take, const uint8_t *const d_src[3], uint8_t *const d_dst[3],
+                  uint8_t *d_tagfl, int64_t n, int64_t nb, hipStream_t st);
 /* for lfq_readset_encode_bam (lfq_readset.hip): the records rewritten on the device.  One LfqBamRead per read of the read set, in
  * its order; rec / end are offsets from data - first_shift, as for the decode */
 struct LfqBamRead {

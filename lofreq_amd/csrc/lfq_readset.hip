@@ -14,7 +14,7 @@ extern "C" {
  * copy and leave their per-base results (lb, ai, ad, sq) there for the next stage.  The host arrays handed to
  * lfq_readset_create stay the caller's and must outlive the read set: the sparse host-side steps (geometry from the
  * CIGARs, the indel event tables) read them in place. */
-enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5, LFQ_RSC_IDQ = 6, LFQ_RSC_PINBASES = 7 };
+enum { LFQ_RSC_BLOB = 0, LFQ_RSC_TAGS = 1, LFQ_RSC_PMAX = 2, LFQ_RSC_TAGFL = 3, LFQ_RSC_PINFL = 4, LFQ_RSC_KEEP = 5, LFQ_RSC_IDQ = 6, LFQ_RSC_PINBASES = 7, LFQ_RSC_STORED = 8 };
 
 static bool rs_cache_pinned(int kind)
 {
@@ -82,7 +82,8 @@ struct LfqReadsetOwned {
 #define LFQ_UP_CHUNKS 6
 struct lfq_readset {
     lfq_ctx *c;
-    size_t cap[7];                      /* capacities of blob, tag_blob, d_pmax, d_tagfl, h_fl_pin, d_keep, idq_blob (rs_cache_*) */
+    size_t cap[9];                      /* capacities of blob, tag_blob, d_pmax, d_tagfl, h_fl_pin, d_keep, idq_blob, -, stored_blob
+                                           (rs_cache_*; LFQ_RSC_PINBASES: LfqReadsetOwned::pin_cap) */
     int64_t n, n_bases, n_cig, ref_len;
     const int32_t *pos;
     const int64_t *cigar_off, *seq_off;
@@ -139,6 +140,12 @@ struct lfq_readset {
     hipEvent_t ev_chunk[LFQ_UP_CHUNKS]; /* bases + qualities of the reads up to chunk j have landed */
     hipEvent_t ev_stage[2];             /* [0]: everything but BI / BD, [1]: all of it */
     LfqReadsetOwned *own;               /* lfq_readset_viterbi's result: the host views above point into it (else null) */
+    /* lfq_readset_create_from_bam_tags: the first lb / ai / ad strings the records carry, waiting for lfq_readset_baq_fill */
+    std::vector<uint8_t> stored_fl;     /* [n] bit 0 / 1 / 2: lb / ai / ad stored; empty: no read has a stored tag */
+    std::vector<uint8_t> take;          /* [n] the last fill's merge mask, as it went to d_take */
+    uint8_t *stored_blob;               /* take[n] | lb | ai | ad, the arrays of the tags a read has */
+    uint8_t *d_take, *d_st[3];          /* (d_st[t] null: no read has tag t) */
+    bool filled;                        /* the resident lb / ai / ad hold stored bytes: no longer what `alnqual` would append */
 };
 
 /* the reads, qualities, CIGARs and the contig are on the device (BI / BD may still be on their way: the BAQ kernels do
@@ -258,6 +265,7 @@ void lfq_readset_destroy(lfq_readset *rs)
             (void)hipEventDestroy(rs->ev_idq);
         }
         rs_cache_give(rs->c, LFQ_RSC_IDQ, rs->idq_blob, rs->cap[LFQ_RSC_IDQ]);
+        rs_cache_give(rs->c, LFQ_RSC_STORED, rs->stored_blob, rs->cap[LFQ_RSC_STORED]);
         if (rs->ev_keep) (void)hipEventDestroy(rs->ev_keep);
         if (rs->own) {
             rs_cache_give(rs->c, LFQ_RSC_PINBASES, rs->own->pin_bases, rs->own->pin_cap);
@@ -311,6 +319,8 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     rs->up_rc = LFQ_OK;
     rs->up_fl = nullptr;
     rs->own = nullptr;
+    rs->stored_blob = rs->d_take = rs->d_st[0] = rs->d_st[1] = rs->d_st[2] = nullptr;
+    rs->filled = false;
     rs->has_lb = rs->has_idaq = rs->has_sqb = rs->has_bi = rs->has_bd = false;
     const int64_t n = rs->n, nb = rs->n_bases;
     {
@@ -894,13 +904,14 @@ int lfq_baq_idaq_batch(lfq_ctx *c, const lfq_baq_reads *rd, int baq_extended, ui
     return rc;
 }
 
-/* bam_prob_realn_core_ext for every read of the set: lb (and ai / ad) stay on the device */
-int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq_i)
+/* bam_prob_realn_core_ext for every read of the set: lb (and ai / ad) stay on the device.  skip (lfq_readset_baq_fill; null: no
+ * read is left out): skip[r] != 0 leaves read r out of every launch list -- its lb stays 0, its ai / ad '~', its tag flags clear.
+ * merge (lfq_readset_baq_fill again): behind the HMM kernels, on their stream, the merge pass puts the stored bytes of the reads
+ * and tags of rs->take in place of what is there.  No read left in: no HMM launch, and the context's BAQ times stay as they are.
+ * stats: how many reads the launch lists held and how many launches took them. */
+static int readset_baq_run(lfq_ctx *c, lfq_readset *rs, int baq_extended, bool want_idaq, const uint8_t *skip, bool merge,
+                           lfq_baq_fill_stats *stats = nullptr)
 {
-    if (!c || !rs || rs->c != c || (rs->n > 0 && !rs->qual)) {
-        return LFQ_ERR_INVALID;
-    }
-    const bool want_idaq = want_idaq_i != 0;
     const lfq_readset *rd = rs;             /* the host views carry the names the geometry code below uses */
     const int64_t n = rs->n;
     if (n == 0) {
@@ -925,15 +936,23 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     int max_lq = 0, max_w = 0;
     int part_lq[LFQ_HOST_PARTS] = {0}, part_w[LFQ_HOST_PARTS] = {0};
     int64_t part_narrow[LFQ_HOST_PARTS + 1] = {0}, part_band8[LFQ_HOST_PARTS + 1] = {0}, part_plain[LFQ_HOST_PARTS + 1] = {0};
+    int64_t part_sel[LFQ_HOST_PARTS + 1] = {0};                     /* reads that are not skipped */
     LfqPin<uint8_t> has_id(c, (size_t)n);                            /* the read has an I or D operation (what idaq looks at) */
     LFQ_PIN_OK(has_id);
     int part_lrn[LFQ_HOST_PARTS] = {0}, part_lqn[LFQ_HOST_PARTS] = {0};
     int parts = 1;
     lfq_for_reads(n, [&](int64_t r_begin, int64_t r_end, int part) {
     int max_lq = 0, max_w = 0, lrn = 0, lqn = 0;    /* of this part */
-    int64_t n_nar = 0, n_b8 = 0, n_pl = 0;
+    int64_t n_nar = 0, n_b8 = 0, n_pl = 0, n_in = 0;
     for (int64_t r = r_begin; r < r_end; r++) {
         LfqBaqGeom &o = h[(size_t)r];
+        if (skip && skip[r]) {                          /* in no list: no launch reads its geometry */
+            o.xb = o.l_ref = o.bw = 0;
+            has_id[(size_t)r] = 0;
+            width[(size_t)r] = -1;
+            continue;
+        }
+        n_in++;
         const int l_qseq = (int)(rd->seq_off[r + 1] - rd->seq_off[r]);
         const uint32_t *cg = rd->cigar + rd->cigar_off[r];
         const int n_cigar = (int)(rd->cigar_off[r + 1] - rd->cigar_off[r]);
@@ -991,6 +1010,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     part_narrow[part + 1] = n_nar;
     part_plain[part + 1] = n_pl;
     part_band8[part + 1] = n_b8;
+    part_sel[part + 1] = n_in;
     part_lrn[part] = lrn;
     part_lqn[part] = lqn;
     }, &parts);
@@ -1003,7 +1023,9 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
         part_narrow[p + 1] += part_narrow[p];
         part_plain[p + 1] += part_plain[p];
         part_band8[p + 1] += part_band8[p];
+        part_sel[p + 1] += part_sel[p];
     }
+    const int64_t n_run = part_sel[parts];          /* the reads of the launch lists: all of them without `skip` */
     tmb[1] = lfq_now_ms();
     /* launch order: the narrow-band reads first, in input order (neighbouring reads share their reference window in the
      * caches), then the band-8 reads, the others behind them.  Every part of the read range knows where its reads go. */
@@ -1012,8 +1034,11 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     const int64_t n_narrow = part_narrow[parts], n_band8 = part_band8[parts], n_plain = part_plain[parts];
     lfq_for_reads(n, [&](int64_t r_begin, int64_t r_end, int part) {
         int64_t pi = part_plain[part], ni = n_plain + (part_narrow[part] - part_plain[part]), bi = n_narrow + part_band8[part];
-        int64_t wi = n - 1 - (r_begin - part_narrow[part] - part_band8[part]);    /* wide reads before this part */
+        int64_t wi = n_run - 1 - (part_sel[part] - part_narrow[part] - part_band8[part]);    /* wide reads before this part */
         for (int64_t r = r_begin; r < r_end; r++) {
+            if (width[(size_t)r] < 0) {
+                continue;                           /* skipped */
+            }
             const bool short_ref = h[(size_t)r].l_ref <= LFQ_BAQ_LDS_MAX_LREF;
             if (use_lds && width[(size_t)r] <= LFQ_BAQ_LDS_CELLS && short_ref) {
                 if (want_idaq && has_id[(size_t)r]) {
@@ -1105,7 +1130,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             budget_b = (int64_t)lfq_knobs().baq_scratch_mb << 20;
         }
         /* + 3: the four groups of reads (plain narrow, narrow with indels, band 8, wide) round up to whole wavefronts separately */
-        int64_t waves = std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64 + 3, budget_b / per_wave));
+        int64_t waves = std::max<int64_t>(1, std::min<int64_t>((n_run + 63) / 64 + 3, budget_b / per_wave));
         auto keep = [&](auto **slot, int64_t *have, int64_t need) {
             if (need > *have) {
                 if (*slot) (void)hipFree(*slot);
@@ -1159,7 +1184,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
          * beside the narrow-band launches on the side streams, in scratch slots of their own behind the narrow ones'
          * (wavefront w of a launch owns slot w).  The narrow-band kernel runs one wavefront per SIMD, so a launch is cut
          * to a whole number of rounds over the SIMDs: a launch of 7.3 rounds takes as long as one of 8. */
-        const int64_t n_wide = n - n_narrow - n_band8;
+        const int64_t n_wide = n_run - n_narrow - n_band8;
         const int64_t waves_wide = (n_wide + 63) / 64, waves_b8 = (n_band8 + 63) / 64;
         const bool side_ok = n_narrow > 0 && c->side[0] != nullptr && c->side[1] != nullptr && !lfq_knobs().single_stream;
         const bool beside = side_ok && waves_wide + waves_b8 > 0 && waves_wide + waves_b8 < waves / 4;
@@ -1193,7 +1218,7 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
             rc = c->baq_t.begin(c->stream);     /* around the call's BAQ kernels (lfq_last_baq_times) */
         }
         c->baq_launches = 0;
-        c->baq_reads = n;
+        c->baq_reads = n_run;
         c->baq_bases = n_bases;
         {
             LfqBaqArgs Ap = A;                      /* the plain instantiation: no indel table */
@@ -1274,17 +1299,34 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
                 rc = lfq_launch_baq(A, std::min<int64_t>(waves * 64, n_narrow + n_band8 - first), 2, c->stream);
                 c->baq_launches++;
             }
-            for (int64_t first = n_narrow + n_band8; rc == LFQ_OK && first < n; first += waves * 64) {
+            for (int64_t first = n_narrow + n_band8; rc == LFQ_OK && first < n_run; first += waves * 64) {
                 A.first_read = (int32_t)first;
-                rc = lfq_launch_baq(A, std::min<int64_t>(waves * 64, n - first), 0, c->stream);
+                rc = lfq_launch_baq(A, std::min<int64_t>(waves * 64, n_run - first), 0, c->stream);
                 c->baq_launches++;
             }
         }
     }
-    if (rc == LFQ_OK) {
+    if (rc == LFQ_OK && !(skip && n_run == 0)) {
         rc = c->baq_t.end(c->stream);
     }
     tmb[3] = lfq_now_ms();
+    if (rc == LFQ_OK && merge) {
+        /* the stored tags over the computed ones, and their ai / ad bits into what the flag merge below reads */
+        uint8_t *const dst[3] = {rs->d_lb, want_idaq ? rs->d_ai : nullptr, want_idaq ? rs->d_ad : nullptr};
+        if (hipMemcpyAsync(rs->d_take, rs->take.data(), (size_t)n, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            rc = LFQ_ERR_HIP;
+        }
+        if (rc == LFQ_OK) {
+            rc = c->fill_t.begin(c->stream);
+        }
+        if (rc == LFQ_OK) {
+            rc = lfq_bam_merge((const int64_t *)rs->d_soff, rs->d_take, rs->d_st, dst, want_idaq ? rs->d_tagfl : nullptr, n, n_bases,
+                               c->stream);
+        }
+        if (rc == LFQ_OK) {
+            rc = c->fill_t.end(c->stream);
+        }
+    }
     /* which reads got an ai / ad tag (bam_md_ext.c:238-243) joins the resident flags as bits 2, 3 on the device; the
      * merged byte travels to pinned memory for the host's event tables.  Nothing here waits for the kernels. */
     if (rc == LFQ_OK && want_idaq) {
@@ -1309,11 +1351,101 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
                 tmb[1] - tmb[0], tmb[2] - tmb[1], tmb[3] - tmb[2], lfq_now_ms() - tmb[3]);
     }
     rs->has_lb = true;
+    rs->filled = merge;
     if (want_idaq) {
         rs->has_idaq = true;
         rs->h_ai = rs->h_ad = nullptr;          /* superseded by the device result */
     }
+    if (stats) {
+        stats->n_need_hmm = n_run;
+        stats->n_hmm_launches = n_run > 0 && max_lq > 0 ? c->baq_launches : 0;
+    }
     return rc;
+}
+
+int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq)
+{
+    if (!c || !rs || rs->c != c || (rs->n > 0 && !rs->qual)) {
+        return LFQ_ERR_INVALID;
+    }
+    return readset_baq_run(c, rs, baq_extended, want_idaq != 0, nullptr, false);
+}
+
+/* lfq_readset_baq where a tag is missing (include/lofreq_amd.h has the rule): need_r on the host, from the CIGARs and the stored
+ * bits of the decode's aux pass */
+int lfq_readset_baq_fill(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq_i, int redo_baq)
+{
+    if (!c || !rs || rs->c != c || (rs->n > 0 && !rs->qual)) {
+        return LFQ_ERR_INVALID;
+    }
+    const bool want_idaq = want_idaq_i != 0;
+    const int64_t n = rs->n;
+    lfq_baq_fill_stats &F = c->fill_stats;
+    memset(&F, 0, sizeof(F));
+    F.n_reads = n;
+    c->fill_hmm = c->fill_merge = 0;
+    if (rs->stored_fl.empty() || n == 0) {
+        const int rc = readset_baq_run(c, rs, baq_extended, want_idaq, nullptr, false, &F);
+        c->fill_hmm = rc == LFQ_OK && F.n_hmm_launches > 0;
+        return rc;
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    LFQ_TRY(readset_baq_wait(rs));
+    LFQ_TRY_HIP(hipStreamSynchronize(c->stream));       /* an earlier fill's copy of rs->take has left the host */
+    const uint8_t keep_bits = (uint8_t)((redo_baq ? 0u : 1u) | (want_idaq ? 6u : 0u));
+    rs->take.resize((size_t)n);
+    std::vector<uint8_t> skip((size_t)n);
+    int64_t part_cnt[LFQ_HOST_PARTS][3];
+    int parts = 1;
+    lfq_for_reads(n, [&](int64_t r0, int64_t r1, int part) {
+        int64_t cnt[3] = {0, 0, 0};
+        for (int64_t r = r0; r < r1; r++) {
+            bool has_ins = false, has_del = false;
+            for (int64_t k = rs->cigar_off[r]; k < rs->cigar_off[r + 1]; k++) {
+                const uint32_t op = rs->cigar[k] & 0xf;
+                has_ins = has_ins || op == 1;
+                has_del = has_del || op == 2;
+            }
+            const uint8_t S = (uint8_t)(rs->stored_fl[(size_t)r] & keep_bits);
+            const bool need = !(S & 1u) || (want_idaq && ((has_del && !(S & 4u)) || (has_ins && !(S & 2u))));
+            skip[(size_t)r] = need ? 0 : 1;
+            rs->take[(size_t)r] = S;
+            for (int t = 0; t < 3; t++) {
+                cnt[t] += (S >> t) & 1u;
+            }
+        }
+        for (int t = 0; t < 3; t++) {
+            part_cnt[part][t] = cnt[t];
+        }
+    }, &parts);
+    const int rc = readset_baq_run(c, rs, baq_extended, want_idaq, skip.data(), true, &F);
+    for (int q = 0; q < parts; q++) {
+        F.n_stored_lb += part_cnt[q][0];
+        F.n_stored_ai += part_cnt[q][1];
+        F.n_stored_ad += part_cnt[q][2];
+    }
+    c->fill_hmm = rc == LFQ_OK && F.n_hmm_launches > 0;
+    c->fill_merge = rc == LFQ_OK;
+    return rc;
+}
+
+int lfq_last_baq_fill_stats(lfq_ctx *c, lfq_baq_fill_stats *s)
+{
+    if (!c || !s) {
+        return LFQ_ERR_INVALID;
+    }
+    *s = c->fill_stats;
+    s->ms_hmm = s->ms_merge = 0.f;
+    if (c->fill_hmm || c->fill_merge) {
+        LFQ_TRY_HIP(hipSetDevice(c->device));
+    }
+    if (c->fill_hmm) {
+        LFQ_TRY(c->baq_t.ms(&s->ms_hmm));
+    }
+    if (c->fill_merge) {
+        LFQ_TRY(c->fill_t.ms(&s->ms_merge));
+    }
+    return LFQ_OK;
 }
 
 int lfq_last_baq_times(lfq_ctx *c, lfq_baq_times *t)
@@ -2988,7 +3120,7 @@ int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset *
     }
     /* what depends on the alignment cannot be carried over: lb, ai / ad, source quality, BI / BD computed from the CIGARs */
     if (rs->has_lb || rs->has_idaq || rs->has_sqb || rs->baq_pending || rs->idq_mode || rs->h_ai || rs->h_ad || rs->h_sq
-        || !rs->sq32.empty()) {
+        || !rs->sq32.empty() || !rs->stored_fl.empty()) {
         return LFQ_ERR_INVALID;
     }
     const int64_t n = rs->n, nb = rs->n_bases;
@@ -3131,10 +3263,10 @@ static LfqBamIn bam_records_in(const lfq_bam_records *recs)
  * from them, with the per-base work -- nibbles -> base codes, qualities, the BI / BD strings found among the aux fields -- done
  * by the two launches of lfq_bamrec.hip.  The host reads per READ only: descriptor checks, prefix sums, the CIGAR words.  *out
  * owns its host arrays (LfqReadsetOwned); the per-base ones come back from the device into pinned memory.  Blocks. */
-int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_readset **out)
+static int readset_from_bam(lfq_ctx *c, const lfq_bam_records *recs, unsigned read_tags, lfq_readset **out)
 {
     if (out) *out = nullptr;
-    if (!c || !recs || !out) {
+    if (!c || !recs || !out || (read_tags & ~(unsigned)(LFQ_BAM_READ_LB | LFQ_BAM_READ_IDAQ))) {
         return LFQ_ERR_INVALID;
     }
     LFQ_TRY(bam_records_check(recs, true, INT64_MAX));
@@ -3187,7 +3319,12 @@ int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_rea
         }
     });
     int any_bi = 0, any_bd = 0;
-    LFQ_TRY(lfq_bam_aux(c, in, desc.data(), n, nb, own->flags.data(), &any_bi, &any_bd));
+    std::vector<uint8_t> stored(read_tags ? (size_t)n : 0);
+    LFQ_TRY(lfq_bam_aux(c, in, desc.data(), n, nb, own->flags.data(), &any_bi, &any_bd, read_tags, stored.data()));
+    uint32_t any_stored = 0;
+    for (uint8_t f : stored) {
+        any_stored |= f;
+    }
     /* the pinned landing area of the per-base arrays, from the context's cache; the host views of the read set point into it */
     const size_t stride = (size_t)lfq_al(nb + 16);
     own->pin_bases = (uint8_t *)rs_cache_take(c, LFQ_RSC_PINBASES, stride * (size_t)(2 + any_bi + any_bd), &own->pin_cap);
@@ -3215,11 +3352,68 @@ int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_rea
     if (rc == LFQ_OK) {
         rc = readset_upload_wait(ns);               /* the per-read arrays are on the device */
     }
+    if (rc == LFQ_OK && any_stored) {
+        /* the strings the records carry, per base, beside the read set's arrays: the merge mask of a fill, then lb | ai | ad */
+        const int64_t each = lfq_al(nb + 16);
+        int64_t off = lfq_al(n);
+        int64_t o_st[3];
+        for (int t = 0; t < 3; t++) {
+            o_st[t] = off;
+            off += ((any_stored >> t) & 1u) ? each : 0;
+        }
+        ns->stored_blob = (uint8_t *)rs_cache_take(c, LFQ_RSC_STORED, (size_t)off, &ns->cap[LFQ_RSC_STORED]);
+        if (!ns->stored_blob) {
+            rc = LFQ_ERR_NOMEM;
+        } else {
+            ns->d_take = ns->stored_blob;
+            for (int t = 0; t < 3; t++) {
+                ns->d_st[t] = ((any_stored >> t) & 1u) ? ns->stored_blob + o_st[t] : nullptr;
+            }
+            ns->stored_fl.swap(stored);
+            rc = lfq_bam_stored(c, ns->d_st);
+        }
+    }
     if (rc != LFQ_OK) {
         lfq_readset_destroy(ns);
         return rc;
     }
     *out = ns;
+    return LFQ_OK;
+}
+
+int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_readset **out)
+{
+    return readset_from_bam(c, recs, 0, out);
+}
+
+int lfq_readset_create_from_bam_tags(lfq_ctx *c, const lfq_bam_records *recs, unsigned read_tags, lfq_readset **out)
+{
+    return readset_from_bam(c, recs, read_tags, out);
+}
+
+int lfq_readset_fetch_stored_tags(lfq_ctx *c, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out,
+                                  uint8_t *stored_flags_out)
+{
+    if (!c || !rs || rs->c != c) {
+        return LFQ_ERR_INVALID;
+    }
+    if (rs->n == 0) {
+        return LFQ_OK;
+    }
+    const size_t nb = (size_t)rs->n_bases;
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    uint8_t *const dst[3] = {lb_out, ai_out, ad_out};
+    for (int t = 0; t < 3; t++) {
+        if (dst[t] && rs->d_st[t] && nb > 0) {
+            LFQ_TRY_HIP(hipMemcpyAsync(dst[t], rs->d_st[t], nb, hipMemcpyDeviceToHost, c->stream));
+        } else if (dst[t]) {
+            memset(dst[t], 33, nb);
+        }
+    }
+    LFQ_TRY_HIP(hipStreamSynchronize(c->stream));
+    for (int64_t r = 0; stored_flags_out && r < rs->n; r++) {
+        stored_flags_out[r] = rs->stored_fl.empty() ? 0 : rs->stored_fl[(size_t)r];
+    }
     return LFQ_OK;
 }
 
@@ -3289,7 +3483,8 @@ int lfq_readset_encode_bam(lfq_ctx *c, lfq_readset *rs, const lfq_bam_records *r
         }
     }
     if (((what & LFQ_BAM_PUT_LB) && !rs->has_lb) || ((what & LFQ_BAM_PUT_IDAQ) && !rs->has_idaq)
-        || ((what & LFQ_BAM_PUT_INDELQUAL) && !rs->idq_mode)) {
+        || ((what & LFQ_BAM_PUT_INDELQUAL) && !rs->idq_mode)
+        || ((what & (LFQ_BAM_PUT_LB | LFQ_BAM_PUT_IDAQ)) && rs->filled)) {    /* (stored bytes are not what alnqual appends) */
         return LFQ_ERR_INVALID;
     }
     if (n == 0) {

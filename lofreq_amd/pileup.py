@@ -327,6 +327,13 @@ def last_bam_decode_times(caller):
     return {k: getattr(t, k) for k, _ in _lib.BamDecodeTimes._fields_}
 
 
+def last_baq_fill_stats(caller):
+    """lfq_last_baq_fill_stats -> dict(n_reads, n_need_hmm, n_stored_lb, n_stored_ai, n_stored_ad, n_hmm_launches, ms_hmm, ms_merge)"""
+    t = _lib.BaqFillStats()
+    _lib.check(_lib.load().lfq_last_baq_fill_stats(caller.h, C.byref(t)), "lfq_last_baq_fill_stats")
+    return {k: getattr(t, k) for k, _ in _lib.BaqFillStats._fields_ if k != "pad"}
+
+
 def last_bam_encode_times(caller):
     """lfq_last_bam_encode_times -> dict(upload_ms, kernels_ms, download_ms, n_reads, n_in_bytes, n_out_bytes, n_launches)"""
     t = _lib.BamEncodeTimes()
@@ -457,11 +464,12 @@ class ReadSet:
         return self
 
     @classmethod
-    def from_bam_records(cls, caller, data, data_off, pos, flag, mapq, l_qname, n_cigar, l_qseq, ref):
+    def from_bam_records(cls, caller, data, data_off, pos, flag, mapq, l_qname, n_cigar, l_qseq, ref, read_tags=0):
         """lfq_readset_create_from_bam: the read set of BAM records as they lie in memory -- data: the bytes of every record from
         read_name on (bam1_t.data), concatenated; data_off [n + 1] into it; pos, flag, mapq, l_qname, n_cigar, l_qseq: the core
         fields per read; ref: the contig (bytes).  Bases, qualities and BI / BD are decoded on the device; the read set owns
-        its host arrays, so only `ref` is kept alive here."""
+        its host arrays, so only `ref` is kept alive here.  read_tags (lfq_readset_create_from_bam_tags): LFQ_BAM_READ_LB /
+        LFQ_BAM_READ_IDAQ keep the first lb / ai and ad field of every record on the device for baq_fill()."""
         self = cls.__new__(cls)
         self.caller = caller
         self.L = _lib.load()
@@ -480,7 +488,11 @@ class ReadSet:
         rc.ref_len = len(self._keep["ref"])
         self.seq_off = np.concatenate([[0], np.cumsum(a["l_qseq"], dtype=np.int64)]).astype(np.int64)
         h = C.c_void_p()
-        _lib.check(self.L.lfq_readset_create_from_bam(caller.h, C.byref(rc), C.byref(h)), "lfq_readset_create_from_bam")
+        if read_tags:
+            _lib.check(self.L.lfq_readset_create_from_bam_tags(caller.h, C.byref(rc), int(read_tags), C.byref(h)),
+                       "lfq_readset_create_from_bam_tags")
+        else:
+            _lib.check(self.L.lfq_readset_create_from_bam(caller.h, C.byref(rc), C.byref(h)), "lfq_readset_create_from_bam")
         self.h = h
         if not hasattr(caller, "_readsets"):
             import weakref
@@ -496,6 +508,16 @@ class ReadSet:
         out = [np.zeros(max(nb, 1), np.uint8) for _ in range(4)] + [np.zeros(max(self.n, 1), np.uint8)]
         _lib.check(self.L.lfq_readset_fetch_bases(self.caller.h, self.h, *[o.ctypes.data for o in out]), "lfq_readset_fetch_bases")
         return tuple(o[:nb] for o in out[:4]) + (out[4][: self.n],)
+
+    def fetch_stored_tags(self):
+        """lfq_readset_fetch_stored_tags: the lb / ai / ad strings the records carried, from the device -> (lb, ai, ad: uint8 per
+        base in the seq_off layout, '!' throughout for a read without the tag; flags: uint8 per read, bit 0 / 1 / 2 = lb / ai /
+        ad stored)"""
+        nb = int(self.seq_off[-1])
+        out = [np.zeros(max(nb, 1), np.uint8) for _ in range(3)] + [np.zeros(max(self.n, 1), np.uint8)]
+        _lib.check(self.L.lfq_readset_fetch_stored_tags(self.caller.h, self.h, *[o.ctypes.data for o in out]),
+                   "lfq_readset_fetch_stored_tags")
+        return tuple(o[:nb] for o in out[:3]) + (out[3][: self.n],)
 
     def encode_bam(self, recs, src=None, what=_lib.LFQ_BAM_PUT_ALIGNMENT):
         """lfq_readset_encode_bam: the results of this read set's steps written into the bytes of the BAM records its reads came
@@ -551,6 +573,12 @@ class ReadSet:
 
     def baq(self, extended=True, idaq=False):
         _lib.check(self.L.lfq_readset_baq(self.caller.h, self.h, 1 if extended else 0, 1 if idaq else 0), "lfq_readset_baq")
+
+    def baq_fill(self, extended=True, idaq=False, redo_baq=False):
+        """lfq_readset_baq_fill: baq() that keeps the stored lb / ai / ad of from_bam_records(..., read_tags=) and runs the HMM
+        only for the reads that lack a tag (`lofreq call`'s default; redo_baq: -D)"""
+        _lib.check(self.L.lfq_readset_baq_fill(self.caller.h, self.h, 1 if extended else 0, 1 if idaq else 0, 1 if redo_baq else 0),
+                   "lfq_readset_baq_fill")
 
     def source_qual(self, def_nm_q=-1, min_bq=6, ign=None):
         sq = np.zeros(max(self.n, 1), np.int32)

@@ -48,6 +48,7 @@ extern "C" {
 /* (10 still: lfq_readset_create_from_bam, lfq_readset_fetch_bases, lfq_last_bam_decode_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_readset_create_from_bam_tags, lfq_readset_fetch_stored_tags, lfq_readset_baq_fill, lfq_last_baq_fill_stats likewise.) */
 /* (10 still: lfq_readset_encode_bam, lfq_last_bam_encode_times are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_bgzf_inflate, lfq_last_bgzf_times, lfq_bam_scan_records and its helpers, lfq_readset_create_from_bgzf likewise.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -732,6 +733,108 @@ typedef struct lfq_bam_encode_times {
     int n_launches;
 } lfq_bam_encode_times;
 int lfq_last_bam_encode_times(lfq_ctx *ctx, lfq_bam_encode_times *t);
+
+/* --- BGZF blocks inflated on the device: the step in front of lfq_readset_create_from_bam ------------------------------------------
+ * A BAM file is a series of BGZF blocks (SAM specification section 4.1), each a gzip member of at most 65536 bytes that inflates
+ * to at most 65536.  lfq_bgzf_inflate takes the blocks of a region as they lie in the file: they go down the link compressed, one
+ * launch inflates them (raw deflate, RFC 1951: stored, fixed and dynamic blocks; lofreq_amd/csrc/lfq_inflate.h) and checks each
+ * block's CRC-32 and ISIZE against its trailer, and the inflated bytes come back -- and stay on the device as well, see below.
+ *
+ * The host walks the block headers: ID1 ID2 = 31 139, CM = 8, FLG with FEXTRA, and among the extra subfields -- wherever it stands
+ * -- the one with SI1 SI2 = 'B' 'C' and SLEN 2, whose value + 1 is the block's size; ISIZE is the block's last four bytes.
+ * LFQ_ERR_INVALID, before a device is touched: a NULL ctx or out, n_bytes < 0, a NULL comp with n_bytes > 0; a bad magic, CM or
+ * FLG; a subfield that runs past XLEN; no BC subfield; a block shorter than its own header plus trailer; a header or a block
+ * that runs past n_bytes; an ISIZE above 65536.
+ * The compressed bytes go down in one copy, from the caller's memory if it is pinned and through a pinned staging area otherwise.
+ * The empty block (the 28-byte end-of-file marker, ISIZE 0) is an ordinary block; bytes between the end of the final deflate block
+ * and the trailer are ignored; n_bytes == 0 is LFQ_OK with an empty result and nothing launched.
+ *
+ * status[b] is 0 or the first thing found wrong with block b:
+ *   1 malformed deflate data (block type 3, a stored block whose LEN is not ~NLEN, an over-subscribed or incomplete code -- a single
+ *     code of one bit excepted, as in zlib --, a 16-repeat with nothing to repeat, a repeat past the last length, no end-of-block
+ *     code, a code that is not assigned, length symbol 286 / 287, distance symbol 30 / 31)
+ *   2 the input ends inside a symbol, a block header or a stored block
+ *   3 a symbol would write past ISIZE
+ *   4 a match reaches before the first byte of the block's own output (BGZF blocks share no history)
+ *   5 the stream ends with fewer than ISIZE bytes written
+ *   6 the CRC-32 of the output is not the trailer's
+ * Each is decided from the positions before anything is read or written: the kernel terminates on any input, no load leaves a
+ * block's compressed bytes by more than the aligned dword around its first / last byte inside the library's own buffer, and no
+ * store leaves [data_off[b], data_off[b] + ISIZE_b).  The bytes of a block with a nonzero status are unspecified; the other blocks
+ * of the call are intact.  Any nonzero status: LFQ_ERR_INVALID with *out still pointing at the result, so that status[] can be
+ * read; the context stays usable.
+ *
+ * The result is the context's, valid until its next lfq_bgzf_inflate or lfq_destroy.  Until then the inflated bytes also STAY ON
+ * THE DEVICE: lfq_readset_create_from_bam(_tags) and lfq_readset_encode_bam on this context, given records whose `data` lies inside
+ * result->data, copy them device to device instead of across the link again (n_decodes_from_device counts such calls).  Blocks. */
+typedef struct lfq_bgzf_result {
+    int64_t n_blocks;
+    const int64_t *comp_off;   /* [n_blocks + 1] offsets of the blocks in the input */
+    const int64_t *data_off;   /* [n_blocks + 1] offsets of their output in data (prefix sums of ISIZE) */
+    const int32_t *status;     /* [n_blocks] 0 = ok */
+    const uint8_t *data;       /* the inflated bytes, pinned host memory, the context's */
+    int64_t n_bytes;
+} lfq_bgzf_result;
+int lfq_bgzf_inflate(lfq_ctx *ctx, const uint8_t *comp, int64_t n_bytes, const lfq_bgzf_result **out);
+/* the context's last lfq_bgzf_inflate on the device's clock: the compressed bytes and block descriptors down, the kernel, statuses
+ * and inflated bytes back into pinned memory; n_decodes_from_device: the decode / encode calls since then that took their records
+ * from the resident inflated bytes */
+typedef struct lfq_bgzf_times {
+    double upload_ms, kernels_ms, download_ms;
+    int64_t n_blocks, n_in_bytes, n_out_bytes;
+    int n_launches, n_decodes_from_device;
+} lfq_bgzf_times;
+int lfq_last_bgzf_times(lfq_ctx *ctx, lfq_bgzf_times *t);
+
+/* The records of inflated BAM bytes, located and filtered as sam_itr_next + mplp_func (plp.c:606-722) keep them.  Host only, no
+ * context.  bam[first .. stop) is a chain of records as they lie in the file: block_size (int32) and that many bytes, of which the
+ * first 32 are the core (refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq, next_refID, next_pos, tlen).  `first` points
+ * behind the file's header (magic, text, references), which stays the caller's, as do BED overlap (the caller owns the BED: it
+ * drops entries from the arrays) and MPLP_ILLUMINA13.
+ * A record is kept when, in this order:
+ *   refID >= 0, and refID == tid when tid >= 0;
+ *   !(flag & flag_mask)                                             (unmapped, secondary, QC fail, duplicate: plp.c:613-624);
+ *   pos < end && endpos > beg, endpos = pos + the reference bases of the CIGAR (M D N = X), or pos + 1 when that is 0 (bam_endpos);
+ *   mapq > max_mq: the mapq handed out is max_mq; otherwise mapq < min_mq drops the record; otherwise, with no_orphan, a paired
+ *     read (flag 1) without the proper-pair bit (flag 2) is dropped -- the reference's else-if chain (plp.c:707-721);
+ *   l_seq > 0 and n_cigar_op > 0                                    (as lfq_region_add_record drops the others).
+ * (*out)->recs describes the kept records where they lie: data = bam, data_off[r] = the record's read_name, data_off[n_reads] =
+ * the end of the last kept record (`first` when none is kept).  Records in a file do not abut -- the next one's block_size and
+ * core, and the dropped records, lie between -- so record r is [data_off[r], data_end[r]) and NOT [data_off[r], data_off[r + 1]):
+ * lfq_readset_create_from_bam_scan and lfq_readset_create_from_bgzf decode with data_end; lfq_readset_create_from_bam takes
+ * records that abut.
+ * n_seen: the complete records walked; n_consumed: the offset of the first record that does not end before `stop` (a chunk may end
+ * inside a record or its block_size: the caller carries the tail over; LFQ_OK).
+ * LFQ_ERR_INVALID (*out = NULL): a NULL bam, o or out; first < 0, stop < first; block_size < 32; l_seq < 0 or a record whose
+ * l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq exceeds its block_size - 32. */
+typedef struct lfq_bam_scan_opts {
+    int32_t tid;               /* -1 = any */
+    int64_t beg, end;          /* 0-based, half-open */
+    int min_mq, max_mq, no_orphan;
+    unsigned flag_mask;
+} lfq_bam_scan_opts;
+/* tid -1, beg 0, end INT64_MAX, min_mq 0, max_mq 255, no_orphan 0, flag_mask 4 | 256 | 512 | 1024 */
+void lfq_bam_scan_opts_init(lfq_bam_scan_opts *o);
+typedef struct lfq_bam_scan {
+    lfq_bam_records recs;      /* the kept records; ref / ref_len are 0 for the caller to set */
+    const int64_t *data_end;   /* [n_reads] one past the last byte of record r */
+    int64_t n_seen, n_consumed;
+} lfq_bam_scan;
+int lfq_bam_scan_records(const uint8_t *bam, int64_t first, int64_t stop, const lfq_bam_scan_opts *o, lfq_bam_scan **out);
+void lfq_bam_scan_free(lfq_bam_scan *s);
+/* lfq_readset_create_from_bam_tags on the records of a scan -- or of any lfq_bam_scan the caller fills in, such as the kept
+ * records of several scans over one buffer (integration/lofreq_amd_region.c) --: record r is [data_off[r], data_end[r]), with
+ * data_end[r] <= data_off[r + 1]; recs.ref / ref_len set by the caller; n_seen and n_consumed are not read.  Records inside the
+ * context's live lfq_bgzf_inflate result are taken from the device copy.  Everything else as lfq_readset_create_from_bam_tags. */
+int lfq_readset_create_from_bam_scan(lfq_ctx *ctx, const lfq_bam_scan *scan, unsigned read_tags, lfq_readset **out);
+
+/* lfq_bgzf_inflate + lfq_bam_scan_records over [first, stop_or_neg) of the inflated bytes (negative: to their end) +
+ * lfq_readset_create_from_bam_tags on the kept records, whose bytes are taken from the device copy of the inflated data: in every
+ * observable way that decode on those records.  *n_consumed_or_null: the scan's n_consumed.  Errors of the three steps as they
+ * return them; *out = NULL then. */
+int lfq_readset_create_from_bgzf(lfq_ctx *ctx, const uint8_t *comp, int64_t n_bytes, int64_t first, int64_t stop_or_neg,
+                                 const lfq_bam_scan_opts *o, const char *ref, int64_t ref_len, unsigned read_tags,
+                                 lfq_readset **out, int64_t *n_consumed_or_null);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

@@ -41,6 +41,9 @@ static int rv_reserve(rvec *v, int64_t more)
     return LFQ_OK;
 }
 
+/* one lfq_region_add_bgzf call: where its blocks lie in the region's staging, and the part of their inflated bytes to scan */
+typedef struct { int64_t comp_at, first, stop; } reg_chunk;
+
 /* the reads of one region as the flat arrays lfq_readset_create takes; two of them, because the host arrays of region k
  * must stay as they are until region k is finished -- which happens while region k + 1 is being filled */
 typedef struct {
@@ -48,7 +51,12 @@ typedef struct {
     /* lfq_region_add_record: the records as they lie in bam1_t.data (pinned: they go down by DMA) and their descriptors; pos,
      * mapq and flags above are shared with the array road */
     rvec rec, rec_off, rec_flag, rec_lqname, rec_ncig, rec_lqseq;
-    int fed_by;                     /* 0: no read yet, 1: lfq_region_add_read, 2: lfq_region_add_record */
+    /* lfq_region_add_bgzf: the compressed blocks of every chunk, one behind the other (pinned), the chunks, and -- filled by
+     * lfq_region_end from the scans of the inflated bytes -- where each kept record ends; the descriptors above are shared with
+     * the record road */
+    rvec bgz, chunk, rec_end;
+    int32_t bgz_tid;
+    int fed_by;                     /* 0: no read yet, 1: lfq_region_add_read, 2: lfq_region_add_record, 3: lfq_region_add_bgzf */
     int64_t n, nb;
     int any_bi, any_bd;
     char *target;
@@ -116,12 +124,16 @@ static void buf_init(reg_buf *b)
     b->rec_flag.elt = b->rec_lqname.elt = sizeof(uint16_t);
     b->rec_ncig.elt = sizeof(uint32_t);
     b->rec_lqseq.elt = sizeof(int32_t);
+    b->bgz.elt = 1;
+    b->bgz.pinned = 1;
+    b->chunk.elt = sizeof(reg_chunk);
+    b->rec_end.elt = sizeof(int64_t);
 }
 
 static void buf_free(reg_buf *b)
 {
     rvec *all[] = {&b->pos, &b->cig_off, &b->cig, &b->seq_off, &b->seq, &b->qual, &b->mapq, &b->rev, &b->bi, &b->bd, &b->flags,
-                   &b->rec, &b->rec_off, &b->rec_flag, &b->rec_lqname, &b->rec_ncig, &b->rec_lqseq};
+                   &b->rec, &b->rec_off, &b->rec_flag, &b->rec_lqname, &b->rec_ncig, &b->rec_lqseq, &b->bgz, &b->chunk, &b->rec_end};
     size_t i;
     for (i = 0; i < sizeof(all) / sizeof(all[0]); i++) {
         if (all[i]->pinned) {
@@ -231,6 +243,7 @@ int lfq_region_begin(lfq_region *r, const char *target_name, const char *ref, in
     b->pos.n = b->cig.n = b->seq.n = b->qual.n = b->mapq.n = b->rev.n = b->bi.n = b->bd.n = b->flags.n = 0;
     b->cig_off.n = b->seq_off.n = 0;
     b->rec.n = b->rec_off.n = b->rec_flag.n = b->rec_lqname.n = b->rec_ncig.n = b->rec_lqseq.n = 0;
+    b->bgz.n = b->chunk.n = b->rec_end.n = 0;
     b->fed_by = 0;
     b->n = b->nb = 0;
     b->any_bi = b->any_bd = 0;
@@ -278,8 +291,8 @@ int lfq_region_add_read(lfq_region *r, int32_t pos, int flag, int mapq, int n_ci
         return 0;                               /* nothing the pileup could place */
     }
     b = &r->buf[r->cur];
-    if (b->fed_by == 2) {
-        return LFQ_ERR_INVALID;                 /* a region is fed by one of the two functions only */
+    if (b->fed_by > 1) {
+        return LFQ_ERR_INVALID;                 /* a region is fed by one of the three functions only */
     }
     b->fed_by = 1;
     if (rv_reserve(&b->pos, 1) || rv_reserve(&b->cig_off, 1) || rv_reserve(&b->seq_off, 1) || rv_reserve(&b->cig, n_cigar)
@@ -342,8 +355,8 @@ int lfq_region_add_record(lfq_region *r, int32_t pos, int flag, int mapq, int l_
         return 0;                               /* nothing the pileup could place */
     }
     b = &r->buf[r->cur];
-    if (b->fed_by == 1) {
-        return LFQ_ERR_INVALID;                 /* a region is fed by one of the two functions only */
+    if (b->fed_by == 1 || b->fed_by == 3) {
+        return LFQ_ERR_INVALID;                 /* a region is fed by one of the three functions only */
     }
     b->fed_by = 2;
     if (rv_reserve(&b->pos, 1) || rv_reserve(&b->mapq, 1) || rv_reserve(&b->flags, 1) || rv_reserve(&b->rec, (int64_t)l_data + 16)
@@ -369,12 +382,42 @@ int lfq_region_add_record(lfq_region *r, int32_t pos, int flag, int mapq, int l_
     return 1;
 }
 
-/* the read set of a region fed by lfq_region_add_record: decoded on the device; which tags its reads came with is what the
- * decode found */
+/* One chunk of an index query -- or the whole region -- as it lies in the file: n_bytes of whole BGZF blocks.  They are copied into
+ * the region's pinned staging; lfq_region_end inflates, scans and decodes them on the device (lofreq_amd_region.h) */
+int lfq_region_add_bgzf(lfq_region *r, int32_t tid, const uint8_t *comp, int64_t n_bytes, int64_t first, int64_t stop_or_neg)
+{
+    reg_buf *b;
+    reg_chunk *c;
+    if (!r || !r->open || n_bytes < 0 || (n_bytes > 0 && !comp) || first < 0 || (stop_or_neg >= 0 && stop_or_neg < first)) {
+        return LFQ_ERR_INVALID;
+    }
+    b = &r->buf[r->cur];
+    if (b->fed_by == 1 || b->fed_by == 2 || (b->chunk.n > 0 && b->bgz_tid != tid)) {
+        return LFQ_ERR_INVALID;                 /* a region is fed by one of the three functions only, and lies on one contig */
+    }
+    b->fed_by = 3;
+    b->bgz_tid = tid;
+    if (rv_reserve(&b->bgz, n_bytes + 16) || rv_reserve(&b->chunk, 1)) {
+        return LFQ_ERR_NOMEM;
+    }
+    if (n_bytes > 0) {
+        memcpy((uint8_t *)b->bgz.p + b->bgz.n, comp, (size_t)n_bytes);
+    }
+    c = (reg_chunk *)b->chunk.p + b->chunk.n;
+    c->comp_at = b->bgz.n;
+    c->first = first;
+    c->stop = stop_or_neg;
+    b->bgz.n += n_bytes;
+    b->chunk.n += 1;
+    return LFQ_OK;
+}
+
+static int region_decoded_flags(lfq_region *r, reg_buf *b, int rc);
+
+/* the read set of a region fed by lfq_region_add_record: decoded on the device */
 static int region_readset_from_records(lfq_region *r, reg_buf *b)
 {
     lfq_bam_records rc_;
-    int64_t i;
     int rc;
     memset(&rc_, 0, sizeof(rc_));
     rc_.n_reads = b->n;
@@ -393,6 +436,111 @@ static int region_readset_from_records(lfq_region *r, reg_buf *b)
     } else {
         rc = lfq_readset_create_from_bam(r->ctx, &rc_, &b->rs);
     }
+    return region_decoded_flags(r, b, rc);
+}
+
+/* the read set of a region fed by lfq_region_add_bgzf: the staged blocks inflated in one call, every chunk's part of the
+ * inflated bytes scanned with the region's filters, the kept records of all chunks decoded from the device copy */
+static int region_readset_from_bgzf(lfq_region *r, reg_buf *b)
+{
+    const lfq_bgzf_result *R = NULL;
+    const reg_chunk *ch = (const reg_chunk *)b->chunk.p;
+    lfq_bam_scan_opts so;
+    lfq_bam_scan S;
+    int64_t k, blk = 0, last_end = 0;
+    int rc = lfq_bgzf_inflate(r->ctx, (const uint8_t *)b->bgz.p, b->bgz.n, &R);
+    if (rc != LFQ_OK) {
+        return rc;
+    }
+    lfq_bam_scan_opts_init(&so);
+    so.tid = b->bgz_tid;
+    so.beg = b->beg;
+    so.end = b->end;
+    so.min_mq = r->o.min_mq;
+    so.max_mq = r->o.max_mq;
+    so.no_orphan = r->o.no_orphan;
+    b->n = b->nb = 0;
+    for (k = 0; k < b->chunk.n; k++) {
+        lfq_bam_scan *s = NULL;
+        int64_t base, lim = R->n_bytes, first, stop, i, m;
+        while (blk < R->n_blocks && R->comp_off[blk] < ch[k].comp_at) {
+            blk++;
+        }
+        if (R->comp_off[blk] != ch[k].comp_at) {
+            return LFQ_ERR_INVALID;             /* (a chunk is a whole number of blocks) */
+        }
+        base = R->data_off[blk];
+        if (k + 1 < b->chunk.n) {
+            int64_t nb_ = blk;
+            while (nb_ < R->n_blocks && R->comp_off[nb_] < ch[k + 1].comp_at) {
+                nb_++;
+            }
+            lim = R->data_off[nb_];
+        }
+        first = base + ch[k].first;
+        stop = ch[k].stop < 0 ? lim : base + ch[k].stop;
+        if (first > lim || stop > lim) {
+            return LFQ_ERR_INVALID;
+        }
+        rc = lfq_bam_scan_records(R->data, first, stop, &so, &s);
+        if (rc != LFQ_OK) {
+            return rc;
+        }
+        m = s->recs.n_reads;
+        if (rv_reserve(&b->pos, m) || rv_reserve(&b->mapq, m) || rv_reserve(&b->rec_off, m + 1) || rv_reserve(&b->rec_end, m)
+            || rv_reserve(&b->rec_flag, m) || rv_reserve(&b->rec_lqname, m) || rv_reserve(&b->rec_ncig, m)
+            || rv_reserve(&b->rec_lqseq, m)) {
+            lfq_bam_scan_free(s);
+            return LFQ_ERR_NOMEM;
+        }
+        for (i = 0; i < m; i++) {
+            ((int64_t *)b->rec_off.p)[b->n + i] = s->recs.data_off[i];
+            ((int64_t *)b->rec_end.p)[b->n + i] = s->data_end[i];
+            ((int32_t *)b->pos.p)[b->n + i] = s->recs.pos[i];
+            ((uint8_t *)b->mapq.p)[b->n + i] = s->recs.mapq[i];
+            ((uint16_t *)b->rec_flag.p)[b->n + i] = s->recs.flag[i];
+            ((uint16_t *)b->rec_lqname.p)[b->n + i] = s->recs.l_qname[i];
+            ((uint32_t *)b->rec_ncig.p)[b->n + i] = s->recs.n_cigar[i];
+            ((int32_t *)b->rec_lqseq.p)[b->n + i] = s->recs.l_qseq[i];
+            b->nb += s->recs.l_qseq[i];
+            last_end = s->data_end[i];
+        }
+        b->n += m;
+        b->pos.n = b->mapq.n = b->rec_off.n = b->rec_end.n = b->rec_flag.n = b->rec_lqname.n = b->rec_ncig.n = b->rec_lqseq.n = b->n;
+        lfq_bam_scan_free(s);
+    }
+    if (b->n == 0) {
+        return LFQ_OK;
+    }
+    b->flags.n = 0;
+    if (rv_reserve(&b->flags, b->n)) {
+        return LFQ_ERR_NOMEM;
+    }
+    b->flags.n = b->n;
+    ((int64_t *)b->rec_off.p)[b->n] = last_end;
+    b->rec_off.n = b->n + 1;
+    memset(&S, 0, sizeof(S));
+    S.recs.n_reads = b->n;
+    S.recs.data = R->data;
+    S.recs.data_off = (const int64_t *)b->rec_off.p;
+    S.recs.pos = (const int32_t *)b->pos.p;
+    S.recs.flag = (const uint16_t *)b->rec_flag.p;
+    S.recs.mapq = (const uint8_t *)b->mapq.p;
+    S.recs.l_qname = (const uint16_t *)b->rec_lqname.p;
+    S.recs.n_cigar = (const uint32_t *)b->rec_ncig.p;
+    S.recs.l_qseq = (const int32_t *)b->rec_lqseq.p;
+    S.recs.ref = b->ref;
+    S.recs.ref_len = b->ref_len;
+    S.data_end = (const int64_t *)b->rec_end.p;
+    rc = lfq_readset_create_from_bam_scan(r->ctx, &S, r->reuse_tags ? LFQ_BAM_READ_LB | (r->o.use_idaq ? LFQ_BAM_READ_IDAQ : 0) : 0,
+                                          &b->rs);
+    return region_decoded_flags(r, b, rc);
+}
+
+/* which tags the reads of a decoded region came with is what the decode found */
+static int region_decoded_flags(lfq_region *r, reg_buf *b, int rc)
+{
+    int64_t i;
     if (rc == LFQ_OK) {
         rc = lfq_readset_fetch_bases(r->ctx, b->rs, NULL, NULL, NULL, NULL, (uint8_t *)b->flags.p);
         if (rc != LFQ_OK) {
@@ -412,12 +560,20 @@ static int region_start(lfq_region *r, reg_buf *b)
 {
     lfq_pileup_reads rd;
     lfq_pileup_indel_tags tg;
-    int rc;
+    int rc = LFQ_OK;
+    if (b->fed_by == 3) {
+        rc = region_readset_from_bgzf(r, b);    /* (how many reads the region has is what the scan keeps) */
+        if (rc != LFQ_OK) {
+            return rc;
+        }
+    }
     if (b->n == 0) {
         b->started = 1;
         return LFQ_OK;
     }
-    if (b->fed_by == 2) {
+    if (b->fed_by == 3) {
+        /* decoded above */
+    } else if (b->fed_by == 2) {
         rc = region_readset_from_records(r, b);
     } else {
         memset(&rd, 0, sizeof(rd));
@@ -452,7 +608,7 @@ static int region_start(lfq_region *r, reg_buf *b)
         }
     }
     if (r->o.use_baq || r->o.use_idaq) {                                /* plp.c:667-683 */
-        if (r->reuse_tags && b->fed_by == 2) {                          /* baq_flag 1, or 2 under -D (plp.c:676-678) */
+        if (r->reuse_tags && b->fed_by >= 2) {                        /* baq_flag 1, or 2 under -D (plp.c:676-678) */
             rc = lfq_readset_baq_fill(r->ctx, b->rs, r->o.baq_extended, r->o.use_idaq ? 1 : 0, r->reuse_tags == 2);
         } else {
             rc = lfq_readset_baq(r->ctx, b->rs, r->o.baq_extended, r->o.use_idaq ? 1 : 0);

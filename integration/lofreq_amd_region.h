@@ -8,7 +8,8 @@
  *     call_vars per column                 lofreq_call.c:887-935 (call_indels, call_snvs, report_var)
  * What stays with htslib on the CPU: opening the BAM, the index query, decompressing records into bam1_t, the read-level
  * filters of mplp_func (plp.c:608-632: unmapped / secondary / QC-fail / duplicate, BED overlap).  Unpacking a record's bases,
- * qualities and BI / BD tags is the device's with lfq_region_add_record, the caller's thread's with lfq_region_add_read.  The column callback
+ * qualities and BI / BD tags is the device's with lfq_region_add_record, the caller's thread's with lfq_region_add_read; with
+ * lfq_region_add_bgzf the decompression, the record iteration and those filters (BED overlap excepted) leave htslib too.  The column callback
  * (integration/lofreq_amd_shim.c) keeps working for everything that wants plp_col_t; this path is for `lofreq call`
  * itself, whose end-to-end time was the CPU pileup + BAQ once the per-column statistics ran on the GPU.
  *
@@ -113,6 +114,19 @@ int lfq_region_add_read(lfq_region *r, int32_t pos, int flag, int mapq, int n_ci
  * (LFQ_ERR_INVALID from lfq_region_end).  lfq_region_end blocks for the decode of the region it starts. */
 int lfq_region_add_record(lfq_region *r, int32_t pos, int flag, int mapq, int l_qname, int n_cigar, int l_qseq,
                           const uint8_t *data, int l_data);
+/* The region's reads as they lie IN THE FILE: n_bytes of whole BGZF blocks -- the compressed bytes between the two virtual offsets
+ * of a chunk of the index query, with first = the low 16 bits of the chunk's begin offset (where its first record starts in the
+ * inflated bytes of its first block) and stop_or_neg = where to stop in the chunk's inflated bytes, or negative for their end.
+ * Once or several times per region, chunks in file order, all of contig tid.  No sam_itr_next, no inflate on this thread: the
+ * blocks are copied into a pinned staging buffer, and lfq_region_end inflates them on the device (lfq_bgzf_inflate), scans every
+ * chunk's records with the filters of plp.c:606-722 (lfq_bam_scan_records: refID == tid, the flag mask 4 | 256 | 512 | 1024, overlap
+ * with the region's [beg0, end0), min_mq / max_mq / no_orphan of the options) and decodes the kept ones from the device copy
+ * (lfq_readset_create_from_bam_scan) -- with lfq_region_set_reuse_tags as for lfq_region_add_record.  BED overlap and
+ * MPLP_ILLUMINA13 are not applied on this road.  VCF lines, counters and the return values of lfq_region_end are those of the same
+ * records fed by lfq_region_add_record.  Returns LFQ_OK; mixing it with the other two functions within a region is
+ * LFQ_ERR_INVALID.  A block that does not inflate, a malformed record chain or aux field fails the region (LFQ_ERR_INVALID from
+ * lfq_region_end). */
+int lfq_region_add_bgzf(lfq_region *r, int32_t tid, const uint8_t *comp, int64_t n_bytes, int64_t first, int64_t stop_or_neg);
 int lfq_region_end(lfq_region *r);
 /* finishes the last region; *indel_calls_wo_idaq_or_null: report_var's counter (lofreq_call.c:109-111) */
 int lfq_region_close(lfq_region *r, int64_t *indel_calls_wo_idaq_or_null);

@@ -18,7 +18,7 @@ from .viterbi import viterbi_batch
 from .indelqual import indelqual_batch
 from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_indel_quals, format_plp_quals,
                      format_plp_summary, last_bam_decode_times, last_bam_encode_times, last_baq_fill_stats, last_plp_quals_times, pileup_indel_columns, pileup_snv_tracks, plp_quals,
-                     skip_snv_columns)
+                     skip_snv_columns, BgzfError, bam_scan_records, bgzf_inflate, last_bgzf_times)
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
 
@@ -34,4 +34,5 @@ __all__ = [
     "last_bam_encode_times", "LFQ_BAM_PUT_ALIGNMENT", "LFQ_BAM_DROP_ALN_TAGS", "LFQ_BAM_PUT_LB", "LFQ_BAM_PUT_IDAQ",
     "LFQ_BAM_KEEP_EXISTING", "LFQ_BAM_PUT_INDELQUAL",
     "LFQ_BAM_READ_LB", "LFQ_BAM_READ_IDAQ", "last_baq_fill_stats",
+    "bgzf_inflate", "BgzfError", "bam_scan_records", "last_bgzf_times",
 ]

@@ -166,6 +166,28 @@ class BamEncodeTimes(C.Structure):
                 ("n_in_bytes", C.c_int64), ("n_out_bytes", C.c_int64), ("n_launches", C.c_int)]
 
 
+class BgzfResult(C.Structure):
+    """lfq_bgzf_result: owned by the context, valid until its next lfq_bgzf_inflate"""
+    _fields_ = [("n_blocks", C.c_int64)] + [(n, C.c_void_p) for n in ("comp_off", "data_off", "status", "data")] + [
+        ("n_bytes", C.c_int64)]
+
+
+class BgzfTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("kernels_ms", C.c_double), ("download_ms", C.c_double), ("n_blocks", C.c_int64),
+                ("n_in_bytes", C.c_int64), ("n_out_bytes", C.c_int64), ("n_launches", C.c_int), ("n_decodes_from_device", C.c_int)]
+
+
+class BamScanOpts(C.Structure):
+    """lfq_bam_scan_opts"""
+    _fields_ = [("tid", C.c_int32), ("beg", C.c_int64), ("end", C.c_int64), ("min_mq", C.c_int), ("max_mq", C.c_int),
+                ("no_orphan", C.c_int), ("flag_mask", C.c_uint)]
+
+
+class BamScan(C.Structure):
+    """lfq_bam_scan: freed with lfq_bam_scan_free"""
+    _fields_ = [("recs", BamRecords), ("data_end", C.c_void_p), ("n_seen", C.c_int64), ("n_consumed", C.c_int64)]
+
+
 class PileupIndelTags(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("bi", "bd", "ai", "ad", "tag_flags", "sq")]
 
@@ -229,6 +251,8 @@ EXPORTS = [
     "lfq_readset_create_from_bam", "lfq_readset_fetch_bases", "lfq_last_bam_decode_times",
     "lfq_readset_create_from_bam_tags", "lfq_readset_fetch_stored_tags", "lfq_readset_baq_fill", "lfq_last_baq_fill_stats",
     "lfq_readset_encode_bam", "lfq_last_bam_encode_times",
+    "lfq_bgzf_inflate", "lfq_last_bgzf_times", "lfq_bam_scan_opts_init", "lfq_bam_scan_records", "lfq_bam_scan_free",
+    "lfq_readset_create_from_bgzf", "lfq_readset_create_from_bam_scan",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
     "lfq_plp_quals_from_tracks", "lfq_format_plp_quals", "lfq_set_indel_arrays_all_columns", "lfq_format_plp_indel_quals",
@@ -368,6 +392,16 @@ def load():
     L.lfq_last_bam_decode_times.argtypes = [vp, C.POINTER(BamDecodeTimes)]
     L.lfq_readset_encode_bam.argtypes = [vp, vp, C.POINTER(BamRecords), vp, C.c_uint, C.POINTER(C.POINTER(BamEncoded))]
     L.lfq_last_bam_encode_times.argtypes = [vp, C.POINTER(BamEncodeTimes)]
+    L.lfq_bgzf_inflate.argtypes = [vp, vp, C.c_int64, C.POINTER(C.POINTER(BgzfResult))]
+    L.lfq_last_bgzf_times.argtypes = [vp, C.POINTER(BgzfTimes)]
+    L.lfq_bam_scan_opts_init.argtypes = [C.POINTER(BamScanOpts)]
+    L.lfq_bam_scan_opts_init.restype = None
+    L.lfq_bam_scan_records.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(BamScanOpts), C.POINTER(C.POINTER(BamScan))]
+    L.lfq_bam_scan_free.argtypes = [C.POINTER(BamScan)]
+    L.lfq_bam_scan_free.restype = None
+    L.lfq_readset_create_from_bam_scan.argtypes = [vp, C.POINTER(BamScan), C.c_uint, C.POINTER(vp)]
+    L.lfq_readset_create_from_bgzf.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(BamScanOpts), vp, C.c_int64,
+                                               C.c_uint, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.lfq_readset_destroy.argtypes = [vp]
     L.lfq_readset_destroy.restype = None
     L.lfq_readset_baq.argtypes = [vp, vp, C.c_int, C.c_int]

@@ -534,19 +534,26 @@ static int bam_stage(LfqBamState *S, const uint8_t **data_io, int64_t data_bytes
 }
 
 /* the leg both calls begin with, inside up_t: d_buf grown to `total`; the records down, behind first_shift bytes of room so that a
- * record keeps the alignment it has in the caller's buffer, through the staging area unless they lie in pinned memory; the call's
+ * record keeps the alignment it has in the caller's buffer, through the staging area unless they lie in pinned memory -- or device
+ * to device when they lie in the context's live lfq_bgzf_inflate result, whose bytes are still resident (lfq_bgzf.hip); the call's
  * per-read descriptors down to o_desc; the 256 bytes of the error words at o_err cleared */
 static int bam_upload(lfq_ctx *c, LfqBamState *S, const LfqBamIn &in, int64_t total, int64_t o_desc, const void *desc,
                       size_t desc_bytes, int64_t o_err)
 {
     LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
     const uint8_t *data = in.data;
-    if (!in.pinned) {
+    /* records inside the context's live lfq_bgzf_inflate result are on the device already: they do not cross the link again */
+    const uint8_t *resident = in.data_bytes > 0 ? lfq_bgzf_resident(c, in.data, in.data_bytes) : nullptr;
+    if (!resident && !in.pinned) {
         LFQ_TRY(bam_stage(S, &data, in.data_bytes));
     }
     hipStream_t st = c->stream;
     LFQ_TRY(S->up_t.begin(st));
-    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + in.first_shift, data, (size_t)in.data_bytes, hipMemcpyHostToDevice, st));
+    if (resident) {
+        LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + in.first_shift, resident, (size_t)in.data_bytes, hipMemcpyDeviceToDevice, st));
+    } else {
+        LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + in.first_shift, data, (size_t)in.data_bytes, hipMemcpyHostToDevice, st));
+    }
     LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_desc, desc, desc_bytes, hipMemcpyHostToDevice, st));
     LFQ_TRY_HIP(hipMemsetAsync(S->d_buf + o_err, 0, 256, st));
     return S->up_t.end(st);

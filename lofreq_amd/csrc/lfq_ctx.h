@@ -7,6 +7,7 @@
  *   lfq_indel_api.hip  the indel tests (lfq_call_indel_tests_batch, lfq_call_indels_batch)
  *   lfq_readset.hip    the resident read set: upload, BAQ / IDAQ, source quality, both pileups
  *   lfq_bamrec.hip     BAM records decoded and rewritten on the device: kernels and their launches (for lfq_readset.hip)
+ *   lfq_bgzf.hip       BGZF blocks inflated on the device (over lfq_inflate.h), the record scan, lfq_readset_create_from_bgzf
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -451,6 +452,7 @@ struct lfq_ctx {
     struct { void *p; size_t cap; int used; } pin_pool[LFQ_PIN_SLOTS];   /* LfqPin: pinned host temporaries */
     struct LfqViterbiState *vit;     /* lfq_viterbi_batch: its result and device buffers (lfq_viterbi.hip; created on first use) */
     struct LfqBamState *bam;         /* lfq_readset_create_from_bam / _encode_bam: records, descriptors, results and timing (lfq_bamrec.hip; created on first use) */
+    struct LfqBgzfState *bgzf;       /* lfq_bgzf_inflate: its buffers, result and timing (lfq_bgzf.hip; created on first use) */
 };
 
 template <typename T>
@@ -494,6 +496,21 @@ static inline void free_pinned(uint8_t **ptr, int64_t *cap)
     if (*ptr) (void)hipHostFree(*ptr);
     *ptr = nullptr;
     *cap = 0;
+}
+
+/* is `p` pinned (or registered) host memory?  The runtime copies from such memory by DMA and hipMemcpyAsync returns at once */
+static inline bool lfq_is_pinned(const void *p)
+{
+    if (!p) {
+        return true;                        /* nothing to copy */
+    }
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();            /* plain malloc'ed memory: an error, by design of that call */
+        return false;
+    }
+    return at.type == hipMemoryTypeHost;
 }
 
 /* Host temporaries a DMA reads or writes come from a grow-only pool of pinned blocks owned by the context (lfq_api.hip) */
@@ -595,6 +612,10 @@ struct LfqBamEncIn {
 };
 int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **out);
 int lfq_bam_encode_empty(lfq_ctx *c, const lfq_bam_encoded **out);
+/* lfq_bgzf.hip.  What lfq_destroy frees of lfq_ctx::bgzf; and for bam_upload (lfq_bamrec.hip): the device address of host bytes
+ * [p, p + bytes) when they lie inside the context's live inflate result (counted as a decode from the device), else null */
+void lfq_bgzf_release(lfq_ctx *c);
+const uint8_t *lfq_bgzf_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);
@@ -606,6 +627,9 @@ int lfq_stage_tracks(lfq_ctx *c, const lfq_tracks *tr, int tracks_on_device, lfq
 int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos, int64_t n_sites, int min_plp_bq,
                            const int64_t *key_off, const char *key_chars, const uint8_t *key_del, lfq_tracks *out,
                            int32_t *cov_out, int32_t *nb_out, int32_t *tails_out, int32_t *ev_out);
+/* lfq_readset_create_from_bam_tags with records that do not abut: record r ends at data_end[r] <= data_off[r + 1] (null: at
+ * data_off[r + 1]).  lfq_readset.hip, for lfq_readset_create_from_bgzf (lfq_bgzf.hip) */
+int lfq_readset_from_bam_ends(lfq_ctx *c, const lfq_bam_records *recs, const int64_t *data_end, unsigned read_tags, lfq_readset **out);
 }
 
 #endif

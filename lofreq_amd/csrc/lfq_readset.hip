@@ -212,21 +212,6 @@ static int readset_upload_wait(lfq_readset *rs, hipStream_t st = nullptr)
     return rs ? rs->up_rc.load() : (int)LFQ_OK;
 }
 
-/* is `p` pinned (or registered) host memory?  The runtime copies from such memory by DMA and hipMemcpyAsync returns at once */
-static bool lfq_is_pinned(const void *p)
-{
-    if (!p) {
-        return true;                        /* nothing to copy */
-    }
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();            /* plain malloc'ed memory: an error, by design of that call */
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-
 /* the host side of an lfq_readset_baq that is still running: merged tag flags (bit 0 BI, 1 BD, 2 ai, 3 ad) into rs->fl */
 static int readset_baq_wait(lfq_readset *rs)
 {
@@ -3228,7 +3213,7 @@ int lfq_readset_viterbi(lfq_ctx *c, lfq_readset *rs, int def_qual, lfq_readset *
 /* What both BAM entries refuse of an lfq_bam_records before a device is touched (include/lofreq_amd.h): n_reads < 0, a null
  * per-read array, and per record decreasing offsets, a negative length or fewer bytes than its fixed part.  Each entry's own:
  * the decode needs `ref`, the encode refuses a record of more than max_record bytes. */
-static int bam_records_check(const lfq_bam_records *recs, bool need_ref, int64_t max_record)
+static int bam_records_check(const lfq_bam_records *recs, bool need_ref, int64_t max_record, const int64_t *data_end = nullptr)
 {
     const int64_t n = recs->n_reads;
     if (n < 0 || (n > 0 && (!recs->data || !recs->data_off || !recs->pos || !recs->flag || !recs->mapq || !recs->l_qname
@@ -3236,8 +3221,8 @@ static int bam_records_check(const lfq_bam_records *recs, bool need_ref, int64_t
         return LFQ_ERR_INVALID;
     }
     for (int64_t r = 0; r < n; r++) {
-        const int64_t o0 = recs->data_off[r], o1 = recs->data_off[r + 1], l = recs->l_qseq[r];
-        if (o1 < o0 || o1 - o0 > max_record || l < 0
+        const int64_t o0 = recs->data_off[r], o1 = data_end ? data_end[r] : recs->data_off[r + 1], l = recs->l_qseq[r];
+        if (o1 < o0 || o1 > recs->data_off[r + 1] || o1 - o0 > max_record || l < 0
             || o1 - o0 < (int64_t)recs->l_qname[r] + 4 * (int64_t)recs->n_cigar[r] + (l + 1) / 2 + l) {
             return LFQ_ERR_INVALID;
         }
@@ -3263,13 +3248,13 @@ static LfqBamIn bam_records_in(const lfq_bam_records *recs)
  * from them, with the per-base work -- nibbles -> base codes, qualities, the BI / BD strings found among the aux fields -- done
  * by the two launches of lfq_bamrec.hip.  The host reads per READ only: descriptor checks, prefix sums, the CIGAR words.  *out
  * owns its host arrays (LfqReadsetOwned); the per-base ones come back from the device into pinned memory.  Blocks. */
-static int readset_from_bam(lfq_ctx *c, const lfq_bam_records *recs, unsigned read_tags, lfq_readset **out)
+int lfq_readset_from_bam_ends(lfq_ctx *c, const lfq_bam_records *recs, const int64_t *data_end, unsigned read_tags, lfq_readset **out)
 {
     if (out) *out = nullptr;
     if (!c || !recs || !out || (read_tags & ~(unsigned)(LFQ_BAM_READ_LB | LFQ_BAM_READ_IDAQ))) {
         return LFQ_ERR_INVALID;
     }
-    LFQ_TRY(bam_records_check(recs, true, INT64_MAX));
+    LFQ_TRY(bam_records_check(recs, true, INT64_MAX, data_end));
     const int64_t n = recs->n_reads;
     std::unique_ptr<LfqReadsetOwned> own(new LfqReadsetOwned());
     own->cigar_off.resize((size_t)n + 1);
@@ -3315,7 +3300,7 @@ static int readset_from_bam(lfq_ctx *c, const lfq_bam_records *recs, unsigned re
                 memcpy(o->cigar.data() + o->cigar_off[(size_t)r], in.data + at, (size_t)nc * 4);
             }
             seq_src[r] = in.first_shift + at + 4 * nc;
-            rec_end[r] = in.first_shift + recs->data_off[r + 1] - first;
+            rec_end[r] = in.first_shift + (data_end ? data_end[r] : recs->data_off[r + 1]) - first;
         }
     });
     int any_bi = 0, any_bd = 0;
@@ -3383,12 +3368,12 @@ static int readset_from_bam(lfq_ctx *c, const lfq_bam_records *recs, unsigned re
 
 int lfq_readset_create_from_bam(lfq_ctx *c, const lfq_bam_records *recs, lfq_readset **out)
 {
-    return readset_from_bam(c, recs, 0, out);
+    return lfq_readset_from_bam_ends(c, recs, nullptr, 0, out);
 }
 
 int lfq_readset_create_from_bam_tags(lfq_ctx *c, const lfq_bam_records *recs, unsigned read_tags, lfq_readset **out)
 {
-    return readset_from_bam(c, recs, read_tags, out);
+    return lfq_readset_from_bam_ends(c, recs, nullptr, read_tags, out);
 }
 
 int lfq_readset_fetch_stored_tags(lfq_ctx *c, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out,

@@ -341,6 +341,81 @@ def last_bam_encode_times(caller):
     return {k: getattr(t, k) for k, _ in _lib.BamEncodeTimes._fields_}
 
 
+class BgzfError(RuntimeError):
+    """lfq_bgzf_inflate found a block it cannot inflate: .status (int32 per block, nonzero = what is wrong, include/lofreq_amd.h),
+    .data / .data_off as bgzf_inflate returns them (the bytes of the blocks with status 0 are intact)"""
+
+    def __init__(self, msg, data, data_off, status):
+        RuntimeError.__init__(self, msg)
+        self.data, self.data_off, self.status = data, data_off, status
+
+
+def _as_u8(buf):
+    return np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf, np.uint8)
+
+
+def bgzf_inflate(caller, comp):
+    """lfq_bgzf_inflate: the BGZF blocks `comp` (bytes or uint8 array, as they lie in the file) inflated and CRC-checked on the
+    device -> (data: uint8 array, data_off: int64 [n_blocks + 1], status: int32 [n_blocks]), copies.  Raises RuntimeError for
+    framing the host refuses, BgzfError (with the three arrays) when a block's status is nonzero."""
+    a = _as_u8(comp)
+    out = C.POINTER(_lib.BgzfResult)()
+    rc = _lib.load().lfq_bgzf_inflate(caller.h, a.ctypes.data if len(a) else None, len(a), C.byref(out))
+    if not out:
+        _lib.check(rc, "lfq_bgzf_inflate")
+    r = out.contents
+    nb = int(r.n_blocks)
+    data_off = np.ctypeslib.as_array(C.cast(r.data_off, C.POINTER(C.c_int64)), (nb + 1,)).copy()
+    status = np.ctypeslib.as_array(C.cast(r.status, C.POINTER(C.c_int32)), (nb,)).copy() if nb else np.zeros(0, np.int32)
+    data = np.ctypeslib.as_array(C.cast(r.data, C.POINTER(C.c_uint8)), (int(r.n_bytes),)).copy() if r.n_bytes else np.zeros(0, np.uint8)
+    if rc != _lib.LFQ_OK:
+        raise BgzfError("lfq_bgzf_inflate failed: %s (%d); status of the blocks: %s"
+                        % (_lib.load().lfq_strerror(rc).decode(), rc, status.tolist()), data, data_off, status)
+    return data, data_off, status
+
+
+def last_bgzf_times(caller):
+    """lfq_last_bgzf_times -> dict(upload_ms, kernels_ms, download_ms, n_blocks, n_in_bytes, n_out_bytes, n_launches,
+    n_decodes_from_device)"""
+    t = _lib.BgzfTimes()
+    _lib.check(_lib.load().lfq_last_bgzf_times(caller.h, C.byref(t)), "lfq_last_bgzf_times")
+    return {k: getattr(t, k) for k, _ in _lib.BgzfTimes._fields_}
+
+
+def _scan_opts(tid=-1, beg=0, end=None, min_mq=0, max_mq=255, no_orphan=False, flag_mask=None):
+    o = _lib.BamScanOpts()
+    _lib.load().lfq_bam_scan_opts_init(C.byref(o))
+    o.tid, o.beg, o.min_mq, o.max_mq, o.no_orphan = int(tid), int(beg), int(min_mq), int(max_mq), 1 if no_orphan else 0
+    if end is not None:
+        o.end = int(end)
+    if flag_mask is not None:
+        o.flag_mask = int(flag_mask)
+    return o
+
+
+def bam_scan_records(bam, first=0, stop=None, **opts):
+    """lfq_bam_scan_records (host only): the records of inflated BAM bytes bam[first:stop], filtered as sam_itr_next + mplp_func
+    keep them.  opts: tid (-1 = any), beg, end, min_mq, max_mq, no_orphan, flag_mask (default 4 | 256 | 512 | 1024).
+    -> dict: data_off [n + 1], data_end, pos, flag, mapq, l_qname, n_cigar, l_qseq [n] of the kept records (record r is
+    bam[data_off[r]:data_end[r]]), n_seen, n_consumed"""
+    L = _lib.load()
+    a = _as_u8(bam)
+    o = _scan_opts(**opts)
+    out = C.POINTER(_lib.BamScan)()
+    _lib.check(L.lfq_bam_scan_records(a.ctypes.data if len(a) else None, int(first), len(a) if stop is None else int(stop),
+                                      C.byref(o), C.byref(out)), "lfq_bam_scan_records")
+    try:
+        s = out.contents
+        n = int(s.recs.n_reads)
+        get = lambda p, ct, k: np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (k,)).copy() if k else np.zeros(0, ct)
+        return {"data_off": get(s.recs.data_off, C.c_int64, n + 1), "data_end": get(s.data_end, C.c_int64, n),
+                "pos": get(s.recs.pos, C.c_int32, n), "flag": get(s.recs.flag, C.c_uint16, n), "mapq": get(s.recs.mapq, C.c_uint8, n),
+                "l_qname": get(s.recs.l_qname, C.c_uint16, n), "n_cigar": get(s.recs.n_cigar, C.c_uint32, n),
+                "l_qseq": get(s.recs.l_qseq, C.c_int32, n), "n_seen": int(s.n_seen), "n_consumed": int(s.n_consumed)}
+    finally:
+        L.lfq_bam_scan_free(out)
+
+
 def _format_grown(call, what):
     """a formatter whose text grows with the depth: ask for the length, then write"""
     n = call(None, 0)
@@ -493,6 +568,36 @@ class ReadSet:
                        "lfq_readset_create_from_bam_tags")
         else:
             _lib.check(self.L.lfq_readset_create_from_bam(caller.h, C.byref(rc), C.byref(h)), "lfq_readset_create_from_bam")
+        self.h = h
+        if not hasattr(caller, "_readsets"):
+            import weakref
+            caller._readsets = weakref.WeakSet()
+        caller._readsets.add(self)
+        return self
+
+    @classmethod
+    def from_bgzf(cls, caller, comp, first, ref, stop=-1, read_tags=0, **opts):
+        """lfq_readset_create_from_bgzf: the read set of the BAM records in the BGZF blocks `comp` (bytes or uint8 array) --
+        inflated on the device, scanned from byte `first` of the inflated data to `stop` (negative: its end) under `opts`
+        (bam_scan_records), decoded from the device copy.  .n_consumed: the scan's; .kept: the dict bam_scan_records returns.
+        (To know the kept reads on this side the binding inflates and scans once more in front of the call.)"""
+        self = cls.__new__(cls)
+        self.caller = caller
+        self.L = _lib.load()
+        a = _as_u8(comp)
+        data, _, _ = bgzf_inflate(caller, a)
+        self.kept = bam_scan_records(data, int(first), None if stop < 0 else int(stop), **opts)
+        self.n = len(self.kept["pos"])
+        self.seq_off = np.concatenate([[0], np.cumsum(self.kept["l_qseq"], dtype=np.int64)]).astype(np.int64)
+        self._keep = {"ref": bytes(ref)}
+        o = _scan_opts(**opts)
+        h = C.c_void_p()
+        consumed = C.c_int64(0)
+        _lib.check(self.L.lfq_readset_create_from_bgzf(caller.h, a.ctypes.data if len(a) else None, len(a), int(first), int(stop),
+                                                       C.byref(o), C.cast(C.c_char_p(self._keep["ref"]), C.c_void_p),
+                                                       len(self._keep["ref"]), int(read_tags), C.byref(h), C.byref(consumed)),
+                   "lfq_readset_create_from_bgzf")
+        self.n_consumed = int(consumed.value)
         self.h = h
         if not hasattr(caller, "_readsets"):
             import weakref

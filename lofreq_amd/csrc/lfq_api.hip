@@ -691,11 +691,11 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
     }
     LFQ_TRY(grow(&c->d_scratch, &c->scratch_doubles, per_block * n_big_blocks));
     if (!c->d_longs) {
-        /* row-split bookkeeping: 64 Ki column records, 8 Mi segment cells (128 MiB); a column that does not
-         * get its cells simply runs unsplit */
+        /* row-split bookkeeping: 64 Ki column records with the item table of the segment kernels behind them (lfq_seg_items.h,
+         * 2 MiB), 8 Mi segment cells (128 MiB); a column that does not get its cells simply runs unsplit */
         c->long_cap = 1 << 16;
         c->pool_cells = kn.split_pool_cells;                    /* 0 disables row splitting */
-        LFQ_TRY_HIP(hipMalloc((void **)&c->d_longs, (size_t)c->long_cap * sizeof(LfqLong)));
+        LFQ_TRY_HIP(hipMalloc((void **)&c->d_longs, (size_t)c->long_cap * (sizeof(LfqLong) + LFQ_SEG_MAX * sizeof(int32_t))));
         LFQ_TRY_HIP(hipMalloc((void **)&c->d_pool, (size_t)std::max(c->pool_cells, 1) * sizeof(LfqSegCell)));
         LFQ_TRY_HIP(hipEventCreateWithFlags(&c->ev_segw, hipEventDisableTiming));
         LFQ_TRY_HIP(hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
@@ -779,6 +779,14 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         const int light_waves_per_cu = kn.light_kernel == 0 ? screen_auto : 10;
         const int n_light_waves = (int)std::min<int64_t>((int64_t)c->n_cu * light_waves_per_cu, std::max<int64_t>(seg_cols / 8, 4));
         const int n_mid_waves = (int)std::min<int64_t>((int64_t)c->n_cu * 4, std::max<int64_t>(seg_cols, 4));
+        /* Wavefronts per workgroup of the latency-bound long-column kernels (mid kernel, row segments): 4.  Beside the next
+         * batch's count kernel -- 1024-thread workgroups, two per CU, all eight wave slots of every SIMD -- a CU that holds ONE
+         * live DP wavefront runs one count workgroup instead of two, so fewer, fuller DP workgroups were tried for the context
+         * that queues without a gate: listing the row segments densely (lfq_seg_items.h: 126 workgroups of 4 instead of 251
+         * half-empty ones) gave C3 2.67 -> 2.59 ms per step; 8 wavefronts per workgroup on top of that gave nothing, 16 lost
+         * 0.5 ms (112-127 VGPRs: such a workgroup fits no CU that runs a count workgroup).  LFQ_DP_WG_WAVES (tuning build)
+         * still selects 8 or 16 there, for the A/B and the tests; profiles/NOTES.md, 2026-10-20. */
+        const int dp_wg = (c->batch_gate == LFQ_GATE_NONE && !indel_mode && kn.dp_wg_waves > 0) ? kn.dp_wg_waves : 4;
         const bool run_big = !kn.skip_big, run_mid = !kn.skip_mid;     /* profiling aid: run the DP classes in isolation */
         const bool dbg_sync = kn.debug_sync != 0;                      /* debugging aid: serialize and name the stages */
 #define LFQ_DBG_STAGE(name)                                                        \
@@ -805,7 +813,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         }
         LFQ_TRY_HIP(hipEventRecord(c->ev_prep, side0));
         if (run_mid) {
-            LFQ_TRY(lfq_launch_dp_mid(T, P, c->d_luts, d_counts, W, d_pvals, pvals_capacity, n_mid_waves, side1));
+            LFQ_TRY(lfq_launch_dp_mid(T, P, c->d_luts, d_counts, W, d_pvals, pvals_capacity, n_mid_waves, dp_wg, side1));
             LFQ_DBG_STAGE("mid");
         }
         /* The unsplit big columns (lfq_dp_big_kernel: what the prep kernel queued because it is too short or too wide to cut
@@ -823,7 +831,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
             big_joined = true;
         }
         if (run_big) {
-            LFQ_TRY(lfq_launch_dp_seg(1, T, P, c->d_luts, W, c->n_cu * 8, side0));
+            LFQ_TRY(lfq_launch_dp_seg(1, T, P, c->d_luts, W, c->n_cu * 8, dp_wg, side0));
             LFQ_DBG_STAGE("seg big");
             LFQ_TRY(tail_record(c, 0, side0));
             LFQ_TRY(lfq_launch_dp_combine(1, P, d_counts, W, d_pvals, pvals_capacity, c->n_cu, side0));
@@ -839,7 +847,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         }
         LFQ_TRY_HIP(hipStreamWaitEvent(side1, c->ev_prep, 0));     /* K = 250..252 of the big class lands in class 1 */
         if (run_mid || run_big) {
-            LFQ_TRY(lfq_launch_dp_seg(0, T, P, c->d_luts, W, c->n_cu * 8, side1));
+            LFQ_TRY(lfq_launch_dp_seg(0, T, P, c->d_luts, W, c->n_cu * 8, dp_wg, side1));
             LFQ_DBG_STAGE("seg mid");
             LFQ_TRY(tail_record(c, 1, side1));
             LFQ_TRY(lfq_launch_dp_combine(0, P, d_counts, W, d_pvals, pvals_capacity, c->n_cu, side1));

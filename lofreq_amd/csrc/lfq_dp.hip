@@ -519,8 +519,14 @@ __device__ __forceinline__ int lfq_seg_class(int K)
     return K <= 63 ? 0 : (K <= 252 ? 1 : (K <= 504 ? 2 : (K <= 1008 ? 3 : 4)));
 }
 
-/* reserve pool cells and a record slot for a column that is about to be split; nullptr = run it unsplit.
- * Called by one lane. */
+/* the item table of the row-segment kernels (lfq_seg_items.h) lives behind the records */
+__device__ __forceinline__ int32_t *lfq_seg_items_of(const LfqWork &W)
+{
+    return reinterpret_cast<int32_t *>(W.longs + W.long_cap);
+}
+
+/* reserve pool cells and a record slot for a column that is about to be split, and list its n_seg segments as items of
+ * the segment kernel; nullptr = run it unsplit.  Called by one lane. */
 __device__ __forceinline__ LfqLong *lfq_long_reserve(const LfqWork &W, int K, int n_seg, int64_t *cell0)
 {
     const int cells = 2 * n_seg * (K + 1);          /* the segments + the intermediate results of the fold tree */
@@ -534,6 +540,8 @@ __device__ __forceinline__ LfqLong *lfq_long_reserve(const LfqWork &W, int K, in
     if (slot >= per_class) {
         return nullptr;
     }
+    const int item0 = atomicAdd(&W.counters[LFQ_CNT_SEG_ITEMS + lfq_seg_mode_of(cls)], n_seg);
+    lfq_seg_items_put(lfq_seg_items_of(W), per_class, item0, cls, slot, 0, n_seg, 0, 1);
     *cell0 = c0;
     return W.longs + cls * per_class + slot;
 }
@@ -916,6 +924,9 @@ __device__ __forceinline__ void lfq_wave_column(const LfqColCtx &cx, LfqRaw raw,
                 if (c0 + cells <= W.pool_cells) {
                     const int slot = lfq_claim(&W.counters[LFQ_CNT_LONG0 + cls], 1);
                     if (slot < per_class) {
+                        /* the new segments 1 .. n_seg - 1 become items of lfq_dp_seg_kernel<0> (lfq_seg_items.h) */
+                        const int item0 = lfq_claim(&W.counters[LFQ_CNT_SEG_ITEMS + lfq_seg_mode_of(cls)], n_new);
+                        lfq_seg_items_put(lfq_seg_items_of(W), per_class, item0, cls, slot, 1, n_seg, lane, 64);
                         lfq_strip_store_cells<C>(S, lane, shift, K, W.pool + c0);
                         if (lane == 0) {
                             LfqLong r;
@@ -973,16 +984,23 @@ __device__ __forceinline__ void lfq_wave_column(const LfqColCtx &cx, LfqRaw raw,
     }
 }
 
-template <int MAXC>
-__global__ __launch_bounds__(256) void lfq_dp_wave_kernel(LfqTracksDev T, LfqParams P,
-                                                          const LfqLuts *__restrict__ g_luts,
-                                                          const lfq_col_counts *__restrict__ counts, LfqWork W,
-                                                          int base_idx, int count_idx,
-                                                          lfq_col_pvals *__restrict__ pvals,
-                                                          int64_t pvals_capacity, int batch, int only_if_gl64)
+/* WG = wavefronts per workgroup: 4 in every release launch.  With 8 or 16 (LFQ_DP_WG_WAVES, tuning build, mid class of a
+ * context that queues its batches without a gate) the same wavefronts come as few large workgroups and the FIRST claim is one
+ * atomic per workgroup for WG * batch columns -- wavefront w takes base + w * batch -- so that the columns of a short list land in
+ * the first workgroups to start instead of one or two on every CU; later claims are per wavefront, as with 4.  Measured
+ * beside the count kernel, neither gains (profiles/NOTES.md, 2026-10-20): this kernel holds 112 VGPRs, a workgroup of 16
+ * needs a SIMD's whole register file four times over and waits for a CU without any count workgroup. */
+template <int MAXC, int WG = 4>
+__global__ __launch_bounds__(WG * 64) void lfq_dp_wave_kernel(LfqTracksDev T, LfqParams P,
+                                                              const LfqLuts *__restrict__ g_luts,
+                                                              const lfq_col_counts *__restrict__ counts, LfqWork W,
+                                                              int base_idx, int count_idx,
+                                                              lfq_col_pvals *__restrict__ pvals,
+                                                              int64_t pvals_capacity, int batch, int only_if_gl64)
 {
     __shared__ LfqLuts s_luts;
-    __shared__ LfqRow s_rows[4][64];
+    __shared__ LfqRow s_rows[WG][64];
+    __shared__ int s_first;
     (void)only_if_gl64;
     if (MAXC > 1) {
         /* few, long, latency-bound columns sharing SIMDs with the throughput-bound light kernel:
@@ -1003,8 +1021,19 @@ __global__ __launch_bounds__(256) void lfq_dp_wave_kernel(LfqTracksDev T, LfqPar
      * the record of column i+2 are in flight. */
     const int BATCH = batch;            /* run-time on purpose, see lfq_claim */
     int32_t *head = &W.counters[(MAXC == 1) ? LFQ_CNT_HEAD_LIGHT : LFQ_CNT_HEAD_MID];
-    for (;;) {
-        int b0 = lfq_claim(head, BATCH);
+    int b_first = 0;
+    if (WG > 4) {
+        if (wave == 0) {
+            const int b = lfq_claim(head, WG * BATCH);
+            if (lfq_lane() == 0) {
+                s_first = b;
+            }
+        }
+        __syncthreads();
+        b_first = __builtin_amdgcn_readfirstlane(s_first) + wave * BATCH;
+    }
+    for (bool first = true;; first = false) {
+        int b0 = (WG > 4 && first) ? b_first : lfq_claim(head, BATCH);
         if (b0 >= n_work) {
             break;
         }
@@ -1778,42 +1807,35 @@ __device__ __forceinline__ void lfq_wave_segment(const LfqColCtx &cx, int64_t ch
 }
 
 /* MODE 0: the classes fed by the mid kernel (1 and 4 cells per lane); MODE 1: the classes fed by the big
- * prep kernel (8, 16, 32).  Items = (record, segment) pairs, class-major, static stride over the
- * wavefronts: the loop is free of atomics. */
-template <int MODE>
-__global__ __launch_bounds__(256) void lfq_dp_seg_kernel(LfqTracksDev T, LfqParams P,
-                                                         const LfqLuts *__restrict__ g_luts, LfqWork W)
+ * prep kernel (8, 16, 32).  Items = the (record, segment) pairs the mode's producers listed (lfq_seg_items.h): item i
+ * on wavefront i, static stride over the wavefronts -- the loop is free of atomics, and the live wavefronts are the
+ * first ones of the launch: C3's 502 segments of a gate-less context are 126 workgroups, where the stride of LFQ_SEG_MAX
+ * items per record spread them over 251.  A workgroup beyond the last item exits before it touches LDS.  WG = wavefronts per
+ * workgroup (lfq_launch_dp_seg): 4 in every release launch, 8 / 16 under LFQ_DP_WG_WAVES (see lfq_dp_wave_kernel). */
+template <int MODE, int WG>
+__global__ __launch_bounds__(WG * 64) void lfq_dp_seg_kernel(LfqTracksDev T, LfqParams P,
+                                                             const LfqLuts *__restrict__ g_luts, LfqWork W)
 {
     __shared__ LfqLuts s_luts;
-    __shared__ LfqRow s_rows[4][64];
+    __shared__ LfqRow s_rows[WG][64];
+    constexpr int C_LO = MODE ? LFQ_SEG_MODE0_CLASSES : 0;
+    const int per_class = W.long_cap / LFQ_SEG_CLASSES;
+    const int total = W.counters[LFQ_CNT_SEG_ITEMS + MODE];
+    if ((int)blockIdx.x * WG >= total) {
+        return;
+    }
     __builtin_amdgcn_s_setprio(3);
     lfq_luts_to_lds(&s_luts, g_luts);
     __syncthreads();
-    constexpr int C_LO = MODE ? 2 : 0, C_N = MODE ? 3 : 2;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int per_class = W.long_cap / LFQ_SEG_CLASSES;
-    int n_items[C_N], total = 0;
-#pragma unroll
-    for (int c = 0; c < C_N; c++) {
-        n_items[c] = min(W.counters[LFQ_CNT_LONG0 + C_LO + c], per_class) * LFQ_SEG_MAX;
-        total += n_items[c];
-    }
+    const int32_t *items = lfq_seg_items_of(W) + lfq_seg_items_base(MODE, per_class);
     LfqRow *rows = s_rows[wave];
-    const int n_waves_total = (int)gridDim.x * 4;
-    for (int idx = (int)blockIdx.x * 4 + wave; idx < total; idx += n_waves_total) {
-        int c = 0, i = idx;
-#pragma unroll
-        for (int k = 0; k < C_N - 1; k++) {
-            if (c == k && i >= n_items[k]) {
-                i -= n_items[k];
-                c = k + 1;
-            }
-        }
-        const int r = i % LFQ_SEG_MAX;
-        const LfqLong R = W.longs[(C_LO + c) * per_class + i / LFQ_SEG_MAX];
-        if (r < R.phase1 || r >= R.n_seg) {
-            continue;
-        }
+    const int n_waves_total = (int)gridDim.x * WG;
+    for (int idx = (int)blockIdx.x * WG + wave; idx < total; idx += n_waves_total) {
+        int cls, slot, r, rec;
+        lfq_seg_item_unpack(__builtin_amdgcn_readfirstlane(items[idx]), per_class, &cls, &slot, &r, &rec);
+        const int c = cls - C_LO;
+        const LfqLong R = W.longs[rec];
         LfqColCtx cx;
         lfq_ctx_from_long(cx, R, P);
         int64_t c0, c1;
@@ -2880,14 +2902,26 @@ int lfq_launch_dp_light(const LfqTracksDev &t, const LfqParams &p, const LfqLuts
 
 int lfq_launch_dp_mid(const LfqTracksDev &t, const LfqParams &p, const LfqLuts *d_luts,
                       const lfq_col_counts *d_counts, const LfqWork &w, lfq_col_pvals *d_pvals,
-                      int64_t pvals_capacity, int n_waves, void *stream)
+                      int64_t pvals_capacity, int n_waves, int wg_waves, void *stream)
 {
     if (t.ncols <= 0 || n_waves <= 0) {
         return LFQ_OK;
     }
-    const unsigned blocks = (unsigned)((n_waves + 3) / 4);
-    hipLaunchKernelGGL(lfq_dp_wave_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, p,
-                       d_luts, d_counts, w, LFQ_CNT_LIGHT, LFQ_CNT_MID, d_pvals, pvals_capacity, 1, 0);
+    if (wg_waves != 4 && wg_waves != 8 && wg_waves != 16) {
+        return LFQ_ERR_INVALID;
+    }
+    const dim3 grid((unsigned)((n_waves + wg_waves - 1) / wg_waves)), block(64u * wg_waves);
+#define LFQ_LAUNCH_MID(WG)                                                                                          \
+    hipLaunchKernelGGL((lfq_dp_wave_kernel<4, WG>), grid, block, 0, (hipStream_t)stream, t, p, d_luts, d_counts, w, \
+                       LFQ_CNT_LIGHT, LFQ_CNT_MID, d_pvals, pvals_capacity, 1, 0)
+    if (wg_waves == 4) {
+        LFQ_LAUNCH_MID(4);
+    } else if (wg_waves == 8) {
+        LFQ_LAUNCH_MID(8);
+    } else {
+        LFQ_LAUNCH_MID(16);
+    }
+#undef LFQ_LAUNCH_MID
     return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
 }
 
@@ -2919,17 +2953,31 @@ int lfq_launch_dp_big_prep(const LfqTracksDev &t, const LfqParams &p, const LfqL
 }
 
 int lfq_launch_dp_seg(int mode, const LfqTracksDev &t, const LfqParams &p, const LfqLuts *d_luts,
-                      const LfqWork &w, int n_waves, void *stream)
+                      const LfqWork &w, int n_waves, int wg_waves, void *stream)
 {
     if (t.ncols <= 0 || n_waves <= 0) {
         return LFQ_OK;
     }
-    const dim3 grid((unsigned)((n_waves + 3) / 4)), block(256);
-    if (mode == 0) {
-        hipLaunchKernelGGL(lfq_dp_seg_kernel<0>, grid, block, 0, (hipStream_t)stream, t, p, d_luts, w);
-    } else {
-        hipLaunchKernelGGL(lfq_dp_seg_kernel<1>, grid, block, 0, (hipStream_t)stream, t, p, d_luts, w);
+    if (wg_waves != 4 && wg_waves != 8 && wg_waves != 16) {
+        return LFQ_ERR_INVALID;
     }
+    const dim3 grid((unsigned)((n_waves + wg_waves - 1) / wg_waves)), block(64u * wg_waves);
+#define LFQ_LAUNCH_SEG(WG)                                                                                          \
+    do {                                                                                                            \
+        if (mode == 0) {                                                                                            \
+            hipLaunchKernelGGL((lfq_dp_seg_kernel<0, WG>), grid, block, 0, (hipStream_t)stream, t, p, d_luts, w);   \
+        } else {                                                                                                    \
+            hipLaunchKernelGGL((lfq_dp_seg_kernel<1, WG>), grid, block, 0, (hipStream_t)stream, t, p, d_luts, w);   \
+        }                                                                                                           \
+    } while (0)
+    if (wg_waves == 4) {
+        LFQ_LAUNCH_SEG(4);
+    } else if (wg_waves == 8) {
+        LFQ_LAUNCH_SEG(8);
+    } else {
+        LFQ_LAUNCH_SEG(16);
+    }
+#undef LFQ_LAUNCH_SEG
     return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
 }
 

@@ -116,6 +116,7 @@ struct LfqLong {              /* 128 bytes */
 };
 
 #define LFQ_SEG_MAX 8
+#include "lfq_seg_items.h"      /* the (class, record, segment) items of the row-segment kernels and their table */
 /* a row segment always runs on ONE wavefront, with as many cells per lane as its K needs: the classes are
  * K <= 63 (1 cell per lane), <= 252 (4), <= 504 (8), <= 1008 (16), <= 2016 (32) -- (K + C) / C <= 64 lanes
  * incl. alignment.  More cells per lane = fewer instructions
@@ -147,7 +148,8 @@ struct LfqWork {
     int32_t *gcounters;       /* batch-wide counters shared by all segments, see LFQ_GC_* */
     int32_t *counters;        /* [16] of this segment, see LFQ_CNT_* */
     int32_t *block_sums;      /* scan scratch */
-    LfqLong *longs;           /* [long_cap]: LFQ_SEG_CLASSES lists of long_cap / LFQ_SEG_CLASSES records each */
+    LfqLong *longs;           /* [long_cap]: LFQ_SEG_CLASSES lists of long_cap / LFQ_SEG_CLASSES records each; behind them the item
+                               * table of the row-segment kernels, long_cap * LFQ_SEG_MAX int32 (lfq_seg_items.h) */
     int32_t *unsplit;         /* big-list indices of the big columns that run unsplit (lfq_dp_big_kernel) */
     LfqSegCell *pool;         /* [pool_cells] segment distributions, bump-allocated (LFQ_CNT_POOL) */
     int32_t long_cap;
@@ -187,6 +189,7 @@ struct LfqWork {
 #define LFQ_CNT_KHIST 40            /* .. 46: light columns with K <= lfq_khist_thr(f): the screen kernel's register variants */
 #define LFQ_NKHIST 7
 #define LFQ_CNT_LONG0 16       /* +class: row-split columns per cells-per-lane class (LFQ_SEG_CLASSES) */
+#define LFQ_CNT_SEG_ITEMS 22   /* and 23: listed row segments per mode of lfq_dp_seg_kernel (lfq_seg_items.h) */
 
 /* ---- environment knobs ---------------------------------------------------------------------------
  * Environment variables, read ONCE per process (first lfq_create / first use) into this struct; no entry point
@@ -237,6 +240,8 @@ struct LfqKnobs {
     long baq_scratch_mb;       /* LFQ_BAQ_SCRATCH_MB: -1 = from free HBM */
     int private_stream;        /* LFQ_PRIVATE_STREAM (0): lfq_create gives every context a launch stream of its own (lfq_set_private_stream) */
     int bound_gate;            /* LFQ_BOUND_GATE (1): 0 = every light column runs the screen's DP (A/B of the bound gate, lfq_bound.h) */
+    int dp_wg_waves;           /* LFQ_DP_WG_WAVES (0 = 4): 4 / 8 / 16 wavefronts per workgroup of the mid kernel and the row-segment kernels of
+                                * a context that queues its batches without a gate (lfq_batch_device_impl) */
 };
 const LfqKnobs &lfq_knobs(void);
 /* CPUs this process may actually use: the affinity mask and the cgroup's cpu.max quota, not the machine's core count
@@ -498,7 +503,7 @@ int lfq_launch_dp_quad(const LfqTracksDev &t, const LfqParams &p, const LfqLuts 
 /* (phase: 0 = screen + retry, 1 = the screen kernel only, 2 = the retry kernel only) */
 int lfq_launch_dp_mid(const LfqTracksDev &t, const LfqParams &p, const LfqLuts *d_luts,
                       const lfq_col_counts *d_counts, const LfqWork &w, lfq_col_pvals *d_pvals,
-                      int64_t pvals_capacity, int n_waves, void *stream);
+                      int64_t pvals_capacity, int n_waves, int wg_waves, void *stream);
 int lfq_launch_dp_big(const LfqTracksDev &t, const LfqParams &p, const LfqLuts *d_luts,
                       const lfq_col_counts *d_counts, const LfqWork &w, lfq_col_pvals *d_pvals,
                       int64_t pvals_capacity, double *d_scratch, int64_t scratch_doubles_per_block,
@@ -507,7 +512,9 @@ int lfq_launch_dp_big_prep(const LfqTracksDev &t, const LfqParams &p, const LfqL
                            const lfq_col_counts *d_counts, const LfqWork &w, lfq_col_pvals *d_pvals,
                            int64_t pvals_capacity, int n_blocks, void *stream);
 int lfq_launch_dp_seg(int mode, const LfqTracksDev &t, const LfqParams &p, const LfqLuts *d_luts,
-                      const LfqWork &w, int n_waves, void *stream);
+                      const LfqWork &w, int n_waves, int wg_waves, void *stream);
+/* (wg_waves: wavefronts per workgroup, 4 / 8 / 16.  4 is what every release launch uses; 8 and 16 pack the same wavefronts
+ * into few workgroups and are selected by LFQ_DP_WG_WAVES only: see lfq_batch_device_impl) */
 int lfq_launch_dp_combine(int mode, const LfqParams &p, const lfq_col_counts *d_counts, const LfqWork &w,
                           lfq_col_pvals *d_pvals, int64_t pvals_capacity, int n_blocks, void *stream);
 int lfq_launch_synth(const struct lfq_synth_spec *d_spec_host, int64_t col_begin, int64_t ncols,

@@ -49,6 +49,7 @@ extern "C" {
 /* (10 still: lfq_readset_create_from_bam_tags, lfq_readset_fetch_stored_tags, lfq_readset_baq_fill, lfq_last_baq_fill_stats likewise.) */
 /* (10 still: lfq_readset_encode_bam, lfq_last_bam_encode_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_bgzf_inflate, lfq_last_bgzf_times, lfq_bam_scan_records and its helpers, lfq_readset_create_from_bgzf likewise.) */
+/* (10 still: lfq_bgzf_deflate, lfq_last_bgzf_deflate_times, lfq_bam_frame_encoded are new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -699,9 +700,9 @@ int lfq_last_baq_fill_stats(lfq_ctx *ctx, lfq_baq_fill_stats *s);
  *                           empty ones included (lofreq_indelqual.c:69-104), in Dindel mode for records with !(flag & 0x704)
  *                           only, the others pass through (:143-148).
  * With several bits set the result is that of the reference commands run one after the other (their tag sets are disjoint).
- * What the caller still does when it writes the records out: the core fields in front of each record -- block_size, refID, pos
- * and n_cigar from the result, mate fields --, core.bin, which depends on the new pos and CIGAR and is the caller's to recompute,
- * and BGZF.
+ * What is still missing for a file: the core fields in front of each record -- block_size, refID, pos and n_cigar from the
+ * result, mate fields -- and core.bin, which depends on the new pos and CIGAR: lfq_bam_frame_encoded below puts them there; and
+ * BGZF: lfq_bgzf_deflate.
  * *out is the context's: valid until its next encode or lfq_destroy.  The call blocks until the blob is complete.
  * LFQ_ERR_INVALID, before a device is touched: a NULL ctx, rs, recs or out; what == 0, an unknown bit, KEEP_EXISTING without
  * PUT_LB / PUT_IDAQ; the descriptor cases of the decode (ref aside) and a record of 2^31 bytes or more; a read set of another
@@ -835,6 +836,72 @@ int lfq_readset_create_from_bam_scan(lfq_ctx *ctx, const lfq_bam_scan *scan, uns
 int lfq_readset_create_from_bgzf(lfq_ctx *ctx, const uint8_t *comp, int64_t n_bytes, int64_t first, int64_t stop_or_neg,
                                  const lfq_bam_scan_opts *o, const char *ref, int64_t ref_len, unsigned read_tags,
                                  lfq_readset **out, int64_t *n_consumed_or_null);
+
+/* --- the last two steps of writing a BAM: the records framed, the bytes cut into BGZF blocks and compressed -----------------------
+ * lfq_bam_frame_encoded makes the BODY OF A BAM FILE from the context's last lfq_readset_encode_bam result, which is still on the
+ * device.  cores: 32 bytes per ORIGINAL record, as they lie in the file behind block_size (refID, pos, l_read_name, mapq, bin,
+ * n_cigar_op, flag, l_seq, next_refID, next_pos, tlen), indexed through the result's `src`.  Record j of the output is
+ *     block_size (int32 = 32 + the record's length) | core' | the record's bytes
+ * where core' is cores[src[j]] with three fields replaced: pos and n_cigar_op from the encode result, and bin; everything else --
+ * refID, mapq, flag, l_read_name, l_seq, the mate fields -- is copied.  bin is the SAM specification's reg2bin of [pos, end)
+ * (section 5.3), end = pos + the reference bases (M D N = X) of the CIGAR words in the output record; the alignment counts as
+ * length 1 when that is 0 or the read is unmapped (flag 4), as section 4.2 says, so pos = -1 gives 4680.  The reference never
+ * sets core.bin after replace_cigar: the bin here is the specification's, not necessarily the 2.1.4 binary's.
+ * Two launches: one lane per read computes end and bin, a gather pass writes the body.  The body comes back into pinned memory AND
+ * STAYS ON THE DEVICE, so that lfq_bgzf_deflate given framed->data (or a part of it) takes it from there.
+ * LFQ_ERR_INVALID: a NULL argument; no live encode result on the context; n_cores <= an index in src; a core whose l_read_name or
+ * l_seq is not that of the record it is put in front of; a record with more than 65535 CIGAR operations.  n_reads == 0: LFQ_OK,
+ * an empty result, nothing launched.  *out is the context's: valid until its next frame or encode, or lfq_destroy.  Blocks. */
+typedef struct lfq_bam_framed {
+    int64_t n_reads;
+    const int64_t *rec_off;    /* [n + 1] where record j (its block_size) starts in data */
+    const uint8_t *data;       /* the body, pinned host memory, the context's */
+    int64_t n_bytes;
+} lfq_bam_framed;
+int lfq_bam_frame_encoded(lfq_ctx *ctx, const uint8_t *cores, int64_t n_cores, const lfq_bam_framed **out);
+
+/* lfq_bgzf_deflate cuts `data` into BGZF blocks (SAM specification section 4.1) and compresses every block on the device: raw
+ * deflate (RFC 1951; lofreq_amd/csrc/lfq_deflate.h), one stream of one final block per BGZF block -- the smallest, by exact bit
+ * count, of a stored block (5 + n bytes), one with the fixed codes and one with dynamic codes over an LZ77 match search (lengths 3
+ * to 258, distances up to 32768) inside the block; ties go to the lower type.  There are no compression levels.
+ *   cuts_or_null  NULL: a block every 65280 bytes (htslib's BGZF_BLOCK_SIZE: a stored block of it still fits BSIZE).  Otherwise
+ *                 n_cuts strictly increasing offsets inside (0, n_bytes): the blocks are the pieces between them, each at most
+ *                 65280 bytes -- for a caller that wants no record split across blocks, or virtual offsets for an index: byte
+ *                 p of data lies in the block b with data_off[b] <= p < data_off[b + 1], and its virtual offset is
+ *                 (file offset of comp + comp_off[b]) << 16 | (p - data_off[b]);
+ *   flags         LFQ_BGZF_PUT_EOF appends the 28-byte end-of-file marker.
+ * Every block is the 18 header bytes 1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 and BSIZE - 1, as htslib writes them, the
+ * stream, and CRC-32 and ISIZE of its payload, both computed on the device.  The bytes written depend on the payload alone: the
+ * host program lofreq_amd/csrc/lfq_deflate_check.cpp prints the same streams.
+ * The input goes down in one copy, from the caller's memory if it is pinned and through a pinned staging area otherwise -- unless
+ * `data` lies inside the context's live lfq_bgzf_inflate result or inside its live lfq_bam_frame_encoded result: then the payload is
+ * taken from the device copy (n_from_device = 1).  Two launches: one wavefront per block compresses into a slot of the block's
+ * own; eight bytes a block come back, from which comp_off follows; a second kernel writes header, stream and trailer to their
+ * final places; one copy brings comp back.  The kernel terminates on every input, loads nothing outside the aligned dwords around
+ * a block's payload inside the library's own buffers and stores nothing outside the block's slot.
+ * LFQ_ERR_INVALID, before a device is touched: a NULL ctx or out; n_bytes < 0; NULL data with n_bytes > 0; an unknown flag bit;
+ * NULL cuts with n_cuts > 0; n_cuts < 0; cuts not strictly increasing inside (0, n_bytes); a piece above 65280 bytes.
+ * n_bytes == 0: LFQ_OK, no blocks, nothing launched; comp is then just the marker when LFQ_BGZF_PUT_EOF is set.
+ * *out is the context's: valid until its next lfq_bgzf_deflate or lfq_destroy.  Blocks. */
+#define LFQ_BGZF_PUT_EOF 1
+typedef struct lfq_bgzf_deflated {
+    int64_t n_blocks;          /* the end-of-file marker not counted */
+    const int64_t *data_off;   /* [n_blocks + 1] block b holds input bytes [data_off[b], data_off[b + 1]) */
+    const int64_t *comp_off;   /* [n_blocks + 1] where block b starts in comp */
+    const uint8_t *btype;      /* [n_blocks] 0 stored, 1 fixed, 2 dynamic */
+    const uint8_t *comp;       /* the blocks, then the marker if asked for; pinned host memory, the context's */
+    int64_t n_bytes;           /* all of comp */
+} lfq_bgzf_deflated;
+int lfq_bgzf_deflate(lfq_ctx *ctx, const uint8_t *data, int64_t n_bytes, const int64_t *cuts_or_null, int64_t n_cuts,
+                     unsigned flags, const lfq_bgzf_deflated **out);
+/* the context's last lfq_bgzf_deflate on the device's clock: the input and the offsets down, the two kernels, sizes and blocks back
+ * into pinned memory; n_from_device: 1 when the input was taken from a resident result */
+typedef struct lfq_bgzf_deflate_times {
+    double upload_ms, kernels_ms, download_ms;
+    int64_t n_blocks, n_in_bytes, n_out_bytes;
+    int n_launches, n_from_device;
+} lfq_bgzf_deflate_times;
+int lfq_last_bgzf_deflate_times(lfq_ctx *ctx, lfq_bgzf_deflate_times *t);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

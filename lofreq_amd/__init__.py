@@ -6,7 +6,7 @@ Bonferroni emit test, behind LoFreq's column interface.  Compute lives in hand-w
 mirror of the reference interface plus region sharding across GPUs.
 """
 from ._lib import (LFQ_BAM_DROP_ALN_TAGS, LFQ_BAM_KEEP_EXISTING, LFQ_BAM_PUT_ALIGNMENT, LFQ_BAM_PUT_IDAQ, LFQ_BAM_PUT_INDELQUAL,
-                   LFQ_BAM_PUT_LB, LFQ_BAM_READ_IDAQ, LFQ_BAM_READ_LB)
+                   LFQ_BAM_PUT_LB, LFQ_BAM_READ_IDAQ, LFQ_BAM_READ_LB, LFQ_BGZF_PUT_EOF)
 from ._lib import (COL_COUNTS_DTYPE, COL_PVALS_DTYPE, SNV_RECORD_DTYPE, LFQ_PV_LOG, LFQ_PV_LOG_FECLAMP,
                    LFQ_PV_NONE, LFQ_PV_UNDERFLOW, LFQ_USE_BAQ, LFQ_USE_IDAQ, LFQ_USE_MQ, LFQ_USE_SQ,
                    INDEL_RECORD_DTYPE)
@@ -18,7 +18,8 @@ from .viterbi import viterbi_batch
 from .indelqual import indelqual_batch
 from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_indel_quals, format_plp_quals,
                      format_plp_summary, last_bam_decode_times, last_bam_encode_times, last_baq_fill_stats, last_plp_quals_times, pileup_indel_columns, pileup_snv_tracks, plp_quals,
-                     skip_snv_columns, BgzfError, bam_scan_records, bgzf_inflate, last_bgzf_times)
+                     skip_snv_columns, BgzfError, bam_scan_records, bgzf_inflate, last_bgzf_times,
+                     bam_frame_encoded, bgzf_deflate, last_bgzf_deflate_times)
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
 
@@ -35,4 +36,5 @@ __all__ = [
     "LFQ_BAM_KEEP_EXISTING", "LFQ_BAM_PUT_INDELQUAL",
     "LFQ_BAM_READ_LB", "LFQ_BAM_READ_IDAQ", "last_baq_fill_stats",
     "bgzf_inflate", "BgzfError", "bam_scan_records", "last_bgzf_times",
+    "bgzf_deflate", "last_bgzf_deflate_times", "bam_frame_encoded", "LFQ_BGZF_PUT_EOF",
 ]

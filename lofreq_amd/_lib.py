@@ -177,6 +177,25 @@ class BgzfTimes(C.Structure):
                 ("n_in_bytes", C.c_int64), ("n_out_bytes", C.c_int64), ("n_launches", C.c_int), ("n_decodes_from_device", C.c_int)]
 
 
+class BgzfDeflated(C.Structure):
+    """lfq_bgzf_deflated: owned by the context, valid until its next lfq_bgzf_deflate"""
+    _fields_ = [("n_blocks", C.c_int64)] + [(n, C.c_void_p) for n in ("data_off", "comp_off", "btype", "comp")] + [
+        ("n_bytes", C.c_int64)]
+
+
+class BgzfDeflateTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("kernels_ms", C.c_double), ("download_ms", C.c_double), ("n_blocks", C.c_int64),
+                ("n_in_bytes", C.c_int64), ("n_out_bytes", C.c_int64), ("n_launches", C.c_int), ("n_from_device", C.c_int)]
+
+
+class BamFramed(C.Structure):
+    """lfq_bam_framed: owned by the context, valid until its next frame or encode"""
+    _fields_ = [("n_reads", C.c_int64), ("rec_off", C.c_void_p), ("data", C.c_void_p), ("n_bytes", C.c_int64)]
+
+
+LFQ_BGZF_PUT_EOF = 1
+
+
 class BamScanOpts(C.Structure):
     """lfq_bam_scan_opts"""
     _fields_ = [("tid", C.c_int32), ("beg", C.c_int64), ("end", C.c_int64), ("min_mq", C.c_int), ("max_mq", C.c_int),
@@ -253,6 +272,7 @@ EXPORTS = [
     "lfq_readset_encode_bam", "lfq_last_bam_encode_times",
     "lfq_bgzf_inflate", "lfq_last_bgzf_times", "lfq_bam_scan_opts_init", "lfq_bam_scan_records", "lfq_bam_scan_free",
     "lfq_readset_create_from_bgzf", "lfq_readset_create_from_bam_scan",
+    "lfq_bgzf_deflate", "lfq_last_bgzf_deflate_times", "lfq_bam_frame_encoded",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
     "lfq_plp_quals_from_tracks", "lfq_format_plp_quals", "lfq_set_indel_arrays_all_columns", "lfq_format_plp_indel_quals",
@@ -394,6 +414,9 @@ def load():
     L.lfq_last_bam_encode_times.argtypes = [vp, C.POINTER(BamEncodeTimes)]
     L.lfq_bgzf_inflate.argtypes = [vp, vp, C.c_int64, C.POINTER(C.POINTER(BgzfResult))]
     L.lfq_last_bgzf_times.argtypes = [vp, C.POINTER(BgzfTimes)]
+    L.lfq_bgzf_deflate.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_uint, C.POINTER(C.POINTER(BgzfDeflated))]
+    L.lfq_last_bgzf_deflate_times.argtypes = [vp, C.POINTER(BgzfDeflateTimes)]
+    L.lfq_bam_frame_encoded.argtypes = [vp, vp, C.c_int64, C.POINTER(C.POINTER(BamFramed))]
     L.lfq_bam_scan_opts_init.argtypes = [C.POINTER(BamScanOpts)]
     L.lfq_bam_scan_opts_init.restype = None
     L.lfq_bam_scan_records.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(BamScanOpts), C.POINTER(C.POINTER(BamScan))]

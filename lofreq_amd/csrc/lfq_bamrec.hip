@@ -5,6 +5,12 @@
  * aux pass also notes the first lb / ai / ad field, a stored-tag pass lays those strings out per base, and lfq_readset_baq_fill's merge
  * pass puts them over what the HMM kernels computed.  Further down, the way back
  * (lfq_readset_encode_bam): the records rewritten with a read set's results, a plan pass per read and a copy pass per 16 output bytes.
+ * Last, lfq_bam_frame_encoded: block_size and the 32 core bytes put in front of every record of the live encode result -- the body
+ * of a BAM file, left on the device for lfq_bgzf_deflate.
+ *
+ * core.bin there is the SAM specification's reg2bin (section 5.3) of the record's new pos and CIGAR.  The reference never sets
+ * core.bin after replace_cigar (lofreq_viterbi.c:340), so a realigned record of the 2.1.4 binary can carry the bin of its old
+ * alignment: the bin written here is the specification's and not the binary's.
  */
 #include "lfq_ctx.h"
 
@@ -463,6 +469,18 @@ struct LfqBamState {
     uint8_t none[16] = {};              /* `data` of an empty result */
     lfq_bam_encoded result = {};
     lfq_bam_encode_times enc_times = {};
+    /* lfq_bam_frame_encoded: what it needs of the encode result, which stays in d_out (offsets at its front) */
+    bool enc_live = false;              /* `result` and d_out hold a complete encode */
+    int64_t enc_blob = 0;               /* where the blob starts in d_out */
+    std::vector<uint16_t> enc_lq;       /* [n] l_qname / l_qseq of the record read j was made from */
+    std::vector<int32_t> enc_ls;
+    uint8_t *d_frame = nullptr;         /* cores | src | pos | n_cigar | new cores | the body (grow-only) */
+    int64_t d_frame_bytes = 0;
+    uint8_t *h_frame = nullptr;         /* the body on the host, pinned (grow-only) */
+    int64_t h_frame_bytes = 0;
+    int64_t frame_live = 0, frame_body = 0;     /* bytes of the live body at framed.data (0: none); where it starts in d_frame */
+    std::vector<int64_t> rec_off;
+    lfq_bam_framed framed = {};
 };
 
 static LfqBamState *bam_state(lfq_ctx *c)
@@ -480,6 +498,8 @@ void lfq_bam_release(lfq_ctx *c)
         if (S->d_out) (void)hipFree(S->d_out);
         free_pinned(&S->h_stage, &S->h_bytes);
         free_pinned(&S->h_out, &S->h_out_bytes);
+        if (S->d_frame) (void)hipFree(S->d_frame);
+        free_pinned(&S->h_frame, &S->h_frame_bytes);
         for (LfqEvPair *t : {&S->up_t, &S->kern_t, &S->down_t}) {
             t->destroy();
         }
@@ -1012,6 +1032,10 @@ int lfq_bam_encode_empty(lfq_ctx *c, const lfq_bam_encoded **out)
 {
     LfqBamState *S = bam_state(c);
     S->enc_times = {};
+    S->frame_live = 0;
+    S->enc_lq.clear();
+    S->enc_ls.clear();
+    S->enc_live = true;                 /* (an empty result is a result) */
     S->data_off.assign(1, 0);
     S->src.assign(1, 0);
     S->pos.assign(1, 0);
@@ -1024,6 +1048,8 @@ int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **ou
 {
     LfqBamState *S = bam_state(c);
     const int64_t n = in->n;
+    S->enc_live = false;                /* the result before this one is gone, and the body framed from it */
+    S->frame_live = 0;
     LFQ_TRY_HIP(hipSetDevice(c->device));
     lfq_bam_encode_times &T = S->enc_times;
     T = {};
@@ -1112,6 +1138,14 @@ int lfq_bam_encode(lfq_ctx *c, const LfqBamEncIn *in, const lfq_bam_encoded **ou
     S->src.assign(in->src, in->src + n);
     S->pos.assign(in->pos, in->pos + n);
     S->n_cigar.assign(in->n_cigar, in->n_cigar + n);
+    S->enc_lq.resize((size_t)n);
+    S->enc_ls.resize((size_t)n);
+    for (int64_t j = 0; j < n; j++) {
+        S->enc_lq[(size_t)j] = in->reads[j].l_qname;
+        S->enc_ls[(size_t)j] = in->reads[j].l_qseq;
+    }
+    S->enc_blob = o_blob;
+    S->enc_live = n_out > 0;            /* (offsets and blob are on the device) */
     return bam_publish(S, n, S->h_out, out);
 }
 
@@ -1121,5 +1155,215 @@ extern "C" int lfq_last_bam_encode_times(lfq_ctx *c, lfq_bam_encode_times *t)
         return LFQ_ERR_INVALID;
     }
     *t = bam_state(c)->enc_times;
+    return LFQ_OK;
+}
+
+/* ---- lfq_bam_frame_encoded: the body of a BAM file from the live encode result --------------------------------------------------- */
+#define LFQ_BAM_FRAME_READS 256         /* reads per workgroup of the core pass: one lane each */
+#define LFQ_BAM_FRAME_CHUNKS 256        /* 16-byte chunks of the body per workgroup of the gather pass: one lane each */
+#define LFQ_BAM_FRAME_HEAD 36           /* block_size and the core, in front of every record */
+
+struct LfqBamFrameArgs {
+    const uint8_t *blob;                /* the encode result's records */
+    const int64_t *out_off;             /* [n + 1] where they start in it */
+    const uint32_t *cores;              /* [n_cores][8] the caller's */
+    const int64_t *src;                 /* [n] */
+    const int32_t *pos;                 /* [n] */
+    const uint32_t *n_cigar;            /* [n] */
+    uint32_t *new_cores;                /* [n][8] */
+    uint8_t *body;                      /* 16-byte aligned, 16 bytes of slack */
+    int64_t n_reads, n_body;
+};
+
+/* the SAM specification's reg2bin (section 5.3) for [beg, end) */
+__device__ __forceinline__ uint32_t bam_reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+/* core' of read j: the caller's core of record src[j] with pos, n_cigar_op and bin replaced */
+__global__ __launch_bounds__(LFQ_BAM_FRAME_READS) void lfq_bam_frame_core_kernel(LfqBamFrameArgs A)
+{
+    const int64_t j = (int64_t)blockIdx.x * LFQ_BAM_FRAME_READS + threadIdx.x;
+    if (j >= A.n_reads) {
+        return;
+    }
+    const uint32_t *ci = A.cores + 8 * A.src[j];
+    uint32_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        w[k] = ci[k];
+    }
+    const uint32_t l_qname = w[2] & 0xffu, flag = w[3] >> 16, nc = A.n_cigar[j];
+    /* the CIGAR words of the OUTPUT record: behind its name, inside the record (the host checked l_qname against it, and the
+     * encode wrote n_cigar words there) */
+    const int64_t rec = A.out_off[j], rec_end = A.out_off[j + 1];
+    int64_t ref_bases = 0;
+    for (uint32_t k = 0; k < nc; k++) {
+        const int64_t at = rec + l_qname + 4 * (int64_t)k;
+        if (at + 4 > rec_end) {
+            break;
+        }
+        const uint32_t cw = (uint32_t)A.blob[at] | ((uint32_t)A.blob[at + 1] << 8) | ((uint32_t)A.blob[at + 2] << 16)
+                            | ((uint32_t)A.blob[at + 3] << 24);
+        const uint32_t op = cw & 0xfu;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) {
+            ref_bases += cw >> 4;
+        }
+    }
+    const int64_t pos = A.pos[j], end = pos + ((flag & 4u) || ref_bases == 0 ? 1 : ref_bases);
+    w[1] = (uint32_t)A.pos[j];
+    w[2] = (w[2] & 0xffffu) | (bam_reg2bin(pos, end) << 16);
+    w[3] = (w[3] & 0xffff0000u) | (nc & 0xffffu);
+    uint32_t *co = A.new_cores + 8 * j;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        co[k] = w[k];
+    }
+}
+
+/* 16 bytes of the body per lane: record j starts at out_off[j] + 36 j and is block_size | core' | the record's bytes */
+__global__ __launch_bounds__(LFQ_BAM_FRAME_CHUNKS) void lfq_bam_frame_gather_kernel(LfqBamFrameArgs A)
+{
+    const int64_t b0 = ((int64_t)blockIdx.x * LFQ_BAM_FRAME_CHUNKS + threadIdx.x) * 16;
+    if (b0 >= A.n_body) {
+        return;
+    }
+    int64_t lo = 0, hi = A.n_reads - 1;         /* the last record that starts at or in front of b0 */
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (A.out_off[mid] + LFQ_BAM_FRAME_HEAD * mid <= b0) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    int64_t j = lo, start = A.out_off[j] + LFQ_BAM_FRAME_HEAD * j, next = A.out_off[j + 1] + LFQ_BAM_FRAME_HEAD * (j + 1);
+    uint32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const int64_t p = b0 + k;
+        if (p < A.n_body) {
+            if (p >= next) {                    /* (a record is 36 bytes at least: one step a chunk at most; p < n_body keeps j < n) */
+                j++;
+                start = next;
+                next = A.out_off[j + 1] + LFQ_BAM_FRAME_HEAD * (j + 1);
+            }
+            const int64_t o = p - start;
+            uint32_t byte;
+            if (o < 4) {
+                byte = ((uint32_t)(A.out_off[j + 1] - A.out_off[j] + 32) >> (8 * (int)o)) & 0xffu;
+            } else if (o < LFQ_BAM_FRAME_HEAD) {
+                byte = (A.new_cores[8 * j + ((o - 4) >> 2)] >> (8 * (int)((o - 4) & 3))) & 0xffu;
+            } else {
+                byte = A.blob[A.out_off[j] + o - LFQ_BAM_FRAME_HEAD];
+            }
+            v[k >> 2] |= byte << (8 * (k & 3));
+        }
+    }
+    uint32_t *dst = (uint32_t *)(A.body + b0);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        dst[k] = v[k];
+    }
+}
+
+const uint8_t *lfq_bam_framed_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes)
+{
+    LfqBamState *S = c->bam;
+    if (!S || S->frame_live <= 0 || !p || bytes <= 0) {
+        return nullptr;
+    }
+    const uint8_t *h = S->framed.data;
+    if (p < h || p + bytes > h + S->frame_live) {
+        return nullptr;
+    }
+    return S->d_frame + S->frame_body + (p - h);
+}
+
+extern "C" int lfq_bam_frame_encoded(lfq_ctx *c, const uint8_t *cores, int64_t n_cores, const lfq_bam_framed **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !cores || !out || n_cores < 0) {
+        return LFQ_ERR_INVALID;
+    }
+    LfqBamState *S = c->bam;
+    if (!S || !S->enc_live) {
+        return LFQ_ERR_INVALID;
+    }
+    const int64_t n = S->result.n_reads;
+    for (int64_t j = 0; j < n; j++) {
+        const int64_t s = S->src[(size_t)j];
+        if (s < 0 || s >= n_cores) {
+            return LFQ_ERR_INVALID;
+        }
+        const uint8_t *co = cores + 32 * s;
+        int32_t l_seq;
+        memcpy(&l_seq, co + 16, 4);
+        if (co[8] != S->enc_lq[(size_t)j] || l_seq != S->enc_ls[(size_t)j] || S->n_cigar[(size_t)j] > 0xffffu) {
+            return LFQ_ERR_INVALID;
+        }
+    }
+    S->frame_live = 0;                  /* the body before this one is gone */
+    S->rec_off.resize((size_t)n + 1);
+    for (int64_t j = 0; j <= n; j++) {
+        S->rec_off[(size_t)j] = S->data_off[(size_t)j] + LFQ_BAM_FRAME_HEAD * j;
+    }
+    lfq_bam_framed &F = S->framed;
+    F.n_reads = n;
+    F.rec_off = S->rec_off.data();
+    F.data = S->none;
+    F.n_bytes = S->rec_off[(size_t)n];
+    if (n == 0) {
+        *out = &F;
+        return LFQ_OK;
+    }
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    const int64_t n_body = F.n_bytes;
+    const int64_t o_src = lfq_al(n_cores * 32), o_pos = o_src + lfq_al(n * 8), o_nc = o_pos + lfq_al(n * 4), o_new = o_nc + lfq_al(n * 4),
+                  o_body = o_new + lfq_al(n * 32), total = o_body + lfq_al(n_body + 16);
+    LFQ_TRY(grow(&S->d_frame, &S->d_frame_bytes, total));
+    if (n_body + 16 > S->h_frame_bytes) {
+        LFQ_TRY(grow_pinned(&S->h_frame, &S->h_frame_bytes, std::max<int64_t>(n_body + n_body / 4 + 16, 1 << 16)));
+    }
+    /* one pinned block down: cores | src | pos | n_cigar, laid out as on the device */
+    LfqPin<uint8_t> down(c, (size_t)o_new);
+    LFQ_PIN_OK(down);
+    memcpy(down.data(), cores, (size_t)n_cores * 32);
+    memcpy(down.data() + o_src, S->src.data(), (size_t)n * 8);
+    memcpy(down.data() + o_pos, S->pos.data(), (size_t)n * 4);
+    memcpy(down.data() + o_nc, S->n_cigar.data(), (size_t)n * 4);
+    hipStream_t st = c->stream;
+    LFQ_TRY_HIP(hipMemcpyAsync(S->d_frame, down.data(), (size_t)o_new, hipMemcpyHostToDevice, st));
+    LfqBamFrameArgs A;
+    A.blob = S->d_out + S->enc_blob;
+    A.out_off = (const int64_t *)S->d_out;
+    A.cores = (const uint32_t *)S->d_frame;
+    A.src = (const int64_t *)(S->d_frame + o_src);
+    A.pos = (const int32_t *)(S->d_frame + o_pos);
+    A.n_cigar = (const uint32_t *)(S->d_frame + o_nc);
+    A.new_cores = (uint32_t *)(S->d_frame + o_new);
+    A.body = S->d_frame + o_body;
+    A.n_reads = n;
+    A.n_body = n_body;
+    hipLaunchKernelGGL(lfq_bam_frame_core_kernel, dim3((unsigned)((n + LFQ_BAM_FRAME_READS - 1) / LFQ_BAM_FRAME_READS)),
+                       dim3(LFQ_BAM_FRAME_READS), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    const int64_t n_chunks = (n_body + 15) / 16;
+    hipLaunchKernelGGL(lfq_bam_frame_gather_kernel, dim3((unsigned)((n_chunks + LFQ_BAM_FRAME_CHUNKS - 1) / LFQ_BAM_FRAME_CHUNKS)),
+                       dim3(LFQ_BAM_FRAME_CHUNKS), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY_HIP(hipMemcpyAsync(S->h_frame, A.body, (size_t)n_body, hipMemcpyDeviceToHost, st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    S->frame_body = o_body;
+    S->frame_live = n_body;
+    F.data = S->h_frame;
+    *out = &F;
     return LFQ_OK;
 }

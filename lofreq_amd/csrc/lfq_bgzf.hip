@@ -247,7 +247,7 @@ void lfq_bgzf_release(lfq_ctx *c)
     }
 }
 
-const uint8_t *lfq_bgzf_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes)
+const uint8_t *lfq_bgzf_resident_bytes(lfq_ctx *c, const uint8_t *p, int64_t bytes)
 {
     LfqBgzfState *S = c->bgzf;
     if (!S || S->live_bytes <= 0 || !p || bytes <= 0) {
@@ -257,8 +257,16 @@ const uint8_t *lfq_bgzf_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes)
     if (p < h || p + bytes > h + S->live_bytes) {
         return nullptr;
     }
-    S->times.n_decodes_from_device += 1;
     return S->d_out + (p - h);
+}
+
+const uint8_t *lfq_bgzf_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes)
+{
+    const uint8_t *d = lfq_bgzf_resident_bytes(c, p, bytes);
+    if (d) {
+        c->bgzf->times.n_decodes_from_device += 1;
+    }
+    return d;
 }
 
 static inline uint32_t bgzf_le16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }

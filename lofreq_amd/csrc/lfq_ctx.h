@@ -8,6 +8,7 @@
  *   lfq_readset.hip    the resident read set: upload, BAQ / IDAQ, source quality, both pileups
  *   lfq_bamrec.hip     BAM records decoded and rewritten on the device: kernels and their launches (for lfq_readset.hip)
  *   lfq_bgzf.hip       BGZF blocks inflated on the device (over lfq_inflate.h), the record scan, lfq_readset_create_from_bgzf
+ *   lfq_bgzf_deflate.hip   bytes cut into BGZF blocks and compressed on the device (over lfq_deflate.h)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -453,6 +454,7 @@ struct lfq_ctx {
     struct LfqViterbiState *vit;     /* lfq_viterbi_batch: its result and device buffers (lfq_viterbi.hip; created on first use) */
     struct LfqBamState *bam;         /* lfq_readset_create_from_bam / _encode_bam: records, descriptors, results and timing (lfq_bamrec.hip; created on first use) */
     struct LfqBgzfState *bgzf;       /* lfq_bgzf_inflate: its buffers, result and timing (lfq_bgzf.hip; created on first use) */
+    struct LfqBgzfDefState *bgzf_def; /* lfq_bgzf_deflate: likewise (lfq_bgzf_deflate.hip) */
 };
 
 template <typename T>
@@ -616,6 +618,11 @@ int lfq_bam_encode_empty(lfq_ctx *c, const lfq_bam_encoded **out);
  * [p, p + bytes) when they lie inside the context's live inflate result (counted as a decode from the device), else null */
 void lfq_bgzf_release(lfq_ctx *c);
 const uint8_t *lfq_bgzf_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
+/* the same address without the count: for lfq_bgzf_deflate (lfq_bgzf_deflate.hip), which keeps its own; its twin for the live
+ * lfq_bam_frame_encoded result (lfq_bamrec.hip); and what lfq_destroy frees of lfq_ctx::bgzf_def */
+const uint8_t *lfq_bgzf_resident_bytes(lfq_ctx *c, const uint8_t *p, int64_t bytes);
+const uint8_t *lfq_bam_framed_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
+void lfq_bgzf_deflate_release(lfq_ctx *c);
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

@@ -382,6 +382,53 @@ def last_bgzf_times(caller):
     return {k: getattr(t, k) for k, _ in _lib.BgzfTimes._fields_}
 
 
+def bgzf_deflate(caller, data, cuts=None, eof=False):
+    """lfq_bgzf_deflate: `data` (bytes or uint8 array) cut into BGZF blocks -- every 65280 bytes, or at the offsets `cuts` -- and
+    compressed on the device -> (comp: uint8 array, the blocks and, with eof, the end-of-file marker; comp_off: int64
+    [n_blocks + 1]; data_off: int64 [n_blocks + 1]; btype: uint8 [n_blocks], 0 stored / 1 fixed / 2 dynamic), copies"""
+    a = _as_u8(data)
+    cu = None if cuts is None else np.ascontiguousarray(cuts, np.int64)
+    out = C.POINTER(_lib.BgzfDeflated)()
+    _lib.check(_lib.load().lfq_bgzf_deflate(caller.h, a.ctypes.data if len(a) else None, len(a),
+                                            cu.ctypes.data if cu is not None and len(cu) else None, len(cu) if cu is not None else 0,
+                                            _lib.LFQ_BGZF_PUT_EOF if eof else 0, C.byref(out)), "lfq_bgzf_deflate")
+    return bgzf_deflated_arrays(out.contents)
+
+
+def bgzf_deflated_arrays(r):
+    """the copies bgzf_deflate returns, of an lfq_bgzf_deflated"""
+    nb = int(r.n_blocks)
+    comp_off = np.ctypeslib.as_array(C.cast(r.comp_off, C.POINTER(C.c_int64)), (nb + 1,)).copy()
+    data_off = np.ctypeslib.as_array(C.cast(r.data_off, C.POINTER(C.c_int64)), (nb + 1,)).copy()
+    btype = np.ctypeslib.as_array(C.cast(r.btype, C.POINTER(C.c_uint8)), (nb,)).copy() if nb else np.zeros(0, np.uint8)
+    comp = np.ctypeslib.as_array(C.cast(r.comp, C.POINTER(C.c_uint8)), (int(r.n_bytes),)).copy() if r.n_bytes else np.zeros(0, np.uint8)
+    return comp, comp_off, data_off, btype
+
+
+def last_bgzf_deflate_times(caller):
+    """lfq_last_bgzf_deflate_times -> dict(upload_ms, kernels_ms, download_ms, n_blocks, n_in_bytes, n_out_bytes, n_launches,
+    n_from_device)"""
+    t = _lib.BgzfDeflateTimes()
+    _lib.check(_lib.load().lfq_last_bgzf_deflate_times(caller.h, C.byref(t)), "lfq_last_bgzf_deflate_times")
+    return {k: getattr(t, k) for k, _ in _lib.BgzfDeflateTimes._fields_}
+
+
+def bam_frame_encoded(caller, cores):
+    """lfq_bam_frame_encoded: the body of a BAM file from the caller's last ReadSet.encode_bam result.  cores: the 32 core bytes of
+    every ORIGINAL record (bytes or uint8 array of 32 n) -> (data: uint8 array; rec_off: int64 [n_reads + 1]), copies"""
+    a = _as_u8(cores).reshape(-1)
+    if len(a) % 32:
+        raise ValueError("bam_frame_encoded: cores takes 32 bytes per record")
+    out = C.POINTER(_lib.BamFramed)()
+    keep = a if len(a) else np.zeros(32, np.uint8)          # (a pointer even for no cores: NULL is an error of its own)
+    _lib.check(_lib.load().lfq_bam_frame_encoded(caller.h, keep.ctypes.data, len(a) // 32, C.byref(out)), "lfq_bam_frame_encoded")
+    r = out.contents
+    n = int(r.n_reads)
+    rec_off = np.ctypeslib.as_array(C.cast(r.rec_off, C.POINTER(C.c_int64)), (n + 1,)).copy()
+    data = np.ctypeslib.as_array(C.cast(r.data, C.POINTER(C.c_uint8)), (int(r.n_bytes),)).copy() if r.n_bytes else np.zeros(0, np.uint8)
+    return data, rec_off
+
+
 def _scan_opts(tid=-1, beg=0, end=None, min_mq=0, max_mq=255, no_orphan=False, flag_mask=None):
     o = _lib.BamScanOpts()
     _lib.load().lfq_bam_scan_opts_init(C.byref(o))

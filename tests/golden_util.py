@@ -307,3 +307,38 @@ def py_indel_pileup(reads, ref, min_plp_idq=0):
             elif op in "IS":
                 y += l
     return cols
+
+
+def assert_indel_columns_equal(cols, col_pos, want, begin, end):
+    """every field of the indel columns `cols` at the positions `col_pos` against py_indel_pileup's `want`
+    -> the number of events compared"""
+    assert col_pos.tolist() == sorted(p for p in want if begin <= p < end)
+    n_ev = 0
+    for c, p in enumerate(col_pos.tolist()):
+        w = want[p]
+        got = {k: int(getattr(cols, k)[c]) for k in ("coverage_plp", "num_tails", "num_non_indels", "num_ins", "num_dels")}
+        assert got == {"coverage_plp": w["cov"], "num_tails": w["tails"], "num_non_indels": w["non_indels"],
+                       "num_ins": w["n_ins"], "num_dels": w["n_dels"]}, p
+        for sd in range(2):
+            S = cols.sides[sd]
+            assert (int(S["non_fw"][c]), int(S["non_rv"][c])) == (w["non_fw"][sd], w["non_rv"][sd]), (p, sd)
+            e0, e1 = int(S["ev_off"][c]), int(S["ev_off"][c + 1])
+            assert [cols.keys[sd][i] for i in range(e0, e1)] == list(w["ev"][sd].keys()), (p, sd)
+            a, b = int(S["ne_off"][c]), int(S["ne_off"][c + 1])
+            if w["ev"][0] or w["ev"][1]:
+                got_ne, want_ne = list(zip(S["ne_q"][a:b].tolist(), S["ne_mq"][a:b].tolist())), list(w["ne"][sd])
+                if os.environ.get("LFQ_PILEUP_ATOMIC"):
+                    got_ne, want_ne = sorted(got_ne), sorted(want_ne)
+                assert got_ne == want_ne, (p, sd)
+            else:
+                assert a == b
+            for i, key in zip(range(e0, e1), w["ev"][sd]):
+                r0, r1 = int(S["rd_off"][i]), int(S["rd_off"][i + 1])
+                members = w["ev"][sd][key]
+                assert S["rd_q"][r0:r1].tolist() == [m[0] for m in members], (p, key)
+                assert S["rd_aq"][r0:r1].tolist() == [m[1] for m in members], (p, key)
+                assert S["rd_mq"][r0:r1].tolist() == [m[2] for m in members], (p, key)
+                assert S["rd_sq"][r0:r1].tolist() == [min(m[3], 32767) for m in members], (p, key)
+                assert int(S["ev_rv"][i]) == sum(m[4] for m in members) and int(S["ev_fw"][i]) == len(members) - int(S["ev_rv"][i])
+                n_ev += 1
+    return n_ev

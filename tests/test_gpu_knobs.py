@@ -79,6 +79,19 @@ def test_knob_selected_dp_edges(knob, sel):
     test_knob_selected_paths(knob, sel)
 
 
+PLP_EDGES = ["tests/test_gpu_pileup_edges.py"]
+PLP_EDGE_CASES = [
+    ("LFQ_PILEUP_TILES=0", PLP_EDGES),       # a wavefront per position: the kernels the tile kernels must agree with
+    ("LFQ_PILEUP_ATOMIC=1", PLP_EDGES),      # read-major pileup kernels
+]
+
+
+@pytest.mark.parametrize("knob,sel", PLP_EDGE_CASES, ids=[c[0] for c in PLP_EDGE_CASES])
+def test_knob_selected_pileup_edges(knob, sel):
+    """the pileup boundary rows (row capacity, rounds, tile and region edges) on the kernels that replace the tile kernels"""
+    test_knob_selected_paths(knob, sel)
+
+
 _SKIP_PROBE = r"""
 import sys
 sys.path.insert(0, "tests")

@@ -6,6 +6,7 @@
  *   lfq_api.hip        context, streams, the batch driver (layer 1), the call_snvs loop (layer 2), uniq, generator
  *   lfq_indel_api.hip  the indel tests (lfq_call_indel_tests_batch, lfq_call_indels_batch)
  *   lfq_readset.hip    the resident read set: upload, BAQ / IDAQ, source quality, both pileups
+ *   lfq_plp_indel_host.h   the host stages of its indel pileup, plain C++ (and the columns it hands out, LfqIndelColsOwned)
  *   lfq_bamrec.hip     BAM records decoded and rewritten on the device: kernels and their launches (for lfq_readset.hip)
  *   lfq_bgzf.hip       BGZF blocks inflated on the device (over lfq_inflate.h), the record scan, lfq_readset_create_from_bgzf
  *   lfq_bgzf_deflate.hip   bytes cut into BGZF blocks and compressed on the device (over lfq_deflate.h)
@@ -37,6 +38,7 @@
 #include <vector>
 
 #include "lfq_internal.h"
+#include "lfq_plp_indel_host.h"
 #include "lofreq_synth.h"
 
 #define LFQ_TRY_HIP(expr)           \
@@ -55,7 +57,6 @@
         }                           \
     } while (0)
 
-/* the columns handed out by lfq_pileup_indel_columns live here until the next call */
 static inline double lfq_now_ms()
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -179,6 +180,26 @@ private:
     pid_t pid_;
 };
 
+/* f(part) for part in [0, n_parts), part 0 here: the others on the pool's helpers when it is free, else on threads of their own */
+template <typename F>
+static void lfq_run_parts(int n_parts, F f)
+{
+    const std::function<void(int)> task = [&](int p) { f(p); };
+    if (n_parts > 1 && LfqLoopPool::instance().try_run(n_parts, task)) {    /* (one part: the pool is not even created) */
+        f(0);
+        LfqLoopPool::instance().finish();
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int p = 1; p < n_parts; p++) {
+        th.emplace_back([&f, p] { f(p); });
+    }
+    f(0);
+    for (auto &t : th) {
+        t.join();
+    }
+}
+
 /* per-read host loops of the read-set steps (geometry from the CIGARs, event candidates): independent reads, split
  * over a few threads when there are enough of them.  f(begin, end, part) */
 template <typename F>
@@ -196,68 +217,8 @@ static void lfq_for_reads(int64_t n, F f, int *parts_out = nullptr)
     if (parts_out) {
         *parts_out = parts;
     }
-    if (parts == 1) {
-        f((int64_t)0, n, 0);
-        return;
-    }
-    const std::function<void(int)> task = [&](int p) { f(n * p / parts, n * (p + 1) / parts, p); };
-    LfqLoopPool &pool = LfqLoopPool::instance();
-    if (pool.try_run(parts, task)) {
-        f((int64_t)0, n / parts, 0);
-        pool.finish();
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int p = 1; p < parts; p++) {
-        th.emplace_back([&, p] { f(n * p / parts, n * (p + 1) / parts, p); });
-    }
-    f((int64_t)0, n / parts, 0);
-    for (auto &t : th) {
-        t.join();
-    }
+    lfq_run_parts(parts, [&](int p) { f(n * p / parts, n * (p + 1) / parts, p); });
 }
-
-/* std::vector whose resize() leaves new elements of a trivial type uninitialised: the per-region column arrays (tens of MB)
- * are resized by one thread and then written in full by the pool's threads -- value-initialising them first was a serial
- * memset of every array, milliseconds per region. */
-template <class T>
-struct LfqNoInitAlloc : std::allocator<T> {
-    template <class U> struct rebind { typedef LfqNoInitAlloc<U> other; };
-    LfqNoInitAlloc() = default;
-    template <class U> LfqNoInitAlloc(const LfqNoInitAlloc<U> &) {}
-    template <class U> void construct(U *p) { ::new ((void *)p) U; }
-    template <class U, class A0, class... Args> void construct(U *p, A0 &&a0, Args &&...args)
-    {
-        ::new ((void *)p) U(std::forward<A0>(a0), std::forward<Args>(args)...);
-    }
-};
-template <class T> using LfqVec = std::vector<T, LfqNoInitAlloc<T>>;
-
-struct LfqIndelColsOwned {
-    lfq_indel_columns cols;
-    LfqVec<uint8_t> ref_base, cons_indel;
-    LfqVec<int32_t> cov, tails, non_indels, n_ins, n_dels, hrun;
-    std::vector<int32_t> ne_qsum[2];     /* per column: ins_nonevent_qual / del_nonevent_qual (plp.c:810) where the column-major kernel summed them */
-    struct Side {
-        LfqVec<int32_t> non_fw, non_rv, ev_fw, ev_rv;
-        LfqVec<int64_t> ne_off, ev_off, key_off, rd_off;
-        LfqVec<int16_t> ne_q, ne_mq, rd_q, rd_aq, rd_mq, rd_sq;
-        LfqVec<char> key_chars;
-    } side[2];
-    void reset()
-    {
-        memset(&cols, 0, sizeof(cols));
-        ref_base.clear(); cons_indel.clear();
-        cov.clear(); tails.clear(); non_indels.clear(); n_ins.clear(); n_dels.clear(); hrun.clear();
-        ne_qsum[0].clear(); ne_qsum[1].clear();
-        for (Side &s : side) {
-            s.non_fw.clear(); s.non_rv.clear(); s.ev_fw.clear(); s.ev_rv.clear();
-            s.ne_off.clear(); s.ev_off.clear(); s.key_off.clear(); s.rd_off.clear();
-            s.ne_q.clear(); s.ne_mq.clear(); s.rd_q.clear(); s.rd_aq.clear(); s.rd_mq.clear(); s.rd_sq.clear();
-            s.key_chars.clear();
-        }
-    }
-};
 
 /* what lfq_readset_plp_summary hands out (host arrays, valid until the next summary call on the context) */
 struct LfqSummaryOwned {

@@ -210,6 +210,36 @@ static inline char lfq_seq_letter(unsigned code)
     return code > 15u ? 'N' : LFQ_SEQ_LETTERS[code];
 }
 
+#if defined(__HIPCC__)
+__host__ __device__ inline __attribute__((always_inline))      /* (__forceinline__, without the runtime's header) */
+#else
+static inline
+#endif
+int lfq_cigar_peek_indel(const uint32_t *cg, int nc, int k)
+{
+    int indel = 0;          /* htslib's resolve_cigar2: what follows operation k (> 0 inserted, < 0 deleted bases, 0 neither) */
+    if (k + 1 < nc) {
+        const int op2 = cg[k + 1] & 0xf, l2 = cg[k + 1] >> 4;
+        if (op2 == 2) {
+            indel = -l2;
+        } else if (op2 == 1) {
+            indel = l2;
+        } else if (op2 == 6 && k + 2 < nc) {
+            int l3 = 0;
+            for (int kk = k + 2; kk < nc; ++kk) {
+                const int o3 = cg[kk] & 0xf;
+                if (o3 == 1) {
+                    l3 += cg[kk] >> 4;
+                } else if (o3 == 2 || o3 == 0 || o3 == 3 || o3 == 7 || o3 == 8) {
+                    break;
+                }
+            }
+            indel = l3 > 0 ? l3 : 0;
+        }
+    }
+    return indel;
+}
+
 struct LfqKnobs {
     int timing;                /* LFQ_TIMING: host phases of the layer-2 calls to stderr */
     int single_stream;         /* LFQ_SINGLE_STREAM: every kernel on the caller's stream (rocprofv3 --pmc passes) */

@@ -855,31 +855,6 @@ struct LfqTileIndel {
     bool slow;
 };
 
-__device__ __forceinline__ int lfq_cigar_peek_indel(const uint32_t *cg, int nc, int k)
-{
-    int indel = 0;                                      /* resolve_cigar2: what follows operation k */
-    if (k + 1 < nc) {
-        const int op2 = cg[k + 1] & 0xf, l2 = cg[k + 1] >> 4;
-        if (op2 == 2) {
-            indel = -l2;
-        } else if (op2 == 1) {
-            indel = l2;
-        } else if (op2 == 6 && k + 2 < nc) {
-            int l3 = 0;
-            for (int kk = k + 2; kk < nc; ++kk) {
-                const int o3 = cg[kk] & 0xf;
-                if (o3 == 1) {
-                    l3 += cg[kk] >> 4;
-                } else if (o3 == 2 || o3 == 0 || o3 == 3 || o3 == 7 || o3 == 8) {
-                    break;
-                }
-            }
-            indel = l3 > 0 ? l3 : 0;
-        }
-    }
-    return indel;
-}
-
 __device__ __forceinline__ LfqTileIndel lfq_tile_resolve_indel(const uint32_t *cg, int nc, int64_t x, int64_t s0, int64_t p0, int tile)
 {
     LfqTileIndel R;

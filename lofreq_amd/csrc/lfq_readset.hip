@@ -1856,11 +1856,7 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
         h_off[i] = (uint64_t)n_obs;
         n_obs += h_nb[i];
         max_obs = std::max<int64_t>(max_obs, h_nb[i]);
-        uint8_t rb = rs->ref ? (uint8_t)rs->ref[site_pos[i]] : (uint8_t)'N';     /* plp.c:818-823, as the region pileup */
-        if (!(rb == 'A' || rb == 'C' || rb == 'T' || rb == 'G' || rb == 'N')) {
-            rb = 'N';
-        }
-        hdr[(size_t)(t_ref + i)] = rb;
+        hdr[(size_t)(t_ref + i)] = lfq_plp_ref_base(rs->ref, rs->ref_len, site_pos[i]);    /* as the region pileup */
     }
     h_off[n] = (uint64_t)n_obs;
     memcpy(hdr.data() + t_cov, h_cov, (size_t)n * 4);
@@ -1951,13 +1947,26 @@ int lfq_pileup_indel_columns(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_p
     return rc;
 }
 
+/* the host arrays the indel pileup's host stages (lfq_plp_indel_host.h) read: tag bytes where the caller gave them (ai / ad
+ * computed by lfq_readset_baq are fetched per event instead), the -d decision readset_pileup_view made */
+static LfqPlpReads readset_plp_reads(const lfq_ctx *c, const lfq_readset *rs)
+{
+    LfqPlpReads R = {};
+    R.pos = rs->pos; R.cigar_off = rs->cigar_off; R.seq_off = rs->seq_off; R.cigar = rs->cigar;
+    R.seq = rs->seq; R.mapq = rs->mapq; R.reverse = rs->reverse; R.ref = rs->ref; R.ref_len = rs->ref_len;
+    R.bi = rs->h_bi; R.bd = rs->h_bd; R.ai = rs->h_ai; R.ad = rs->h_ad; R.fl = rs->fl.data();
+    R.sq = rs->h_sq ? rs->h_sq : (rs->sq32.empty() ? nullptr : rs->sq32.data());
+    R.idq_mode = rs->idq_mode; R.idq_ins = rs->idq_ins; R.idq_del = rs->idq_del;
+    R.keep = (c->plp_max_depth != LFQ_NO_MAX_DEPTH && rs->keep_valid && !rs->keep.empty()) ? rs->keep.data() : nullptr;
+    return R;
+}
+
 int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, int64_t region_end, int min_plp_idq,
                               const lfq_indel_columns **cols_out, int64_t *col_pos_out)
 {
     if (!c || !rs || rs->c != c || !cols_out || region_end < region_begin || (rs->n > 0 && (!rs->mapq || !rs->reverse))) {
         return LFQ_ERR_INVALID;
     }
-    const lfq_readset *rd = rs;
     if (c->plp_indel) {
         c->plp_indel->reset();              /* keeps the capacity: see LfqPin for what freeing a DMA target costs */
     } else {
@@ -1968,673 +1977,190 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
     memset(&O.cols, 0, sizeof(O.cols));
     *cols_out = &O.cols;
     const int64_t n = rs->n, width = region_end - region_begin;
-    /* tag bytes on the host where the caller gave them; ai / ad computed by lfq_readset_baq are fetched per event */
-    const uint8_t *t_bi = rs->h_bi, *t_bd = rs->h_bd, *t_ai = rs->h_ai, *t_ad = rs->h_ad, *t_fl = rs->fl.data();
-    const int32_t *t_sq = rs->h_sq ? rs->h_sq : (rs->sq32.empty() ? nullptr : rs->sq32.data());
-
-    /* ... and BI / BD computed by lfq_readset_indelqual are evaluated for the event's base: q[0] = BI, q[1] = BD as qualities */
-    auto idq_at = [rs, rd](int64_t r, int qpos, int *q) {
-        if (qpos < 0) {
-            q[0] = q[1] = 0;
-        } else if (rs->idq_mode == LFQ_IDQ_UNIFORM) {
-            q[0] = (int)rs->idq_ins - 33;
-            q[1] = (int)rs->idq_del - 33;
-        } else {
-            q[0] = q[1] = (int)lfq_idq_host_byte(rd->ref, rd->ref_len, rd->pos[r], rd->cigar + rd->cigar_off[r],
-                                                 (int)(rd->cigar_off[r + 1] - rd->cigar_off[r]), qpos) - 33;
-        }
-    };
-
-    double tm[8] = {lfq_now_ms(), 0, 0, 0, 0, 0, 0, 0};
-    /* 1. events from the CIGARs, in read (= pileup) order */
-    struct Ev { int64_t pos; int64_t read; int32_t qpos, indel; };
-    std::vector<Ev> evs;
-    std::vector<Ev> evs_part[LFQ_HOST_PARTS];                    /* per thread, concatenated in read order below */
-    /* (host arrays only: runs while the counter kernel of step 2 does) */
-    auto scan_events = [&]() {
-    const uint8_t *kept = (c->plp_max_depth != LFQ_NO_MAX_DEPTH && rs->keep_valid && !rs->keep.empty()) ? rs->keep.data() : nullptr;
-    lfq_for_reads(n, [&](int64_t r_begin, int64_t r_end, int part) {
-    std::vector<Ev> &evs = evs_part[part];
-    for (int64_t r = r_begin; r < r_end; r++) {
-        if (kept && !kept[r]) {
-            continue;                       /* dropped by the -d cap: in no column */
-        }
-        const uint32_t *cg = rd->cigar + rd->cigar_off[r];
-        const int n_cigar = (int)(rd->cigar_off[r + 1] - rd->cigar_off[r]);
-        const int64_t s0 = rd->seq_off[r];
-        const int l_qseq = (int)(rd->seq_off[r + 1] - s0);
-        const uint32_t fl = t_fl[r];
-        int64_t x = rd->pos[r];
-        int y = 0;
-        int q_ev[2];
-        for (int k = 0; k < n_cigar; ++k) {
-            const int op = cg[k] & 0xf, l = cg[k] >> 4;
-            if (op == 0 || op == 7 || op == 8 || op == 2 || op == 3) {
-                const bool is_del = op == 2 || op == 3;
-                int indel = 0;                                      /* htslib resolve_cigar2: peek at the next operation */
-                if (l > 0 && k + 1 < n_cigar) {
-                    const int op2 = cg[k + 1] & 0xf, l2 = cg[k + 1] >> 4;
-                    if (op2 == 2) {
-                        indel = -l2;
-                    } else if (op2 == 1) {
-                        indel = l2;
-                    } else if (op2 == 6 && k + 2 < n_cigar) {
-                        int l3 = 0;
-                        for (int kk = k + 2; kk < n_cigar; ++kk) {
-                            const int o3 = cg[kk] & 0xf;
-                            if (o3 == 1) {
-                                l3 += cg[kk] >> 4;
-                            } else if (o3 == 2 || o3 == 0 || o3 == 3 || o3 == 7 || o3 == 8) {
-                                break;
-                            }
-                        }
-                        indel = l3 > 0 ? l3 : 0;
-                    }
-                }
-                const int64_t p = x + l - 1;
-                if (indel != 0 && p >= region_begin && p < region_end) {
-                    int qpos = is_del ? y : y + l - 1;
-                    qpos = qpos < l_qseq ? qpos : l_qseq - 1;
-                    if (rs->idq_mode) {
-                        idq_at(r, qpos, q_ev);
-                    }
-                    const int iq = rs->idq_mode ? q_ev[0] : (t_bi && (fl & 1u) && qpos >= 0) ? (int)t_bi[s0 + qpos] - 33 : 0;
-                    const int dq = rs->idq_mode ? q_ev[1] : (t_bd && (fl & 2u) && qpos >= 0) ? (int)t_bd[s0 + qpos] - 33 : 0;
-                    if (!(iq < min_plp_idq || dq < min_plp_idq)) {      /* plp.c:1062 */
-                        evs.push_back({p, r, qpos, indel});
-                    }
-                }
-                x += l;
-                if (!is_del) {
-                    y += l;
-                }
-            } else if (op == 1 || op == 4) {
-                y += l;
-            }
-        }
-    }
-    /* by position, reads of one position in read order: every part sorts its own events on its thread ... */
-    std::stable_sort(evs.begin(), evs.end(), [](const Ev &a, const Ev &b) { return a.pos < b.pos; });
-    });
-    /* ... and the parts, which are consecutive ranges of position-sorted reads and overlap only at their ends, are merged
-     * one after the other (std::inplace_merge keeps equal positions in part order = read order) */
-    const auto by_pos = [](const Ev &a, const Ev &b) { return a.pos < b.pos; };
-    for (int p = 0; p < LFQ_HOST_PARTS; p++) {
-        const size_t mid = evs.size();
-        evs.insert(evs.end(), evs_part[p].begin(), evs_part[p].end());
-        if (mid > 0 && mid < evs.size() && by_pos(evs[mid], evs[mid - 1])) {
-            /* (only the tail of what is there can lie behind the new part's first event) */
-            const auto first = std::upper_bound(evs.begin(), evs.begin() + (std::ptrdiff_t)mid, evs[mid], by_pos);
-            std::inplace_merge(first, evs.begin() + (std::ptrdiff_t)mid, evs.end(), by_pos);
-        }
-    }
-    };
-    const uint8_t *g_ai = nullptr, *g_ad = nullptr;     /* per event, when the qualities come from the device */
-    std::vector<int32_t> qsum[2];           /* per column: quality sum of the reads without an event, from the kernel */
-    /* 5. consensus indel (plp.c:1236-1270): the largest sum of qualities of one event against the sum over the
-     * reads without an event of that side */
-    auto consensus = [&]() {
-    O.cons_indel.assign(O.cov.size(), 0);
-    for (int64_t col = 0; col < (int64_t)O.cov.size(); col++) {
-        for (int sd = 0; sd < 2; sd++) {
-            const LfqIndelColsOwned::Side &S = O.side[sd];
-            if (S.ev_off[(size_t)col] == S.ev_off[(size_t)col + 1]) {
-                continue;                               /* no event of this side: nothing can exceed the non-event sum */
-            }
-            int64_t best = 0, non = 0;
-            for (int64_t e = S.ev_off[(size_t)col]; e < S.ev_off[(size_t)col + 1]; e++) {
-                int64_t sum = 0;
-                for (int64_t i = S.rd_off[(size_t)e]; i < S.rd_off[(size_t)e + 1]; i++) {
-                    sum += S.rd_q[(size_t)i];
-                }
-                best = std::max(best, sum);
-            }
-            if (!qsum[sd].empty()) {
-                non = qsum[sd][(size_t)col];
-            } else {
-                for (int64_t i = S.ne_off[(size_t)col]; i < S.ne_off[(size_t)col + 1]; i++) {
-                    non += S.ne_q[(size_t)i];
-                }
-            }
-            if (best > non) {
-                O.cons_indel[(size_t)col] = 1;
-            }
-        }
-    }
-    };
-
     if (n == 0 || width == 0) {
-        for (int sd = 0; sd < 2; sd++) {
-            O.side[sd].ne_off.assign(1, 0);
-            O.side[sd].ev_off.assign(1, 0);
-            O.side[sd].key_off.assign(1, 0);
-            O.side[sd].rd_off.assign(1, 0);
-        }
-        consensus();
-    } else {
-        /* 2. dense counters on the device */
-        LFQ_TRY_HIP(hipSetDevice(c->device));
-        /* Steps 2 and 3 read nothing lfq_readset_baq writes (of the flag bytes only the BI / BD bits, which its merge
-         * kernel leaves as they are): while its kernels are still running they go to another stream and run beside them --
-         * the BAQ kernels hold one wavefront per SIMD and 416 of its 512 registers, these kernels need 40. */
-        hipStream_t ps = (rs->baq_pending && c->dps && !lfq_knobs().single_stream) ? c->dps : c->stream;
-        (void)readset_pmax(c, rs, ps, true);    /* (its small upload is waited for on this stream: before the stream itself waits) */
-        LFQ_TRY(readset_upload_wait(rs, ps));
-        if (rs->ev_idq) {
-            LFQ_TRY_HIP(hipStreamWaitEvent(ps, rs->ev_idq, 0));
-        }
-        const int64_t o_cnt = 0, o_cur = o_cnt + 9 * lfq_al(width * 4), o_off = o_cur + 2 * lfq_al(width * 4),
-                      total = o_off + 2 * lfq_al(width * 8);
-        LFQ_TRY(grow(&c->d_tmp[1], &c->tmp_bytes[1], total));
-        uint8_t *d = c->d_tmp[1];
-        int16_t *d_ne = nullptr;
-        int rc = LFQ_OK;
-        auto up = [&](int64_t off, const void *src, int64_t bytes) {
-            if (rc == LFQ_OK && src && bytes > 0
-                && hipMemcpyAsync(d + off, src, (size_t)bytes, hipMemcpyHostToDevice, ps) != hipSuccess) {
-                rc = LFQ_ERR_HIP;
+        for (LfqIndelColsOwned::Side &S : O.side) {
+            for (auto *v : {&S.ne_off, &S.ev_off, &S.key_off, &S.rd_off}) {
+                v->assign(1, 0);
             }
-        };
-        if (rc == LFQ_OK && hipMemsetAsync(d + o_cnt, 0, (size_t)(o_off - o_cnt), ps) != hipSuccess) {
+        }
+        lfq_plp_publish(O);
+        return LFQ_OK;
+    }
+    double tm[6] = {lfq_now_ms(), 0, 0, 0, 0, 0};
+    /* 2. dense counters on the device */
+    LFQ_TRY_HIP(hipSetDevice(c->device));
+    /* Steps 2 and 3 read nothing lfq_readset_baq writes (of the flag bytes only the BI / BD bits, which its merge
+     * kernel leaves as they are): while its kernels are still running they go to another stream and run beside them --
+     * the BAQ kernels hold one wavefront per SIMD and 416 of its 512 registers, these kernels need 40. */
+    hipStream_t ps = (rs->baq_pending && c->dps && !lfq_knobs().single_stream) ? c->dps : c->stream;
+    (void)readset_pmax(c, rs, ps, true);    /* (its small upload is waited for on this stream: before the stream itself waits) */
+    LFQ_TRY(readset_upload_wait(rs, ps));
+    if (rs->ev_idq) {
+        LFQ_TRY_HIP(hipStreamWaitEvent(ps, rs->ev_idq, 0));
+    }
+    const int64_t o_cnt = 0, o_cur = o_cnt + 9 * lfq_al(width * 4), o_off = o_cur + 2 * lfq_al(width * 4),
+                  total = o_off + 2 * lfq_al(width * 8);
+    LFQ_TRY(grow(&c->d_tmp[1], &c->tmp_bytes[1], total));
+    uint8_t *d = c->d_tmp[1];
+    /* an error from here on: the pinned blocks of this call may still be a copy's source or target */
+    auto fail = [&](int rc) {
+        (void)hipStreamSynchronize(ps);
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    };
+    if (hipMemsetAsync(d + o_cnt, 0, (size_t)(o_off - o_cnt), ps) != hipSuccess) {
+        return fail(LFQ_ERR_HIP);
+    }
+    LfqPlpIndelArgs A;
+    memset(&A, 0, sizeof(A));
+    A.begin = region_begin;
+    A.width = width;
+    A.min_plp_idq = min_plp_idq;
+    int32_t **cnt[9] = {&A.cov, &A.tails, &A.non_indels, &A.n_ins, &A.n_dels, &A.non_ins_fw, &A.non_del_fw,
+                        &A.ne_qsum[0], &A.ne_qsum[1]};
+    /* the nine per-position counters come back into pinned memory (grow-only): DMA instead of a staged copy */
+    int32_t *h[9] = {nullptr};
+    LFQ_TRY(grow_pinned(&c->h_pin2, &c->pin2_bytes, 9 * lfq_al(width * 4)));
+    for (int i = 0; i < 9; i++) {
+        *cnt[i] = (int32_t *)(d + o_cnt + i * lfq_al(width * 4));
+        h[i] = (int32_t *)(c->h_pin2 + i * lfq_al(width * 4));
+    }
+    /* not coordinate-sorted: refused like mpileup does (lfq_set_pileup_unsorted); -d cap: the kept reads only */
+    int rc = readset_pileup_view(c, rs, ps, true, &A);
+    if (rc == LFQ_OK) {
+        rc = A.pmax_end ? lfq_launch_plp_indel_columns(A, 0, ps) : lfq_launch_plp_indel(A, 0, ps);
+    }
+    const bool have_qsum = A.pmax_end != nullptr;       /* the column-major kernel sums the qualities itself */
+    for (int i = 0; i < (have_qsum ? 9 : 7) && rc == LFQ_OK; i++) {
+        if (hipMemcpyAsync(h[i], *cnt[i], (size_t)width * 4, hipMemcpyDeviceToHost, ps) != hipSuccess) {
             rc = LFQ_ERR_HIP;
         }
-        LfqPlpIndelArgs A;
-        memset(&A, 0, sizeof(A));
-        A.begin = region_begin;
-        A.width = width;
-        A.min_plp_idq = min_plp_idq;
-        int32_t **cnt[9] = {&A.cov, &A.tails, &A.non_indels, &A.n_ins, &A.n_dels, &A.non_ins_fw, &A.non_del_fw,
-                            &A.ne_qsum[0], &A.ne_qsum[1]};
-        for (int i = 0; i < 9; i++) {
-            *cnt[i] = (int32_t *)(d + o_cnt + i * lfq_al(width * 4));
-        }
-        /* the nine per-position counters come back into pinned memory (grow-only): DMA instead of a staged copy */
-        int32_t *h[9] = {nullptr};
-        {
-            LFQ_TRY(grow_pinned(&c->h_pin2, &c->pin2_bytes, 9 * lfq_al(width * 4)));
-            for (int i = 0; i < 9; i++) {
-                h[i] = (int32_t *)(c->h_pin2 + i * lfq_al(width * 4));
-            }
-        }
-        if (rc == LFQ_OK) {
-            /* not coordinate-sorted: refused like mpileup does (lfq_set_pileup_unsorted); -d cap: the kept reads only */
-            rc = readset_pileup_view(c, rs, ps, true, &A);
-        }
-        if (rc == LFQ_OK) {
-            rc = A.pmax_end ? lfq_launch_plp_indel_columns(A, 0, ps) : lfq_launch_plp_indel(A, 0, ps);
-        }
-        const bool have_qsum = A.pmax_end != nullptr;       /* the column-major kernel sums the qualities itself */
-        for (int i = 0; i < (have_qsum ? 9 : 7) && rc == LFQ_OK; i++) {
-            if (hipMemcpyAsync(h[i], *cnt[i], (size_t)width * 4, hipMemcpyDeviceToHost, ps) != hipSuccess) {
+    }
+    if (rc != LFQ_OK) {
+        return fail(rc);
+    }
+    /* 1. events from the CIGARs, every thread those of its reads, then merged (host arrays only: runs while the counter
+     * kernel of step 2 does) */
+    const LfqPlpReads R = readset_plp_reads(c, rs);
+    std::vector<LfqPlpEv> evs, evs_part[LFQ_HOST_PARTS];
+    lfq_for_reads(n, [&](int64_t r_begin, int64_t r_end, int part) {
+        lfq_plp_scan_events(R, r_begin, r_end, region_begin, region_end, min_plp_idq, evs_part[part]);
+    });
+    lfq_plp_merge_events(evs_part, LFQ_HOST_PARTS, evs);
+    /* 4a. the event tables, part by part, while the counter kernel is still on its way (it waits for BI / BD, the end of
+     * the upload): they need the events and the caller's arrays, nothing from the device */
+    const int n_parts = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<long>(std::max<long>(lfq_knobs().host_loop_threads, 1), LFQ_HOST_PARTS), evs.size() / (size_t)std::max<int64_t>(lfq_knobs().host_par_min / 48, 1)));
+    const std::vector<size_t> cut = lfq_plp_table_cuts(evs, n_parts);
+    std::vector<LfqPlpPartTables> pt((size_t)n_parts);
+    lfq_run_parts(n_parts, [&](int t) { lfq_plp_build_tables(R, evs, cut[(size_t)t], cut[(size_t)t + 1], region_begin, pt[(size_t)t]); });
+    LfqPlpTables T;
+    lfq_plp_append_tables(pt, O, T);
+    tm[1] = lfq_now_ms();
+    if (hipStreamSynchronize(ps) != hipSuccess) {
+        return fail(LFQ_ERR_HIP);
+    }
+    tm[2] = lfq_now_ms();
+    /* 3. columns = covered positions; quality arrays of the reads without an event at the event positions */
+    LfqPin<int64_t> pos_off_ins(c, (size_t)width), pos_off_del(c, (size_t)width);      /* DMA sources: pinned */
+    if (!pos_off_ins.ok() || !pos_off_del.ok()) {
+        return fail(LFQ_ERR_NOMEM);
+    }
+    int64_t *const pos_off[2] = {pos_off_ins.data(), pos_off_del.data()};
+    LfqVec<int32_t> col_of((size_t)width);      /* (col_of and pos_off: every position is written by the second pass) */
+    const bool host_arrays = c->indel_host_arrays || !have_qsum;   /* device-only needs the sums from the kernel */
+    std::vector<uint8_t> has_ev;
+    lfq_plp_mark_events(evs, region_begin, width, c->indel_all_columns != 0, has_ev);   /* lfq_set_indel_arrays_all_columns */
+    LfqPlpPartCount pc[LFQ_HOST_PARTS + 1] = {};
+    int parts = 1;
+    lfq_for_reads(width, [&](int64_t p0, int64_t p1, int part) { pc[part + 1] = lfq_plp_cols_count(h, has_ev, p0, p1); }, &parts);
+    lfq_plp_cols_alloc(O, pc, parts, have_qsum);
+    lfq_for_reads(width, [&](int64_t p0, int64_t p1, int part) {
+        lfq_plp_cols_fill(R, h, has_ev, region_begin, p0, p1, pc[part], have_qsum, O, col_of.data(), pos_off, col_pos_out);
+    });
+    const int64_t ne_total[2] = {pc[parts].ne[0], pc[parts].ne[1]}, ne_all = ne_total[0] + ne_total[1];
+    if (ne_all > 0 && grow(&c->d_plp_ne, &c->plp_ne_cap, ne_all * 2) != LFQ_OK) {
+        return fail(LFQ_ERR_NOMEM);
+    }
+    if (ne_all > 0) {
+        int16_t *d_ne = c->d_plp_ne;
+        for (int sd = 0; sd < 2 && rc == LFQ_OK; sd++) {
+            uint8_t *d_off = d + o_off + sd * lfq_al(width * 8);
+            A.ne_off[sd] = (const int64_t *)d_off;
+            A.cursor[sd] = (int32_t *)(d + o_cur + sd * lfq_al(width * 4));
+            if (hipMemcpyAsync(d_off, pos_off[sd], (size_t)width * 8, hipMemcpyHostToDevice, ps) != hipSuccess) {
                 rc = LFQ_ERR_HIP;
             }
         }
-        scan_events();
-        /* 4a. the event tables, part by part, while the counter kernel is still on its way (it waits for BI / BD, the end of
-         * the upload): they need the events and the caller's arrays, nothing from the device.  Merged below (4). */
-        struct PartTables {
-            LfqIndelColsOwned::Side side[2];        /* key_off / rd_off: local running totals, no leading 0 */
-            std::vector<int64_t> cols;              /* positions (relative to the region) with events, ascending */
-            std::vector<int64_t> ev_after[2];       /* local event count of each side after each of them */
-            std::vector<int64_t> rd_ev[2];          /* event index of each entry of side[sd].rd_q (for rd_aq, filled last) */
-        };
-        const int n_parts = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<long>(std::max<long>(lfq_knobs().host_loop_threads, 1), LFQ_HOST_PARTS), evs.size() / (size_t)std::max<int64_t>(lfq_knobs().host_par_min / 48, 1)));
-        std::vector<PartTables> pt((size_t)n_parts);
-        std::vector<size_t> cut((size_t)n_parts + 1, evs.size());
-        cut[0] = 0;
-        for (int t = 1; t < n_parts; t++) {
-            size_t k = evs.size() * (size_t)t / (size_t)n_parts;
-            while (k < evs.size() && k > 0 && evs[k].pos == evs[k - 1].pos) {
-                k++;
-            }
-            cut[(size_t)t] = std::max(k, cut[(size_t)t - 1]);
-        }
-        auto build = [&](int t) {
-            PartTables &P = pt[(size_t)t];
-            std::vector<std::string> keys;
-            std::vector<std::vector<size_t>> members;
-            std::string key;
-            size_t ei = cut[(size_t)t];
-            const size_t e_end = cut[(size_t)t + 1];
-            while (ei < e_end) {
-                const int64_t ppos = evs[ei].pos - region_begin;
-                size_t e1 = ei;
-                while (e1 < e_end && evs[e1].pos - region_begin == ppos) {
-                    e1++;
-                }
-                P.cols.push_back(ppos);             /* the position; its column index is known once the counters are back */
-                for (int sd = 0; sd < 2; sd++) {
-                    LfqIndelColsOwned::Side &S = P.side[sd];
-                    keys.clear();                       /* (reused across columns: no allocation in the common case) */
-                    for (auto &m : members) {
-                        m.clear();
-                    }
-                    size_t n_keys = 0;
-                    for (size_t i = ei; i < e1; i++) {
-                        const Ev &e = evs[i];
-                        if ((e.indel > 0) != (sd == 0)) {
-                            continue;
-                        }
-                        key.clear();
-                        if (sd == 0) {                                  /* inserted bases, plp.c:1082-1086 */
-                            const int64_t s0 = rd->seq_off[e.read], lq = rd->seq_off[e.read + 1] - s0;
-                            for (int j = 1; j <= e.indel; j++) {
-                                const int64_t q = e.qpos + j;
-                                const uint8_t code = q < lq ? rd->seq[s0 + q] : 4;
-                                key.push_back(lfq_seq_letter(code));
-                            }
-                        } else {                                        /* deleted reference bases, :1127-1131 */
-                            for (int j = 1; j <= -e.indel; j++) {
-                                const int64_t g = e.pos + j;
-                                key.push_back(g < rd->ref_len ? (char)toupper((unsigned char)rd->ref[g]) : 'N');
-                            }
-                        }
-                        size_t ki = 0;
-                        while (ki < n_keys && keys[ki] != key) {
-                            ki++;
-                        }
-                        if (ki == n_keys) {
-                            keys.push_back(key);
-                            if (members.size() <= n_keys) {
-                                members.emplace_back();
-                            }
-                            n_keys++;
-                        }
-                        members[ki].push_back(i);
-                    }
-                    for (size_t ki = 0; ki < n_keys; ki++) {
-                        int fw = 0, rv = 0;
-                        for (size_t i : members[ki]) {
-                            const Ev &e = evs[i];
-                            const int64_t s0 = rd->seq_off[e.read];
-                            const uint32_t fl = t_fl[e.read];
-                            const uint8_t *qa = sd == 0 ? t_bi : t_bd;
-                            const bool has_q = qa && (fl & (sd == 0 ? 1u : 2u));
-                            if (rs->idq_mode) {
-                                int q[2];
-                                idq_at(e.read, e.qpos, q);
-                                S.rd_q.push_back((int16_t)q[sd]);
-                            } else {
-                                S.rd_q.push_back((int16_t)(has_q ? (int)qa[s0 + e.qpos] - 33 : 0));
-                            }
-                            S.rd_aq.push_back((int16_t)-1);                  /* filled when the BAQ kernels are through */
-                            P.rd_ev[sd].push_back((int64_t)i);
-                            S.rd_mq.push_back((int16_t)rd->mapq[e.read]);
-                            const int32_t sq = t_sq ? t_sq[e.read] : -1;
-                            S.rd_sq.push_back((int16_t)(sq > 32767 ? 32767 : sq));
-                            if (rd->reverse[e.read]) {
-                                rv++;
-                            } else {
-                                fw++;
-                            }
-                        }
-                        S.ev_fw.push_back(fw);
-                        S.ev_rv.push_back(rv);
-                        S.key_chars.insert(S.key_chars.end(), keys[ki].begin(), keys[ki].end());
-                        S.key_off.push_back((int64_t)S.key_chars.size());
-                        S.rd_off.push_back((int64_t)S.rd_q.size());
-                    }
-                    P.ev_after[sd].push_back((int64_t)S.ev_fw.size());
-                }
-                ei = e1;
-            }
-        };
-        {
-            const std::function<void(int)> task = [&](int t) { build(t); };
-            LfqLoopPool &pool = LfqLoopPool::instance();
-            if (n_parts > 1 && pool.try_run(n_parts, task)) {
-                build(0);
-                pool.finish();
-            } else {
-                std::vector<std::thread> th;
-                for (int t = 1; t < n_parts; t++) {
-                    th.emplace_back(build, t);
-                }
-                build(0);
-                for (auto &x : th) {
-                    x.join();
-                }
-            }
-        }
-        /* ... and appended in order (offsets shifted by what came before); per column with events: where its events end on
-         * either side, and the largest quality sum of one of them */
-        struct EvCol { int64_t pos; int64_t ev_after[2]; int64_t best[2]; bool has[2]; };
-        std::vector<EvCol> ecols;
-        std::vector<int64_t> rd_ev[2];
-        for (int sd = 0; sd < 2; sd++) {
-            LfqIndelColsOwned::Side &S = O.side[sd];
-            S.ev_off.push_back(0);
-            S.key_off.push_back(0);
-            S.rd_off.push_back(0);
-        }
-        for (int t = 0; t < n_parts; t++) {
-            PartTables &P = pt[(size_t)t];
-            int64_t ev_base[2], rd_base[2], key_base[2];
-            for (int sd = 0; sd < 2; sd++) {
-                LfqIndelColsOwned::Side &S = O.side[sd];
-                const LfqIndelColsOwned::Side &L = P.side[sd];
-                ev_base[sd] = (int64_t)S.ev_fw.size();
-                rd_base[sd] = (int64_t)S.rd_q.size();
-                key_base[sd] = (int64_t)S.key_chars.size();
-                S.ev_fw.insert(S.ev_fw.end(), L.ev_fw.begin(), L.ev_fw.end());
-                S.ev_rv.insert(S.ev_rv.end(), L.ev_rv.begin(), L.ev_rv.end());
-                S.key_chars.insert(S.key_chars.end(), L.key_chars.begin(), L.key_chars.end());
-                S.rd_q.insert(S.rd_q.end(), L.rd_q.begin(), L.rd_q.end());
-                S.rd_aq.insert(S.rd_aq.end(), L.rd_aq.begin(), L.rd_aq.end());
-                S.rd_mq.insert(S.rd_mq.end(), L.rd_mq.begin(), L.rd_mq.end());
-                S.rd_sq.insert(S.rd_sq.end(), L.rd_sq.begin(), L.rd_sq.end());
-                rd_ev[sd].insert(rd_ev[sd].end(), P.rd_ev[sd].begin(), P.rd_ev[sd].end());
-                for (int64_t v : L.key_off) {
-                    S.key_off.push_back(v + key_base[sd]);
-                }
-                for (int64_t v : L.rd_off) {
-                    S.rd_off.push_back(v + rd_base[sd]);
-                }
-            }
-            for (size_t i = 0; i < P.cols.size(); i++) {
-                EvCol e;
-                e.pos = P.cols[i];
-                for (int sd = 0; sd < 2; sd++) {
-                    const LfqIndelColsOwned::Side &S = O.side[sd];
-                    const int64_t e0 = ecols.empty() ? 0 : ecols.back().ev_after[sd];
-                    e.ev_after[sd] = ev_base[sd] + P.ev_after[sd][i];
-                    e.best[sd] = 0;
-                    e.has[sd] = e.ev_after[sd] > e0;
-                    for (int64_t ev = e0; ev < e.ev_after[sd]; ev++) {
-                        int64_t sum = 0;
-                        for (int64_t k = S.rd_off[(size_t)ev]; k < S.rd_off[(size_t)ev + 1]; k++) {
-                            sum += S.rd_q[(size_t)k];
-                        }
-                        e.best[sd] = std::max(e.best[sd], sum);
-                    }
-                }
-                ecols.push_back(e);
-            }
-        }
-        tm[1] = lfq_now_ms();
-        if (rc == LFQ_OK && hipStreamSynchronize(ps) != hipSuccess) {
-            rc = LFQ_ERR_HIP;
-        }
-        tm[2] = lfq_now_ms();
-        /* 3. columns = covered positions; quality arrays of the reads without an event at the event positions */
-        LfqPin<int64_t> pos_off_ins(c, (size_t)width), pos_off_del(c, (size_t)width);      /* DMA sources: pinned */
-        if (!pos_off_ins.ok() || !pos_off_del.ok()) {
-            rc = LFQ_ERR_NOMEM;
-        }
-        int64_t *const pos_off[2] = {pos_off_ins.data(), pos_off_del.data()};
-        LfqVec<int32_t> col_of;                     /* column index of an event position (-1: none) */
-        int64_t ne_total[2] = {0, 0};
-        const bool host_arrays = c->indel_host_arrays || !have_qsum;   /* device-only needs the sums from the kernel */
+        A.ne_q[0] = d_ne;
+        A.ne_mq[0] = d_ne + ne_total[0];
+        A.ne_q[1] = d_ne + 2 * ne_total[0];
+        A.ne_mq[1] = d_ne + 2 * ne_total[0] + ne_total[1];
         if (rc == LFQ_OK) {
-            col_of.resize((size_t)width);           /* (col_of and pos_off: every position is written by the second pass) */
-            std::vector<uint8_t> has_ev((size_t)width, 0);
-            for (const Ev &e : evs) {
-                has_ev[(size_t)(e.pos - region_begin)] = 1;
-            }
-            if (c->indel_all_columns) {             /* lfq_set_indel_arrays_all_columns: the arrays of every column */
-                std::fill(has_ev.begin(), has_ev.end(), (uint8_t)1);
-            }
-            /* two passes over the positions, both split over a few threads: count the covered positions and the
-             * non-event reads at event positions per part, then every part fills its slice of the column arrays */
-            int64_t part_cov[LFQ_HOST_PARTS + 1] = {0}, part_ne[2][LFQ_HOST_PARTS + 1] = {{0}, {0}};
-            int parts = 1;
-            lfq_for_reads(width, [&](int64_t p0, int64_t p1, int part) {
-                int64_t nc = 0, ne0 = 0, ne1 = 0;
-                for (int64_t p = p0; p < p1; p++) {
-                    if (h[0][(size_t)p] <= 0) {
-                        continue;
-                    }
-                    nc++;
-                    if (has_ev[(size_t)p]) {
-                        ne0 += h[2][(size_t)p] + h[4][(size_t)p];
-                        ne1 += h[2][(size_t)p] + h[3][(size_t)p];
-                    }
-                }
-                part_cov[part + 1] = nc;
-                part_ne[0][part + 1] = ne0;
-                part_ne[1][part + 1] = ne1;
-            }, &parts);
-            for (int q = 0; q < parts; q++) {
-                part_cov[q + 1] += part_cov[q];
-                part_ne[0][q + 1] += part_ne[0][q];
-                part_ne[1][q + 1] += part_ne[1][q];
-            }
-            const size_t n_cov = (size_t)part_cov[parts];
-            ne_total[0] = part_ne[0][parts];
-            ne_total[1] = part_ne[1][parts];
-            for (auto *v : {&O.cov, &O.tails, &O.non_indels, &O.n_ins, &O.n_dels, &O.hrun}) {
-                v->resize(n_cov);
-            }
-            O.ref_base.resize(n_cov);
-            if (have_qsum) {
-                qsum[0].resize(n_cov);
-                qsum[1].resize(n_cov);
-            }
-            for (int sd = 0; sd < 2; sd++) {
-                O.side[sd].non_fw.resize(n_cov);
-                O.side[sd].non_rv.resize(n_cov);
-                O.side[sd].ne_off.resize(n_cov + 1);
-                O.side[sd].ev_off.reserve(n_cov + 1);
-                O.side[sd].ne_off[0] = 0;
-            }
-            lfq_for_reads(width, [&](int64_t p0, int64_t p1, int part) {
-                size_t ci = (size_t)part_cov[part];
-                int64_t run[2] = {part_ne[0][part], part_ne[1][part]};
-                for (int64_t p = p0; p < p1; p++) {
-                    col_of[(size_t)p] = -1;
-                    pos_off[0][(size_t)p] = -1;
-                    pos_off[1][(size_t)p] = -1;
-                    if (h[0][(size_t)p] <= 0) {
-                        continue;
-                    }
-                    const int64_t gp = region_begin + p;
-                    if (col_pos_out) {
-                        col_pos_out[ci] = gp;
-                    }
-                    char rb = (gp < rd->ref_len) ? rd->ref[gp] : 'N';       /* plp.c:818-823 */
-                    if (!(rb == 'A' || rb == 'C' || rb == 'T' || rb == 'G' || rb == 'N')) {
-                        rb = 'N';
-                    }
-                    O.ref_base[ci] = (uint8_t)rb;
-                    O.cov[ci] = h[0][(size_t)p];
-                    O.tails[ci] = h[1][(size_t)p];
-                    O.non_indels[ci] = h[2][(size_t)p];
-                    O.n_ins[ci] = h[3][(size_t)p];
-                    O.n_dels[ci] = h[4][(size_t)p];
-                    int hr = 1;                                             /* get_hrun, plp.c:744-787 */
-                    if (gp + 1 < rd->ref_len) {
-                        const int ch = toupper((unsigned char)rd->ref[gp + 1]);
-                        for (int64_t i = gp + 2; i < rd->ref_len && toupper((unsigned char)rd->ref[i]) == ch; i++) {
-                            hr++;
-                        }
-                        for (int64_t i = gp; i >= 0 && toupper((unsigned char)rd->ref[i]) == ch; i--) {
-                            hr++;
-                        }
-                    }
-                    O.hrun[ci] = hr;
-                    if (have_qsum) {
-                        qsum[0][ci] = h[7][(size_t)p];
-                        qsum[1][ci] = h[8][(size_t)p];
-                    }
-                    const int32_t ne_cnt[2] = {h[2][(size_t)p] + h[4][(size_t)p], h[2][(size_t)p] + h[3][(size_t)p]};
-                    const int32_t fw[2] = {h[5][(size_t)p], h[6][(size_t)p]};
-                    for (int sd = 0; sd < 2; sd++) {
-                        O.side[sd].non_fw[ci] = fw[sd];
-                        O.side[sd].non_rv[ci] = ne_cnt[sd] - fw[sd];
-                        if (has_ev[(size_t)p]) {
-                            pos_off[sd][(size_t)p] = run[sd];
-                            run[sd] += ne_cnt[sd];
-                            col_of[(size_t)p] = (int32_t)ci;
-                        }
-                        O.side[sd].ne_off[ci + 1] = run[sd];
-                    }
-                    ci++;
-                }
-            });
-            const int64_t ne_all = ne_total[0] + ne_total[1];
-            if (ne_all > 0 && grow(&c->d_plp_ne, &c->plp_ne_cap, ne_all * 2) != LFQ_OK) {
-                rc = LFQ_ERR_NOMEM;
-            }
-            d_ne = c->d_plp_ne;
-            if (rc == LFQ_OK && ne_all > 0) {
-                for (int sd = 0; sd < 2; sd++) {
-                    up(o_off + sd * lfq_al(width * 8), pos_off[sd], width * 8);
-                    A.ne_off[sd] = (const int64_t *)(d + o_off + sd * lfq_al(width * 8));
-                    A.cursor[sd] = (int32_t *)(d + o_cur + sd * lfq_al(width * 4));
-                }
-                A.ne_q[0] = d_ne;
-                A.ne_mq[0] = d_ne + ne_total[0];
-                A.ne_q[1] = d_ne + 2 * ne_total[0];
-                A.ne_mq[1] = d_ne + 2 * ne_total[0] + ne_total[1];
-                if (rc == LFQ_OK) {
-                    rc = A.pmax_end ? lfq_launch_plp_indel_columns(A, 1, ps) : lfq_launch_plp_indel(A, 1, ps);
-                }
-                for (int sd = 0; sd < 2 && rc == LFQ_OK && host_arrays; sd++) {
-                    O.side[sd].ne_q.resize((size_t)ne_total[sd]);
-                    O.side[sd].ne_mq.resize((size_t)ne_total[sd]);
-                    if (ne_total[sd] > 0
-                        && (hipMemcpyAsync(O.side[sd].ne_q.data(), A.ne_q[sd], (size_t)ne_total[sd] * 2, hipMemcpyDeviceToHost, ps) != hipSuccess
-                            || hipMemcpyAsync(O.side[sd].ne_mq.data(), A.ne_mq[sd], (size_t)ne_total[sd] * 2, hipMemcpyDeviceToHost, ps) != hipSuccess)) {
-                        rc = LFQ_ERR_HIP;
-                    }
-                }
-                /* (waited for behind the event tables below) */
-            }
+            rc = A.pmax_end ? lfq_launch_plp_indel_columns(A, 1, ps) : lfq_launch_plp_indel(A, 1, ps);
         }
-        tm[3] = lfq_now_ms();
-        /* ai / ad of the event reads when lfq_readset_baq left them on the device: the gather is queued behind the BAQ
-         * kernels on their stream and lands in pinned memory; nothing waits for it until the event tables and the consensus
-         * flags -- which need neither ai / ad nor the tag bits of the reads -- are built (that host work used to start
-         * when the last BAQ kernel had ended: 7 ms of an idle GPU per region). */
-        LfqPin<int64_t> idx(c, evs.size());
-        LfqPin<uint8_t> g_pin(c, 2 * evs.size());
-        const bool gather_aq = rc == LFQ_OK && rs->has_idaq && !evs.empty();
-        if (gather_aq) {
-            LFQ_PIN_OK(idx);
-            LFQ_PIN_OK(g_pin);
-            for (size_t i = 0; i < evs.size(); i++) {
-                idx[i] = rd->seq_off[evs[i].read] + evs[i].qpos;
-            }
-            const int64_t ne = (int64_t)evs.size();
-            if (grow(&c->d_tmp[2], &c->tmp_bytes[2], ne * 10) != LFQ_OK) {
-                rc = LFQ_ERR_NOMEM;
-            } else {
-                uint8_t *dg = c->d_tmp[2];
-                if (hipMemcpyAsync(dg, idx.data(), (size_t)ne * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess
-                    || lfq_launch_gather2(rs->d_ai, rs->d_ad, (const int64_t *)dg, ne, dg + ne * 8, dg + ne * 9, c->stream) != LFQ_OK
-                    || hipMemcpyAsync(g_pin.data(), dg + ne * 8, (size_t)ne * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
-                    rc = LFQ_ERR_HIP;
-                }
-                g_ai = g_pin.data();
-                g_ad = g_pin.data() + ne;
+        for (int sd = 0; sd < 2 && rc == LFQ_OK && host_arrays; sd++) {
+            O.side[sd].ne_q.resize((size_t)ne_total[sd]);
+            O.side[sd].ne_mq.resize((size_t)ne_total[sd]);
+            if (ne_total[sd] > 0
+                && (hipMemcpyAsync(O.side[sd].ne_q.data(), A.ne_q[sd], (size_t)ne_total[sd] * 2, hipMemcpyDeviceToHost, ps) != hipSuccess
+                    || hipMemcpyAsync(O.side[sd].ne_mq.data(), A.ne_mq[sd], (size_t)ne_total[sd] * 2, hipMemcpyDeviceToHost, ps) != hipSuccess)) {
+                rc = LFQ_ERR_HIP;
             }
         }
         if (rc != LFQ_OK) {
-            (void)hipStreamSynchronize(ps);
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
+            return fail(rc);
         }
-        /* the quality arrays stay resident (c->d_plp_ne): lfq_call_indels_batch builds its pseudo-columns from them on the device */
-        c->plp_ne_total[0] = ne_total[0];
-        c->plp_ne_total[1] = ne_total[1];
-        tm[4] = lfq_now_ms();
-        /* 4. event tables: per column and side, events in order of first appearance (uthash iterates in insertion
-         * order), their reads in pileup order (add_ins_sequence / add_del_sequence, utils.c) */
-        /* Columns with events are few and independent of one another: the event list is cut at position boundaries into a
-         * few parts, every part builds the tables of its columns on its own thread, and the parts are appended in order
-         * (offsets shifted by what came before; the ev_off entries of the event-less columns in between are range fills). */
-        const int64_t ncols = (int64_t)O.cov.size();
-        /* the running event counts per column (the event-less columns repeat the count before them), and the consensus
-         * flags of the columns with events: the largest quality sum of one event against the sum over the reads without an
-         * event of that side (plp.c:1236-1270) -- the former collected at merge time, the latter from the counter kernel */
-        int64_t col_done = 0;                       /* columns [0, col_done) have their ev_off entries */
-        if (have_qsum) {
-            O.cons_indel.assign((size_t)ncols, 0);
+        /* (waited for behind the event tables below) */
+    }
+    tm[3] = lfq_now_ms();
+    /* ai / ad of the event reads when lfq_readset_baq left them on the device: the gather is queued behind the BAQ
+     * kernels on their stream and lands in pinned memory; nothing waits for it until the ev_off entries and the consensus
+     * flags -- which need neither ai / ad nor the tag bits of the reads -- are there (that host work used to start
+     * when the last BAQ kernel had ended: 7 ms of an idle GPU per region). */
+    LfqPin<int64_t> idx(c, evs.size());
+    LfqPin<uint8_t> g_pin(c, 2 * evs.size());
+    const bool gather_aq = rs->has_idaq && !evs.empty();
+    if (gather_aq) {
+        const int64_t ne = (int64_t)evs.size();
+        if (!idx.ok() || !g_pin.ok() || grow(&c->d_tmp[2], &c->tmp_bytes[2], ne * 10) != LFQ_OK) {
+            return fail(LFQ_ERR_NOMEM);
         }
-        for (const EvCol &e : ecols) {
-            const int64_t col = col_of[(size_t)e.pos];
-            if (col < 0) {                          /* (cannot happen: a read with an event covers its position) */
-                (void)hipStreamSynchronize(ps);     /* the pinned blocks of this call may still be a copy's source or target */
-                (void)hipStreamSynchronize(c->stream);
-                return LFQ_ERR_INVALID;
-            }
-            for (int sd = 0; sd < 2; sd++) {
-                LfqIndelColsOwned::Side &S = O.side[sd];
-                S.ev_off.insert(S.ev_off.end(), (size_t)(col - col_done), S.ev_off.back());
-                S.ev_off.push_back(e.ev_after[sd]);
-                if (have_qsum && e.has[sd] && e.best[sd] > (int64_t)qsum[sd][(size_t)col]) {
-                    O.cons_indel[(size_t)col] = 1;
-                }
-            }
-            col_done = col + 1;
+        lfq_plp_gather_index(R, evs, idx.data());
+        uint8_t *dg = c->d_tmp[2];
+        if (hipMemcpyAsync(dg, idx.data(), (size_t)ne * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess
+            || lfq_launch_gather2(rs->d_ai, rs->d_ad, (const int64_t *)dg, ne, dg + ne * 8, dg + ne * 9, c->stream) != LFQ_OK
+            || hipMemcpyAsync(g_pin.data(), dg + ne * 8, (size_t)ne * 2, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+            return fail(LFQ_ERR_HIP);
         }
-        for (int sd = 0; sd < 2; sd++) {            /* the event-less columns behind the last event */
-            O.side[sd].ev_off.insert(O.side[sd].ev_off.end(), (size_t)(ncols - col_done), O.side[sd].ev_off.back());
-        }
-        /* 4b. the scatter pass, the BAQ kernels and the gather behind them: the alignment qualities of the event reads
-         * (plp.c:1069-1073, 1113-1117); from here on the ai / ad bits of rs->fl (t_fl) are valid */
-        if (hipStreamSynchronize(ps) != hipSuccess || (gather_aq && hipStreamSynchronize(c->stream) != hipSuccess)
-            || readset_baq_wait(rs) != LFQ_OK) {
-            return LFQ_ERR_HIP;
-        }
-        for (int sd = 0; sd < 2; sd++) {
-            LfqIndelColsOwned::Side &S = O.side[sd];
-            const uint8_t *aa = sd == 0 ? t_ai : t_ad, *ga = sd == 0 ? g_ai : g_ad;
-            for (size_t j = 0; j < rd_ev[sd].size(); j++) {
-                const Ev &e = evs[(size_t)rd_ev[sd][j]];
-                if (!(t_fl[e.read] & (sd == 0 ? 4u : 8u))) {
-                    continue;                           /* no ai / ad tag on this read: -1 */
-                }
-                if (ga) {
-                    S.rd_aq[j] = (int16_t)((int)ga[(size_t)rd_ev[sd][j]] - 33);
-                } else if (aa) {
-                    S.rd_aq[j] = (int16_t)((int)aa[rd->seq_off[e.read] + e.qpos] - 33);
-                }
-            }
-        }
-        if (!have_qsum) {
-            consensus();
-        }
+    }
+    /* the quality arrays stay resident (c->d_plp_ne): lfq_call_indels_batch builds its pseudo-columns from them on the device */
+    c->plp_ne_total[0] = ne_total[0];
+    c->plp_ne_total[1] = ne_total[1];
+    tm[4] = lfq_now_ms();
+    /* 4. the running event counts per column, and the consensus flags where the counter kernel summed the non-event
+     * qualities: while the scatter pass, the BAQ kernels and the gather run */
+    if (!lfq_plp_fill_ev_off(T, col_of.data(), O)) {
+        return fail(LFQ_ERR_INVALID);
+    }
+    if (have_qsum) {
+        lfq_plp_cons_flags(T, col_of.data(), true, O);
+    }
+    /* 4b. the scatter pass, the BAQ kernels and the gather behind them: the alignment qualities of the event reads; from here
+     * on the ai / ad bits of rs->fl (R.fl) are valid */
+    if (hipStreamSynchronize(ps) != hipSuccess || (gather_aq && hipStreamSynchronize(c->stream) != hipSuccess)
+        || readset_baq_wait(rs) != LFQ_OK) {
+        return LFQ_ERR_HIP;
+    }
+    lfq_plp_fill_rd_aq(R, evs, T, gather_aq ? g_pin.data() : nullptr, gather_aq ? g_pin.data() + evs.size() : nullptr, O);
+    if (!have_qsum) {
+        lfq_plp_cons_flags(T, col_of.data(), false, O);     /* ... else over the quality arrays the scatter pass brought back */
     }
     tm[5] = lfq_now_ms();
-    tm[6] = lfq_now_ms();
     if (lfq_timing_on) {
-        fprintf(stderr, "[lfq timing] indel pileup: counters queued + events %.1f  wait %.1f  columns + scatter queued %.1f  gather queued %.1f  tables + consensus + wait + ai / ad %.1f  - %.1f ms\n",
-                tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], tm[5] - tm[4], tm[6] - tm[5]);
+        fprintf(stderr, "[lfq timing] indel pileup: counters queued + events %.1f  wait %.1f  columns + scatter queued %.1f  gather queued %.1f  tables + consensus + wait + ai / ad %.1f ms\n",
+                tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], tm[5] - tm[4]);
     }
-    /* 6. publish */
-    lfq_indel_columns &C = O.cols;
-    O.ne_qsum[0].swap(qsum[0]);             /* kept for lfq_readset_plp_summary (the key of a consensus indel) */
-    O.ne_qsum[1].swap(qsum[1]);
-    C.cons_indel = O.cons_indel.data();
-    C.ncols = (int64_t)O.cov.size();
-    C.ref_base = O.ref_base.data();
-    C.coverage_plp = O.cov.data();
-    C.num_tails = O.tails.data();
-    C.num_non_indels = O.non_indels.data();
-    C.num_ins = O.n_ins.data();
-    C.num_dels = O.n_dels.data();
-    C.hrun = O.hrun.data();
-    for (int sd = 0; sd < 2; sd++) {
-        LfqIndelColsOwned::Side &S = O.side[sd];
-        S.key_chars.push_back('\0');
-        lfq_indel_side &T = C.side[sd];
-        T.non_fw = S.non_fw.data();
-        T.non_rv = S.non_rv.data();
-        T.ne_off = S.ne_off.data();
-        T.ne_q = S.ne_q.empty() && S.ne_off.back() > 0 ? nullptr : S.ne_q.data();       /* device-only: lfq_set_indel_arrays_on_host */
-        T.ne_mq = S.ne_mq.empty() && S.ne_off.back() > 0 ? nullptr : S.ne_mq.data();
-        T.ev_off = S.ev_off.data();
-        T.key_off = S.key_off.data();
-        T.key_chars = S.key_chars.data();
-        T.ev_fw = S.ev_fw.data();
-        T.ev_rv = S.ev_rv.data();
-        T.rd_off = S.rd_off.data();
-        T.rd_q = S.rd_q.data();
-        T.rd_aq = S.rd_aq.data();
-        T.rd_mq = S.rd_mq.data();
-        T.rd_sq = S.rd_sq.data();
-    }
+    lfq_plp_publish(O);         /* 6. (O.ne_qsum stays for lfq_readset_plp_summary: the key of a consensus indel) */
     return LFQ_OK;
 }
 
@@ -2777,24 +2303,10 @@ int lfq_readset_plp_summary(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, i
     S.hrun.assign(ic->hrun, ic->hrun + ncols);
     S.cov.assign(ic->coverage_plp, ic->coverage_plp + ncols);
     for (int64_t col = 0; col < ncols; col++) {
-        /* consensus indel, plp.c:1231-1268 */
-        int64_t best_ev[2] = {-1, -1};
+        int64_t best_ev[2];                                         /* consensus indel, plp.c:1231-1268 */
         for (int sd = 0; sd < 2; sd++) {
             const lfq_indel_side &T = ic->side[sd];
-            int64_t best = 0;
-            for (int64_t e = T.ev_off[col]; e < T.ev_off[col + 1]; e++) {
-                int64_t sum = 0;                                    /* cons_quals, utils.c:569, 629 */
-                for (int64_t i = T.rd_off[e]; i < T.rd_off[e + 1]; i++) {
-                    sum += T.rd_q[i];
-                }
-                if (sum > best) {
-                    best = sum;
-                    best_ev[sd] = e;
-                }
-            }
-            if (best_ev[sd] >= 0 && !(best > (int64_t)O.ne_qsum[sd][(size_t)col])) {
-                best_ev[sd] = -1;
-            }
+            best_ev[sd] = lfq_plp_cons_event(T.ev_off, T.rd_off, T.rd_q, col, O.ne_qsum[sd][(size_t)col]);
         }
         const int sd = best_ev[0] >= 0 ? 0 : (best_ev[1] >= 0 ? 1 : -1);
         if (sd >= 0) {

@@ -49,7 +49,8 @@ extern "C" {
 /* (10 still: lfq_readset_create_from_bam_tags, lfq_readset_fetch_stored_tags, lfq_readset_baq_fill, lfq_last_baq_fill_stats likewise.) */
 /* (10 still: lfq_readset_encode_bam, lfq_last_bam_encode_times are new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_bgzf_inflate, lfq_last_bgzf_times, lfq_bam_scan_records and its helpers, lfq_readset_create_from_bgzf likewise.) */
-/* (10 still: lfq_bgzf_deflate, lfq_last_bgzf_deflate_times, lfq_bam_frame_encoded are new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_bgzf_deflate, lfq_last_bgzf_deflate_times, lfq_bam_frame_encoded, and the lfq_bam_index_* / lfq_bam_record_* functions are
+ * new functions with new structs; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -902,6 +903,69 @@ typedef struct lfq_bgzf_deflate_times {
     int n_launches, n_from_device;
 } lfq_bgzf_deflate_times;
 int lfq_last_bgzf_deflate_times(lfq_ctx *ctx, lfq_bgzf_deflate_times *t);
+
+/* --- the index of a BAM: its .bai built on the device, written, read and queried ---------------------------------------------------
+ * lfq_bam_index_build makes the index of the records body[rec_off[j] .. rec_off[j + 1]), j < n_recs, that lie in BGZF blocks whose
+ * tables are data_off / comp_off ([n_blocks + 1] each, as lfq_bgzf_deflated and lfq_bgzf_result give them): block b holds bytes
+ * [data_off[b], data_off[b + 1]) of body and starts at byte comp_off[b] + file_off of the file -- file_off lets the caller put the
+ * header's blocks in front.  rec_off and data_off count bytes of body; the records need not start at data_off[0] (a header inside
+ * the first blocks).  n_ref: the references of the file's header.
+ * The index is the one `lofreq index` of the reference's 2.1.4 binary writes, bin for bin and chunk for chunk: INTEGRATION.md
+ * section 13 states the seven rules and tests/golden/bai_binary.json holds them to the binary.  Work proportional to the records
+ * runs on the device (lofreq_amd/csrc/lfq_bamidx.hip), the merging of bins and the fill of the linear index on the host; device
+ * memory is O(records + blocks).
+ * `body` (the records' bytes) may lie inside the context's live lfq_bam_frame_encoded result or its live lfq_bgzf_inflate result:
+ * the records are then taken from the device copy (n_from_device = 1); otherwise they go down once, through a pinned staging area
+ * if the memory is pageable.  No other result of the context is invalidated: frame, encode, inflate and deflate results stay live.
+ * LFQ_ERR_INVALID with *out = NULL.  Before a device is touched: a NULL argument, a negative count or file_off; rec_off or
+ * comp_off not strictly increasing, data_off decreasing; [rec_off[0], rec_off[n_recs]) outside [data_off[0], data_off[n_blocks]]
+ * or outside [0, n_bytes).  From the record pass, which reports the FIRST such record in lfq_bam_index_times.first_bad_record:
+ * a record whose block_size + 4 is not rec_off[j + 1] - rec_off[j], or is below 36; l_read_name + 4 n_cigar_op above what is
+ * left of it; refID >= n_ref or < -1; with refID >= 0, pos < -1 or an end above 2^29; records not sorted -- a refID >= 0 behind a
+ * larger one or behind a refID < 0, or pos going down inside a reference.
+ * n_recs == 0: LFQ_OK, an index of n_ref empty references, nothing launched.
+ * *out is the CALLER'S, a host object with no tie to the context: free it with lfq_bam_index_free.  Blocks. */
+typedef struct lfq_bam_index lfq_bam_index;
+int lfq_bam_index_build(lfq_ctx *ctx, const uint8_t *body, int64_t n_bytes, const int64_t *rec_off, int64_t n_recs,
+                        const int64_t *data_off, const int64_t *comp_off, int64_t n_blocks, int64_t file_off, int32_t n_ref,
+                        lfq_bam_index **out);
+/* the context's last lfq_bam_index_build: records and tables down, the four kernels, the lists back -- on the device's clock --
+ * and the host's finishing pass on the wall clock; first_bad_record: -1, or the record LFQ_ERR_INVALID was returned for */
+typedef struct lfq_bam_index_times {
+    double upload_ms, kernels_ms, download_ms, host_ms;
+    int64_t n_recs, n_chunks, n_intervals, first_bad_record;
+    int n_launches, n_from_device;
+} lfq_bam_index_times;
+int lfq_last_bam_index_times(lfq_ctx *ctx, lfq_bam_index_times *t);
+/* Host only, no context.  The .bai: "BAI\1", n_ref; per reference n_bin, the bins in ascending number with 37450 last (bin,
+ * n_chunk, chunks), n_intv, the offsets; n_no_coor.  *bai is idx's, valid until lfq_bam_index_free.  The binary writes the same
+ * bins in its hash table's order: compare parsed files, not bytes. */
+int lfq_bam_index_bytes(const lfq_bam_index *idx, const uint8_t **bai, int64_t *n_bytes);
+/* any writer's .bai: bins in any order, the trailing n_no_coor optional.  LFQ_ERR_INVALID (*out = NULL): a NULL argument, no
+ * magic, a count that runs past n_bytes, a bin twice in a reference, a bin above 37450, a pseudo-bin without exactly two
+ * chunks, bytes left over. */
+int lfq_bam_index_parse(const uint8_t *bai, int64_t n_bytes, lfq_bam_index **out);
+/* the chunks of the file that hold every mapped record of reference tid overlapping [beg, end) (0-based, half-open): those of
+ * the bins reg2bins(beg, end) names that end above the linear index's value for beg >> 14 (0 past n_intv), begun no earlier than
+ * that value, sorted by begin, overlapping or touching ones merged.  The exact list is the library's own; its contract is that
+ * every such record starts inside one of the chunks, that the chunks are sorted and disjoint and that none begins in front of the
+ * linear value.  (A placed unmapped read is in its bin but not in the linear index, as in the binary: no query promises it.)  A
+ * reference without records or an empty region: n_chunks = 0, LFQ_OK.  LFQ_ERR_INVALID: a NULL argument, tid outside
+ * [0, n_ref).  The arrays are idx's, valid until its next query (an index is not to be queried from two threads at once). */
+int lfq_bam_index_query(const lfq_bam_index *idx, int32_t tid, int64_t beg, int64_t end, const uint64_t **chunk_beg,
+                        const uint64_t **chunk_end, int64_t *n_chunks);
+void lfq_bam_index_free(lfq_bam_index *idx);
+/* Host only: the two loops a writer runs between lfq_bam_frame_encoded / its own records and lfq_bgzf_deflate.
+ * lfq_bam_record_chain: the offsets of EVERY complete record of bam[first .. stop), none filtered (lfq_bam_scan_records filters):
+ * rec_off[n_recs] is where the first incomplete record starts.  LFQ_ERR_INVALID: a NULL argument, first < 0, stop < first, a
+ * block_size below 32.
+ * lfq_bam_record_cuts: the cuts_or_null of lfq_bgzf_deflate for pieces of at most max_piece bytes of [rec_off[0],
+ * rec_off[n_recs]), greedy: each cut is the last record boundary that keeps the piece that long; a record longer than max_piece
+ * is cut every max_piece bytes.  LFQ_ERR_INVALID: a NULL argument, n_recs < 0, max_piece <= 0, rec_off not increasing. */
+int lfq_bam_record_chain(const uint8_t *bam, int64_t first, int64_t stop, int64_t **rec_off, int64_t *n_recs);
+void lfq_bam_record_chain_free(int64_t *rec_off);
+int lfq_bam_record_cuts(const int64_t *rec_off, int64_t n_recs, int64_t max_piece, int64_t **cuts, int64_t *n_cuts);
+void lfq_bam_record_cuts_free(int64_t *cuts);
 
 /* --- source quality: the per-read pre-step of `lofreq call -s` -------------------------
  * source_qual (plp.c:427-593) over count_cigar_ops (samutils.c:437-614) for a batch of reads of one contig (same

@@ -20,6 +20,7 @@ from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_ind
                      format_plp_summary, last_bam_decode_times, last_bam_encode_times, last_baq_fill_stats, last_plp_quals_times, pileup_indel_columns, pileup_snv_tracks, plp_quals,
                      skip_snv_columns, BgzfError, bam_scan_records, bgzf_inflate, last_bgzf_times,
                      bam_frame_encoded, bgzf_deflate, last_bgzf_deflate_times)
+from .bamindex import BamIndex, BamIndexError, bam_index_build, bam_record_chain, bam_record_cuts, last_bam_index_times
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
 
@@ -37,4 +38,5 @@ __all__ = [
     "LFQ_BAM_READ_LB", "LFQ_BAM_READ_IDAQ", "last_baq_fill_stats",
     "bgzf_inflate", "BgzfError", "bam_scan_records", "last_bgzf_times",
     "bgzf_deflate", "last_bgzf_deflate_times", "bam_frame_encoded", "LFQ_BGZF_PUT_EOF",
+    "BamIndex", "BamIndexError", "bam_index_build", "last_bam_index_times", "bam_record_chain", "bam_record_cuts",
 ]

@@ -196,6 +196,13 @@ class BamFramed(C.Structure):
 LFQ_BGZF_PUT_EOF = 1
 
 
+class BamIndexTimes(C.Structure):
+    """lfq_bam_index_times"""
+    _fields_ = [("upload_ms", C.c_double), ("kernels_ms", C.c_double), ("download_ms", C.c_double), ("host_ms", C.c_double),
+                ("n_recs", C.c_int64), ("n_chunks", C.c_int64), ("n_intervals", C.c_int64), ("first_bad_record", C.c_int64),
+                ("n_launches", C.c_int), ("n_from_device", C.c_int)]
+
+
 class BamScanOpts(C.Structure):
     """lfq_bam_scan_opts"""
     _fields_ = [("tid", C.c_int32), ("beg", C.c_int64), ("end", C.c_int64), ("min_mq", C.c_int), ("max_mq", C.c_int),
@@ -273,6 +280,8 @@ EXPORTS = [
     "lfq_bgzf_inflate", "lfq_last_bgzf_times", "lfq_bam_scan_opts_init", "lfq_bam_scan_records", "lfq_bam_scan_free",
     "lfq_readset_create_from_bgzf", "lfq_readset_create_from_bam_scan",
     "lfq_bgzf_deflate", "lfq_last_bgzf_deflate_times", "lfq_bam_frame_encoded",
+    "lfq_bam_index_build", "lfq_last_bam_index_times", "lfq_bam_index_bytes", "lfq_bam_index_parse", "lfq_bam_index_query",
+    "lfq_bam_index_free", "lfq_bam_record_chain", "lfq_bam_record_chain_free", "lfq_bam_record_cuts", "lfq_bam_record_cuts_free",
     "lfq_readset_pileup_sites", "lfq_readset_uniq", "lfq_last_sites_times",
     "lfq_readset_plp_summary", "lfq_format_plp_summary", "lfq_last_summary_times",
     "lfq_plp_quals_from_tracks", "lfq_format_plp_quals", "lfq_set_indel_arrays_all_columns", "lfq_format_plp_indel_quals",
@@ -417,6 +426,19 @@ def load():
     L.lfq_bgzf_deflate.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_uint, C.POINTER(C.POINTER(BgzfDeflated))]
     L.lfq_last_bgzf_deflate_times.argtypes = [vp, C.POINTER(BgzfDeflateTimes)]
     L.lfq_bam_frame_encoded.argtypes = [vp, vp, C.c_int64, C.POINTER(C.POINTER(BamFramed))]
+    L.lfq_bam_index_build.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(vp)]
+    L.lfq_last_bam_index_times.argtypes = [vp, C.POINTER(BamIndexTimes)]
+    L.lfq_bam_index_bytes.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_bam_index_parse.argtypes = [vp, C.c_int64, C.POINTER(vp)]
+    L.lfq_bam_index_query.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_bam_index_free.argtypes = [vp]
+    L.lfq_bam_index_free.restype = None
+    L.lfq_bam_record_chain.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_int64)]
+    L.lfq_bam_record_chain_free.argtypes = [C.POINTER(C.c_int64)]
+    L.lfq_bam_record_chain_free.restype = None
+    L.lfq_bam_record_cuts.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_int64)]
+    L.lfq_bam_record_cuts_free.argtypes = [C.POINTER(C.c_int64)]
+    L.lfq_bam_record_cuts_free.restype = None
     L.lfq_bam_scan_opts_init.argtypes = [C.POINTER(BamScanOpts)]
     L.lfq_bam_scan_opts_init.restype = None
     L.lfq_bam_scan_records.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(BamScanOpts), C.POINTER(C.POINTER(BamScan))]

@@ -503,6 +503,7 @@ void lfq_destroy(lfq_ctx *c)
         lfq_bam_release(c);
         lfq_bgzf_release(c);
         lfq_bgzf_deflate_release(c);
+        lfq_bam_index_release(c);
         if (c->h_tuples) (void)hipHostFree(c->h_tuples);
         if (c->h_nheavy) (void)hipHostFree(c->h_nheavy);
         if (c->ev_heavy) (void)hipEventDestroy(c->ev_heavy);

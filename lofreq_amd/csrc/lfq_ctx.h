@@ -10,6 +10,7 @@
  *   lfq_bamrec.hip     BAM records decoded and rewritten on the device: kernels and their launches (for lfq_readset.hip)
  *   lfq_bgzf.hip       BGZF blocks inflated on the device (over lfq_inflate.h), the record scan, lfq_readset_create_from_bgzf
  *   lfq_bgzf_deflate.hip   bytes cut into BGZF blocks and compressed on the device (over lfq_deflate.h)
+ *   lfq_bamidx.hip         the .bai of a BAM from its records and block tables (over lfq_bamidx.h)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -416,6 +417,7 @@ struct lfq_ctx {
     struct LfqBamState *bam;         /* lfq_readset_create_from_bam / _encode_bam: records, descriptors, results and timing (lfq_bamrec.hip; created on first use) */
     struct LfqBgzfState *bgzf;       /* lfq_bgzf_inflate: its buffers, result and timing (lfq_bgzf.hip; created on first use) */
     struct LfqBgzfDefState *bgzf_def; /* lfq_bgzf_deflate: likewise (lfq_bgzf_deflate.hip) */
+    struct LfqBamIdxState *bamidx;   /* lfq_bam_index_build: likewise (lfq_bamidx.hip) */
 };
 
 template <typename T>
@@ -584,6 +586,7 @@ const uint8_t *lfq_bgzf_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 const uint8_t *lfq_bgzf_resident_bytes(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 const uint8_t *lfq_bam_framed_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 void lfq_bgzf_deflate_release(lfq_ctx *c);
+void lfq_bam_index_release(lfq_ctx *c);    /* lfq_bamidx.hip: what lfq_destroy frees of lfq_ctx::bamidx */
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

@@ -51,6 +51,7 @@ extern "C" {
 /* (10 still: lfq_bgzf_inflate, lfq_last_bgzf_times, lfq_bam_scan_records and its helpers, lfq_readset_create_from_bgzf likewise.) */
 /* (10 still: lfq_bgzf_deflate, lfq_last_bgzf_deflate_times, lfq_bam_frame_encoded, and the lfq_bam_index_* / lfq_bam_record_* functions are
  * new functions with new structs; no existing layout changed.) */
+/* (10 still: lfq_bed_parse and the other lfq_bed_* functions, lfq_set_bed are new functions with a new opaque type; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -527,7 +528,9 @@ int lfq_readset_pileup_indels(lfq_ctx *ctx, lfq_readset *rs, int64_t region_begi
                               const lfq_indel_columns **cols_out, int64_t *col_pos_out);
 /* The reads the pileups of this read set take under the context's current lfq_set_max_depth: keep_out_or_null[r] = 1 for a
  * kept read, 0 for a dropped one; *n_kept_out_or_null = how many are kept (every read without a cap).  Decided once per read
- * set and cap value, on the host, and shared by both pileups.  LFQ_ERR_INVALID for unsorted reads under a cap. */
+ * set and cap value, on the host, and shared by both pileups.  LFQ_ERR_INVALID for unsorted reads under a cap.  A read set
+ * created under targets (lfq_set_bed) reports targets and cap together: the reads the BED keeps, and of those the ones the
+ * cap keeps (BED first); with targets alone unsorted reads are fine. */
 int lfq_readset_kept_reads(lfq_ctx *ctx, lfq_readset *rs, uint8_t *keep_out_or_null, int64_t *n_kept_out_or_null);
 /* copies of the resident tags for writing them back to the BAM; NULL = not wanted.  tag_flags as lfq_baq_idaq_batch */
 int lfq_readset_fetch_tags(lfq_ctx *ctx, lfq_readset *rs, uint8_t *lb_out, uint8_t *ai_out, uint8_t *ad_out,
@@ -791,8 +794,9 @@ int lfq_last_bgzf_times(lfq_ctx *ctx, lfq_bgzf_times *t);
 /* The records of inflated BAM bytes, located and filtered as sam_itr_next + mplp_func (plp.c:606-722) keep them.  Host only, no
  * context.  bam[first .. stop) is a chain of records as they lie in the file: block_size (int32) and that many bytes, of which the
  * first 32 are the core (refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq, next_refID, next_pos, tlen).  `first` points
- * behind the file's header (magic, text, references), which stays the caller's, as do BED overlap (the caller owns the BED: it
- * drops entries from the arrays) and MPLP_ILLUMINA13.
+ * behind the file's header (magic, text, references), which stays the caller's, as does MPLP_ILLUMINA13.  BED overlap is not
+ * this scan's either: the read set made from the records applies the context's targets (lfq_set_bed), masking reads, not removing
+ * records.
  * A record is kept when, in this order:
  *   refID >= 0, and refID == tid when tid >= 0;
  *   !(flag & flag_mask)                                             (unmapped, secondary, QC fail, duplicate: plp.c:613-624);
@@ -1028,6 +1032,49 @@ int lfq_set_pileup_unsorted(lfq_ctx *ctx, int on);
 #define LFQ_NO_MAX_DEPTH (-1)
 int lfq_set_max_depth(lfq_ctx *ctx, int64_t max_depth);
 int lfq_pack_nt_track(const uint8_t *nt_bytes, int64_t n_obs, uint8_t *packed_out);
+
+/* ---- -l / --bed of `lofreq call`: the targets (bedidx.c) ------------------------------------------------------------------------
+ * lfq_bed_parse reads BED text that is already decompressed (gzip stays with the caller) by the rules of bed_read, line by line:
+ *   - an EMPTY line ends the text silently, everything behind it is ignored (the reference's read loop stops at a line of length
+ *     0); a line of blanks only and a line whose first non-blank is '#' are skipped; a trailing '\r' is a blank;
+ *   - leading blanks are stripped, the name runs to the next blank, the rest is sscanf("%u %u"): two numbers are the BED interval
+ *     [beg, end), one number is the 1-based position list format, [p - 1, p) ("c1 100 rs5" and "c1 100.5 102" are position 100; a
+ *     leading '+' is accepted);
+ *   - refused, with the whole text (LFQ_ERR_INVALID, *bad_line_or_null = the 1-based line): no number, unless the name is `browser`
+ *     or `track` (skipped); end < beg after the conversion ("c1 0" of the list format, "c1 -5 7"); and, a departure from the
+ *     reference, which compares such values as negative ints: a value above INT32_MAX;
+ *   - beg == end is accepted; the lines of one name are pooled wherever they stand; duplicates and overlaps are kept.
+ * The table of a name is sorted by (beg, end).  lfq_bed_overlap is bed_overlap's predicate: 1 iff some interval of the name has
+ * end_i > beg and beg_i < end, 0 for a name the BED does not hold.  A zero-length interval [x, x) therefore matches a read with
+ * pos < x < endpos and never a column.  No context, no device. */
+typedef struct lfq_bed lfq_bed;
+int lfq_bed_parse(const char *text, int64_t n_bytes, lfq_bed **bed_out, int64_t *bad_line_or_null);
+void lfq_bed_free(lfq_bed *bed);
+int64_t lfq_bed_n_names(const lfq_bed *bed);
+const char *lfq_bed_name(const lfq_bed *bed, int64_t i);          /* in order of first appearance; NULL outside [0, n_names) */
+/* the intervals of `name` in sorted order: *beg_out / *end_out point into the BED (valid until lfq_bed_free), *n_out = how many;
+ * a name the BED does not hold: LFQ_OK, *n_out = 0, both pointers NULL */
+int lfq_bed_intervals(const lfq_bed *bed, const char *name, const int32_t **beg_out, const int32_t **end_out, int64_t *n_out);
+int lfq_bed_overlap(const lfq_bed *bed, const char *name, int64_t beg, int64_t end);     /* 0 / 1; NULL arguments: 0 */
+
+/* The targets of the read-level pileups of this context.  The table of `name` goes to the device and the context keeps its own copy:
+ * the caller may free the BED at once.  bed_or_null = NULL takes the targets off again (name is then ignored).  A name the BED does
+ * not hold is an empty table: nothing overlaps, no read and no column.
+ * A READ SET TAKES THE CONTEXT'S TARGETS WHEN IT IS CREATED (every lfq_readset_create*, and the read set lfq_readset_viterbi makes);
+ * a later lfq_set_bed changes the read sets created after it only, so that BAQ, the kept reads and both pileups of one read set
+ * see one BED.  For such a read set, as `lofreq call -l` does it:
+ *   - reads (plp.c:625-629): a read whose [pos, bam_endpos) overlaps no interval is dropped before BAQ and before the -d cap.
+ *     lfq_readset_baq / _baq_fill launch the HMM for the other reads only (lfq_last_baq_times.n_reads counts those; a dropped
+ *     read keeps lb 0, ai / ad '~' and tag_flags 0), lfq_set_max_depth's rule runs on the survivors in file order, and
+ *     lfq_readset_kept_reads reports BED and cap together.  Unsorted reads (lfq_set_pileup_unsorted) are taken with a BED alone
+ *     and stay LFQ_ERR_INVALID with a cap;
+ *   - columns (plp.c:1412): lfq_readset_pileup_snv, lfq_readset_pileup_indels and lfq_readset_plp_summary hand out the covered
+ *     positions p whose [p, p + 1) overlaps an interval, in one column numbering.  The decision is made on the device, on the
+ *     per-position counters of the count pass.
+ * lfq_readset_pileup_sites and lfq_readset_uniq take every read (`lofreq uniq` has no -l); lfq_readset_source_qual and
+ * lfq_readset_indelqual compute their values for every read.
+ * LFQ_ERR_INVALID: ctx NULL, or bed given and name NULL. */
+int lfq_set_bed(lfq_ctx *ctx, const lfq_bed *bed_or_null, const char *name_or_null);
 
 /* lfq_call_snvs_batch in two halves, for callers that keep more than one batch in flight (one context per batch in
  * flight): submit launches the kernels and returns; collect waits, fetches the sparse records and finishes them on

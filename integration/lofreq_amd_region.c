@@ -83,6 +83,8 @@ struct lfq_region {
     int64_t wo_idaq;
     int64_t max_depth;              /* lfq_region_set_max_depth; LFQ_NO_MAX_DEPTH by default */
     int max_depth_set;              /* lfq_region_set_max_depth was called: close takes the cap off the context again */
+    const lfq_bed *bed;             /* lfq_region_set_bed; NULL = no targets (the default) */
+    int bed_set;                    /* lfq_region_set_bed was called: close takes the targets off the context again */
     lfq_indelqual_conf idq;         /* lfq_region_set_indelqual; mode 0 = off (the default) */
     int vit_on, vit_def_qual;       /* lfq_region_set_viterbi; off by default */
     int reuse_tags;                 /* lfq_region_set_reuse_tags; 0 by default */
@@ -184,6 +186,20 @@ int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth)
     if (rc == LFQ_OK) {
         r->max_depth = max_depth;
         r->max_depth_set = 1;
+    }
+    return rc;
+}
+
+int lfq_region_set_bed(lfq_region *r, const lfq_bed *bed_or_null)
+{
+    int rc;
+    if (!r || r->open || r->buf[0].started || r->buf[1].started) {
+        return LFQ_ERR_INVALID;                 /* (a region in flight keeps the targets its read set was created under) */
+    }
+    rc = lfq_set_bed(r->ctx, NULL, NULL);       /* every region puts its own contig's table there (region_start) */
+    if (rc == LFQ_OK) {
+        r->bed = bed_or_null;
+        r->bed_set = 1;
     }
     return rc;
 }
@@ -561,6 +577,14 @@ static int region_start(lfq_region *r, reg_buf *b)
     lfq_pileup_reads rd;
     lfq_pileup_indel_tags tg;
     int rc = LFQ_OK;
+    if (r->bed) {
+        /* -l: the table of this region's contig, for the read set created below on any of the three roads (a read set takes the
+         * context's targets when it is created; a contig the BED does not name gets an empty table: no read, no column) */
+        rc = lfq_set_bed(r->ctx, r->bed, b->target);
+        if (rc != LFQ_OK) {
+            return rc;
+        }
+    }
     if (b->fed_by == 3) {
         rc = region_readset_from_bgzf(r, b);    /* (how many reads the region has is what the scan keeps) */
         if (rc != LFQ_OK) {
@@ -637,8 +661,8 @@ static int region_start(lfq_region *r, reg_buf *b)
             return rc;
         }
     }
-    if (r->max_depth != LFQ_NO_MAX_DEPTH) {
-        /* which reads the cap keeps: decided on the host now, while this region's BAQ kernels run (both pileups share it) */
+    if (r->max_depth != LFQ_NO_MAX_DEPTH || r->bed) {
+        /* which reads cap and targets keep: decided now, while this region's BAQ kernels run (both pileups share it) */
         rc = lfq_readset_kept_reads(r->ctx, b->rs, NULL, NULL);
         if (rc != LFQ_OK) {
             lfq_readset_destroy(b->rs);
@@ -859,6 +883,9 @@ int lfq_region_close(lfq_region *r, int64_t *wo_idaq)
     lfq_set_indel_arrays_on_host(r->ctx, 1);
     if (r->max_depth_set) {
         lfq_set_max_depth(r->ctx, LFQ_NO_MAX_DEPTH);
+    }
+    if (r->bed_set) {
+        lfq_set_bed(r->ctx, NULL, NULL);
     }
     buf_free(&r->buf[0]);
     buf_free(&r->buf[1]);

@@ -7,9 +7,10 @@
  *     bam_mplp_auto + compile_plp_col      plp.c:1406-1447, 797-1288 (the pileup and the column builder)
  *     call_vars per column                 lofreq_call.c:887-935 (call_indels, call_snvs, report_var)
  * What stays with htslib on the CPU: opening the BAM, the index query, decompressing records into bam1_t, the read-level
- * filters of mplp_func (plp.c:608-632: unmapped / secondary / QC-fail / duplicate, BED overlap).  Unpacking a record's bases,
+ * filters of mplp_func (plp.c:608-620: unmapped / secondary / QC-fail / duplicate).  Its BED overlap (-l, plp.c:625-629) and the
+ * column rule of plp.c:1412 are the device's once lfq_region_set_bed is called.  Unpacking a record's bases,
  * qualities and BI / BD tags is the device's with lfq_region_add_record, the caller's thread's with lfq_region_add_read; with
- * lfq_region_add_bgzf the decompression, the record iteration and those filters (BED overlap excepted) leave htslib too.  The column callback
+ * lfq_region_add_bgzf the decompression, the record iteration and those filters leave htslib too.  The column callback
  * (integration/lofreq_amd_shim.c) keeps working for everything that wants plp_col_t; this path is for `lofreq call`
  * itself, whose end-to-end time was the CPU pileup + BAQ once the per-column statistics ran on the GPU.
  *
@@ -61,6 +62,13 @@ int lfq_region_open(lfq_region **out, lfq_ctx *ctx, lfq_conf *conf, const lfq_re
  * lfq_region_close takes it off again (LFQ_NO_MAX_DEPTH) if this call set it.  A negative `lofreq call -d` keeps only the first
  * read of each start position in htslib, which is max_depth = 0 here: map it, do not pass -1 through. */
 int lfq_region_set_max_depth(lfq_region *r, int64_t max_depth);
+/* -l / --bed: the targets (lfq_bed_parse, include/lofreq_amd.h) of every region after this call, on all three feeding roads.  Each
+ * region takes the table of its target_name (lfq_set_bed; a name the BED does not hold: no read, no column): a read that overlaps
+ * no interval is dropped in front of BAQ and of the -d cap (plp.c:625-629), a column outside every interval is not tested and
+ * takes no Bonferroni step (plp.c:1412).  The caller does NOT filter reads by the BED itself any more.  `bed` stays the caller's
+ * and must outlive the binding; NULL switches it off.  Same calling rule as lfq_region_set_max_depth; lfq_region_close takes the
+ * targets off the context again if this call set them. */
+int lfq_region_set_bed(lfq_region *r, const lfq_bed *bed_or_null);
 /* `lofreq indelqual` inside the binding (opt-in; default off): the reads of a region in which NO read came with a BI or BD tag
  * (bi == bd == NULL in lfq_region_add_read) get their indel qualities from lfq_readset_indelqual, between the BAQ step and the
  * indel pileup -- conf->mode LFQ_IDQ_DINDEL (`--dindel`, from the region's contig) or LFQ_IDQ_UNIFORM (`-u ins_qual,del_qual`).
@@ -121,8 +129,8 @@ int lfq_region_add_record(lfq_region *r, int32_t pos, int flag, int mapq, int l_
  * blocks are copied into a pinned staging buffer, and lfq_region_end inflates them on the device (lfq_bgzf_inflate), scans every
  * chunk's records with the filters of plp.c:606-722 (lfq_bam_scan_records: refID == tid, the flag mask 4 | 256 | 512 | 1024, overlap
  * with the region's [beg0, end0), min_mq / max_mq / no_orphan of the options) and decodes the kept ones from the device copy
- * (lfq_readset_create_from_bam_scan) -- with lfq_region_set_reuse_tags as for lfq_region_add_record.  BED overlap and
- * MPLP_ILLUMINA13 are not applied on this road.  VCF lines, counters and the return values of lfq_region_end are those of the same
+ * (lfq_readset_create_from_bam_scan) -- with lfq_region_set_reuse_tags as for lfq_region_add_record.  BED overlap is
+ * lfq_region_set_bed's, as on the other roads; MPLP_ILLUMINA13 is not applied on this road.  VCF lines, counters and the return values of lfq_region_end are those of the same
  * records fed by lfq_region_add_record.  Returns LFQ_OK; mixing it with the other two functions within a region is
  * LFQ_ERR_INVALID.  A block that does not inflate, a malformed record chain or aux field fails the region (LFQ_ERR_INVALID from
  * lfq_region_end). */

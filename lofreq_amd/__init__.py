@@ -21,6 +21,7 @@ from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_ind
                      skip_snv_columns, BgzfError, bam_scan_records, bgzf_inflate, last_bgzf_times,
                      bam_frame_encoded, bgzf_deflate, last_bgzf_deflate_times)
 from .bamindex import BamIndex, BamIndexError, bam_index_build, bam_record_chain, bam_record_cuts, last_bam_index_times
+from .bed import Bed, BedError
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
 
@@ -39,4 +40,5 @@ __all__ = [
     "bgzf_inflate", "BgzfError", "bam_scan_records", "last_bgzf_times",
     "bgzf_deflate", "last_bgzf_deflate_times", "bam_frame_encoded", "LFQ_BGZF_PUT_EOF",
     "BamIndex", "BamIndexError", "bam_index_build", "last_bam_index_times", "bam_record_chain", "bam_record_cuts",
+    "Bed", "BedError",
 ]

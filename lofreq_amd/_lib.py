@@ -289,6 +289,7 @@ EXPORTS = [
     "lfq_indelqual_batch", "lfq_readset_indelqual", "lfq_readset_fetch_indelquals", "lfq_last_indelqual_times",
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
+    "lfq_bed_parse", "lfq_bed_free", "lfq_bed_n_names", "lfq_bed_name", "lfq_bed_intervals", "lfq_bed_overlap", "lfq_set_bed",
 ]
 
 class FilterConf(C.Structure):
@@ -483,6 +484,17 @@ def load():
     L.lfq_filter_var_from_snv.restype = None
     L.lfq_filter_var_from_indel.argtypes = [vp, vp]
     L.lfq_filter_var_from_indel.restype = None
+    L.lfq_bed_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_bed_free.argtypes = [vp]
+    L.lfq_bed_free.restype = None
+    L.lfq_bed_n_names.argtypes = [vp]
+    L.lfq_bed_n_names.restype = C.c_int64
+    L.lfq_bed_name.argtypes = [vp, C.c_int64]
+    L.lfq_bed_name.restype = C.c_char_p
+    L.lfq_bed_intervals.argtypes = [vp, C.c_char_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
+                                    C.POINTER(C.c_int64)]
+    L.lfq_bed_overlap.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int64]
+    L.lfq_set_bed.argtypes = [vp, vp, C.c_char_p]
     _lib = L
     return L
 

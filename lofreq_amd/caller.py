@@ -193,6 +193,12 @@ class SnvCaller:
         column) instead of refusing them like mpileup does"""
         _lib.check(self.L.lfq_set_pileup_unsorted(self.h, 1 if on else 0), "lfq_set_pileup_unsorted")
 
+    def set_bed(self, bed, name=None):
+        """lfq_set_bed: the targets of `lofreq call -l` for the read sets created from now on -- the table of `name` in `bed`
+        (a lofreq_amd.Bed); bed=None takes them off again"""
+        from .bed import set_bed
+        set_bed(self, bed, name)
+
     def set_baq_hmm_params(self, gap_open=1e-5, gap_ext=0.4):
         """lfq_set_baq_hmm_params: kpa_ext_par_t.d / .e of the BAQ HMM (defaults: kpa_ext_par_lofreq_illumina,
         kprobaln_ext.c:50; a -DPACBIO_REALN build of the reference uses 0.1 / 0.4, :51)"""

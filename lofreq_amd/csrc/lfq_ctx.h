@@ -11,6 +11,7 @@
  *   lfq_bgzf.hip       BGZF blocks inflated on the device (over lfq_inflate.h), the record scan, lfq_readset_create_from_bgzf
  *   lfq_bgzf_deflate.hip   bytes cut into BGZF blocks and compressed on the device (over lfq_deflate.h)
  *   lfq_bamidx.hip         the .bai of a BAM from its records and block tables (over lfq_bamidx.h)
+ *   lfq_bed.hip            the targets of `lofreq call -l`: the BED itself, lfq_set_bed, the read and column kernels (over lfq_bed.h)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -40,6 +41,7 @@
 
 #include "lfq_internal.h"
 #include "lfq_plp_indel_host.h"
+#include "lfq_bed.h"
 #include "lofreq_synth.h"
 
 #define LFQ_TRY_HIP(expr)           \
@@ -266,6 +268,21 @@ struct LfqEvPair {
     }
 };
 
+/* the table of one name of a BED on the device and on the host (lfq_set_bed, lfq_bed.hip).  The context holds one reference, every
+ * read set created while it was set another: a later lfq_set_bed leaves the read sets of the earlier one as they are */
+struct LfqBedDev {
+    std::atomic<int> refs;
+    LfqBedName host;
+    int32_t *d;                         /* beg[n] | pmax[n] */
+    LfqBedTab tab;                      /* ... as the kernels take them */
+};
+static inline LfqBedDev *lfq_bed_dev_retain(LfqBedDev *b)
+{
+    if (b) b->refs.fetch_add(1);
+    return b;
+}
+void lfq_bed_dev_release(LfqBedDev *b);    /* lfq_bed.hip */
+
 struct lfq_ctx {
     int device;
     hipStream_t stream;
@@ -418,7 +435,7 @@ struct lfq_ctx {
     struct LfqBgzfState *bgzf;       /* lfq_bgzf_inflate: its buffers, result and timing (lfq_bgzf.hip; created on first use) */
     struct LfqBgzfDefState *bgzf_def; /* lfq_bgzf_deflate: likewise (lfq_bgzf_deflate.hip) */
     struct LfqBamIdxState *bamidx;   /* lfq_bam_index_build: likewise (lfq_bamidx.hip) */
-};
+    LfqBedDev *bed;                  /* lfq_set_bed: the targets the read sets created from now on take (null: none) */};
 
 template <typename T>
 int grow(T **ptr, int64_t *cap, int64_t need)
@@ -587,6 +604,12 @@ const uint8_t *lfq_bgzf_resident_bytes(lfq_ctx *c, const uint8_t *p, int64_t byt
 const uint8_t *lfq_bam_framed_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 void lfq_bgzf_deflate_release(lfq_ctx *c);
 void lfq_bam_index_release(lfq_ctx *c);    /* lfq_bamidx.hip: what lfq_destroy frees of lfq_ctx::bamidx */
+/* lfq_bed.hip, for the read set (lfq_readset.hip).  keep_out[r] = 1 iff [pos, bam_endpos) of read r overlaps an interval, one lane
+ * per read, from the resident start positions and CIGAR words; cov[p] (and nb[p], unless null) of every position of
+ * [begin, begin + width) whose [p, p + 1) overlaps none go to 0, one lane per position: no column for the compaction behind it */
+int lfq_launch_bed_keep(const LfqBedTab &tab, const int32_t *pos, const int64_t *cigar_off, const uint32_t *cigar, int64_t n,
+                        uint8_t *keep_out, void *stream);
+int lfq_launch_bed_mask_columns(const LfqBedTab &tab, int64_t begin, int64_t width, int32_t *cov, int32_t *nb_or_null, void *stream);
 extern "C" {
 /* everything the library queues that rewrites what a running batch still reads waits for the batch's last event first */
 int lfq_order_after_batch(lfq_ctx *c, hipStream_t st);

@@ -83,8 +83,9 @@ __global__ __launch_bounds__(256) void lfq_pileup_scatter_kernel(LfqPileupArgs A
             for (int j = 0; j < l; j++) {
                 const int64_t c = x + j - A.begin;
                 const int bq = qual[y + j];
-                if (c >= 0 && c < A.width && bq >= A.min_plp_bq) {
-                    const int ci = A.col_index[c];
+                /* (a covered position need not be a column: targets, lfq_set_bed, leave the flanks of an interval without one) */
+                const int ci = (c >= 0 && c < A.width && bq >= A.min_plp_bq) ? A.col_index[c] : -1;
+                if (ci >= 0) {
                     const uint64_t slot = A.col_off[ci] + (uint64_t)atomicAdd(&A.cursor[c], 1);
                     A.t_nt[slot] = (uint8_t)((seq[y + j] > 4 ? 4 : seq[y + j]) | strand);
                     A.t_bq[slot] = (uint8_t)(bq > 93 ? 93 : bq);                       /* plp.c:948-952 */
@@ -648,7 +649,7 @@ __global__ __launch_bounds__(256) void lfq_pileup_tiles_kernel(LfqPileupArgs A)
                 const uint64_t mk = __ballot(kept);
                 if (!SCATTER) {
                     n_cov[i] += (uint32_t)__popcll(__ballot(any));
-                } else if (kept) {
+                } else if (kept && base[i] != ~0ull) {              /* (~0: no column here -- uncovered, or outside the targets) */
                     const uint64_t slot = base[i] + n_kept[i] + (uint64_t)__popcll(mk & ((1ull << lane) - 1ull));
                     const uint32_t code = rs[off + dp];
                     const uint32_t lb = A.baq ? rb[off + dp] : 0u;

@@ -146,6 +146,13 @@ struct lfq_readset {
     uint8_t *stored_blob;               /* take[n] | lb | ai | ad, the arrays of the tags a read has */
     uint8_t *d_take, *d_st[3];          /* (d_st[t] null: no read has tag t) */
     bool filled;                        /* the resident lb / ai / ad hold stored bytes: no longer what `alnqual` would append */
+    /* -l targets (lfq_set_bed): the context's table when the read set was created (a reference; null: none), and which reads
+     * overlap it -- decided once, on the device (readset_bed_keep) */
+    LfqBedDev *bed;
+    bool bed_valid;
+    int bed_rc;
+    std::vector<uint8_t> bed_keep;      /* [n] 1 = the read overlaps an interval */
+    int64_t n_bed_kept;
 };
 
 /* the reads, qualities, CIGARs and the contig are on the device (BI / BD may still be on their way: the BAQ kernels do
@@ -255,16 +262,19 @@ void lfq_readset_destroy(lfq_readset *rs)
         if (rs->own) {
             rs_cache_give(rs->c, LFQ_RSC_PINBASES, rs->own->pin_bases, rs->own->pin_cap);
         }
+        lfq_bed_dev_release(rs->bed);
         delete rs->own;
         delete rs;
     }
 }
 
-/* lfq_readset_create; rd->seq may be null here (lfq_indelqual_batch: its kernels read no bases).  bases_resident
+/* lfq_readset_create; rd->seq may be null here (lfq_indelqual_batch: its kernels read no bases).  take_bed: the read set takes the
+ * context's targets (lfq_set_bed) -- every read set a caller sees does; those behind lfq_baq_batch and lfq_indelqual_batch, the
+ * library's `alnqual` and `indelqual`, which have no -l, do not.  bases_resident
  * (lfq_readset_viterbi): the per-base device arrays -- seq, qual, BI, BD -- get their room but no copy; the caller fills them
  * on the device before it hands the read set out */
 static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pileup_indel_tags *tg, lfq_readset **out,
-                          bool bases_resident = false)
+                          bool bases_resident = false, bool take_bed = true)
 {
     if (!c || !rd || !out || rd->n_reads < 0
         || (rd->n_reads > 0 && (!rd->pos || !rd->cigar_off || !rd->cigar || !rd->seq_off || !rd->ref))) {
@@ -306,6 +316,10 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     rs->own = nullptr;
     rs->stored_blob = rs->d_take = rs->d_st[0] = rs->d_st[1] = rs->d_st[2] = nullptr;
     rs->filled = false;
+    rs->bed = take_bed ? lfq_bed_dev_retain(c->bed) : nullptr;
+    rs->bed_valid = false;
+    rs->bed_rc = LFQ_OK;
+    rs->n_bed_kept = 0;
     rs->has_lb = rs->has_idaq = rs->has_sqb = rs->has_bi = rs->has_bd = false;
     const int64_t n = rs->n, nb = rs->n_bases;
     {
@@ -329,6 +343,7 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
                   o_lb = take(rd->baq ? nb + 16 : 0), o_fl = take(n), o_sqb = take(n);
     rs->blob = (uint8_t *)rs_cache_take(c, LFQ_RSC_BLOB, (size_t)off, &rs->cap[LFQ_RSC_BLOB]);
     if (!rs->blob) {
+        lfq_bed_dev_release(rs->bed);
         delete rs;
         return LFQ_ERR_NOMEM;
     }
@@ -588,6 +603,56 @@ static int readset_pmax(lfq_ctx *c, lfq_readset *rs, hipStream_t st, bool unsort
     return rs->d_pmax || rs->n == 0 || (unsorted_may && readset_unsorted_ok(c)) ? (int)LFQ_OK : (int)LFQ_ERR_INVALID;
 }
 
+/* ---- -l / --bed (lfq_set_bed) -----------------------------------------------------------------------------------
+ * plp.c:625-629: a read that overlaps no interval of the targets is dropped behind the flag filters and in front of BAQ and of
+ * bam_plp_push.  Which reads those are is decided once per read set, by lfq_bed_keep_kernel on the start positions and CIGAR words
+ * the read set has on the device; the bytes come back once (a byte a read), because the two things that follow are made on the
+ * host: the launch lists of the HMM kernels (readset_baq_run) and the -d rule on the survivors (readset_keep).  The kernel goes to
+ * the context's stream behind the first chunk of the upload, which the small per-read arrays are in front of; the mask lands in
+ * the context's BAQ temporary, which the same stream fills again when the BAQ step runs. */
+static int readset_bed_keep(lfq_ctx *c, lfq_readset *rs)
+{
+    if (!rs->bed || rs->bed_valid) {
+        return rs->bed_rc;
+    }
+    rs->bed_valid = true;
+    const int64_t n = rs->n;
+    rs->n_bed_kept = 0;
+    if (n == 0) {
+        return LFQ_OK;
+    }
+    auto run = [&]() -> int {
+        LFQ_TRY_HIP(hipSetDevice(c->device));
+        LFQ_TRY(readset_upload_wait_reads(rs, 0, c->stream));
+        LfqPin<uint8_t> h(c, (size_t)n);
+        LFQ_PIN_OK(h);
+        if (rs->bed->tab.n > 0) {
+            LFQ_TRY(grow(&c->d_tmp[0], &c->tmp_bytes[0], n));
+            uint8_t *d_mask = c->d_tmp[0];
+            int rc = lfq_launch_bed_keep(rs->bed->tab, (const int32_t *)rs->d_pos, (const int64_t *)rs->d_coff,
+                                         (const uint32_t *)rs->d_cig, n, d_mask, c->stream);
+            if (rc == LFQ_OK && hipMemcpyAsync(h.data(), d_mask, (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+                rc = LFQ_ERR_HIP;
+            }
+            if (hipStreamSynchronize(c->stream) != hipSuccess && rc == LFQ_OK) {
+                rc = LFQ_ERR_HIP;
+            }
+            LFQ_TRY(rc);
+        } else {
+            memset(h.data(), 0, (size_t)n);         /* an empty table: nothing overlaps, nothing to launch */
+        }
+        rs->bed_keep.assign(h.data(), h.data() + n);
+        int64_t kept = 0;
+        for (int64_t r = 0; r < n; r++) {
+            kept += rs->bed_keep[(size_t)r];
+        }
+        rs->n_bed_kept = kept;
+        return LFQ_OK;
+    };
+    rs->bed_rc = run();
+    return rs->bed_rc;
+}
+
 /* ---- -d / --max-depth (lfq_set_max_depth) --------------------------------------------------------------------
  * htslib's bam_plp_push does not push a read that starts at the iterator's current position while its node pool holds more
  * than maxcnt reads (bam_mplp_set_maxcnt, plp.c:1391-1392).  On the reads in file order: the first read at a start position P
@@ -598,13 +663,23 @@ static int readset_pmax(lfq_ctx *c, lfq_readset *rs, hipStream_t st, bool unsort
  *   2. the proof, over the runs of equal start in parallel: if every read were kept, at most (end of the run) - (first read
  *      whose running maximum reaches P) reads would count at the last read of a run at P.  Within the cap at every run:
  *      nothing is dropped, no mask, the pileups run exactly as without a cap;
- *   3. otherwise one walk over the reads with a min-heap of the kept reads' ends (reads * log depth). */
+ *   3. otherwise one walk over the reads with a min-heap of the kept reads' ends (reads * log depth).
+ * With targets (lfq_set_bed) the reads bam_plp_push sees are those the BED leaves (readset_bed_keep), in file order: the mask starts
+ * from them, the proof of step 2 holds for a subset of the reads it counts, and the walk of step 3 passes over the others.  Without
+ * a cap the mask is the BED's, and reads that are not position-sorted are fine (no rule on file order is applied). */
+static bool readset_masked(const lfq_ctx *c, const lfq_readset *rs)
+{
+    return c->plp_max_depth != LFQ_NO_MAX_DEPTH || rs->bed != nullptr;
+}
+
 static int readset_keep(lfq_ctx *c, lfq_readset *rs)
 {
     const int64_t md = c->plp_max_depth;
-    if (md == LFQ_NO_MAX_DEPTH) {
+    if (!readset_masked(c, rs)) {
         return LFQ_OK;
     }
+    LFQ_TRY(readset_bed_keep(c, rs));
+    const uint8_t *bk = rs->bed && rs->n > 0 ? rs->bed_keep.data() : nullptr;
     if (rs->keep_valid && rs->keep_for == md) {
         return rs->keep_rc;
     }
@@ -651,11 +726,22 @@ static int readset_keep(lfq_ctx *c, lfq_readset *rs)
         part_max[part] = run;
         part_sorted[part] = sorted;
     }, &parts);
-    for (int q = 0; q < parts; q++) {
+    for (int q = 0; q < parts && md != LFQ_NO_MAX_DEPTH; q++) {
         if (!part_sorted[q]) {
             rs->keep_rc = LFQ_ERR_INVALID;          /* the rule is defined on file order; bam_mplp_auto refuses such files */
             return rs->keep_rc;
         }
+    }
+    auto bed_only = [&]() {                         /* the mask is the BED's (none where it keeps every read) */
+        if (bk && rs->n_bed_kept < n) {
+            rs->keep = rs->bed_keep;
+            rs->keep_end.swap(end);
+            rs->n_kept = rs->n_bed_kept;
+        }
+        return LFQ_OK;
+    };
+    if (md == LFQ_NO_MAX_DEPTH) {
+        return bed_only();
     }
     if (parts > 1) {
         int32_t before[LFQ_HOST_PARTS];
@@ -688,15 +774,19 @@ static int readset_keep(lfq_ctx *c, lfq_readset *rs)
         }
     });
     if (!drops.load()) {
-        return LFQ_OK;
+        return bed_only();
     }
     /* 3. the walk */
     rs->keep.assign((size_t)n, 0);
     std::priority_queue<int32_t, std::vector<int32_t>, std::greater<int32_t>> live;   /* ends of the kept reads still counted */
-    int64_t kept = 0;
+    int64_t kept = 0, prev = -1;                    /* prev: the read pushed before this one */
     for (int64_t r = 0; r < n; r++) {
+        if (bk && !bk[r]) {
+            continue;
+        }
         const int32_t P = rs->pos[r];
-        const bool first = r == 0 || P != rs->pos[r - 1];
+        const bool first = prev < 0 || P != rs->pos[prev];
+        prev = r;
         if (first) {
             while (!live.empty() && live.top() < P) {
                 live.pop();
@@ -724,7 +814,7 @@ static int readset_keep_device(lfq_ctx *c, lfq_readset *rs, hipStream_t st, cons
 {
     *kept_idx = *kept_pos = *kept_pmax = nullptr;
     LFQ_TRY(readset_keep(c, rs));
-    if (c->plp_max_depth == LFQ_NO_MAX_DEPTH || rs->keep.empty()) {
+    if (!readset_masked(c, rs) || rs->keep.empty()) {
         return LFQ_OK;
     }
     const int64_t n = rs->n;
@@ -797,11 +887,11 @@ static int readset_pileup_view(lfq_ctx *c, lfq_readset *rs, hipStream_t st, bool
     v->pmax_end = rs->d_pmax;
     const int32_t *k_idx, *k_pos, *k_pmax;
     LFQ_TRY(readset_keep_device(c, rs, st, &k_idx, &k_pos, &k_pmax));
-    if (k_idx) {                            /* (null: the cap drops nothing, or there is none) */
+    if (k_idx) {                            /* (null: cap and targets drop nothing, or there are none) */
         v->n_reads = rs->n_kept;
         v->read_idx = k_idx;
         v->pos = k_pos;
-        v->pmax_end = k_pmax;
+        v->pmax_end = rs->d_pmax ? k_pmax : nullptr;    /* (unsorted reads under targets alone: the read-major kernels, still) */
     }
     return LFQ_OK;
 }
@@ -812,7 +902,7 @@ int lfq_readset_kept_reads(lfq_ctx *c, lfq_readset *rs, uint8_t *keep_out, int64
         return LFQ_ERR_INVALID;
     }
     LFQ_TRY(readset_keep(c, rs));
-    const bool capped = c->plp_max_depth != LFQ_NO_MAX_DEPTH;
+    const bool capped = readset_masked(c, rs);
     if (keep_out && rs->n > 0) {
         if (capped && !rs->keep.empty()) {
             memcpy(keep_out, rs->keep.data(), (size_t)rs->n);
@@ -859,7 +949,10 @@ static int readset_from_baq_reads(lfq_ctx *c, const lfq_baq_reads *rd, lfq_reads
     pr.n_reads = rd->n_reads;
     pr.pos = rd->pos; pr.cigar_off = rd->cigar_off; pr.cigar = rd->cigar; pr.seq_off = rd->seq_off;
     pr.seq = rd->seq; pr.qual = rd->qual; pr.ref = rd->ref; pr.ref_len = rd->ref_len;
-    return lfq_readset_create(c, &pr, nullptr, rs);
+    if (pr.n_reads > 0 && !pr.seq) {
+        return LFQ_ERR_INVALID;
+    }
+    return readset_create(c, &pr, nullptr, rs, false, false);
 }
 
 int lfq_baq_batch(lfq_ctx *c, const lfq_baq_reads *rd, int baq_extended, uint8_t *lb_out)
@@ -1353,7 +1446,22 @@ int lfq_readset_baq(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want_idaq
     if (!c || !rs || rs->c != c || (rs->n > 0 && !rs->qual)) {
         return LFQ_ERR_INVALID;
     }
-    return readset_baq_run(c, rs, baq_extended, want_idaq != 0, nullptr, false);
+    const bool want = want_idaq != 0;
+    if (rs->bed && rs->n > 0) {
+        /* plp.c:625-629 comes before the realignment: the HMM runs for the reads the targets keep */
+        LFQ_TRY(readset_bed_keep(c, rs));
+        std::vector<uint8_t> skip((size_t)rs->n);
+        for (int64_t r = 0; r < rs->n; r++) {
+            skip[(size_t)r] = rs->bed_keep[(size_t)r] ? 0 : 1;
+        }
+        if (rs->n_bed_kept == 0) {
+            c->baq_launches = 0;                /* (no launch: readset_baq_run leaves the context's figures alone then) */
+            c->baq_reads = 0;
+            c->baq_bases = rs->n_bases;
+        }
+        return readset_baq_run(c, rs, baq_extended, want, skip.data(), false);
+    }
+    return readset_baq_run(c, rs, baq_extended, want, nullptr, false);
 }
 
 /* lfq_readset_baq where a tag is missing (include/lofreq_amd.h has the rule): need_r on the host, from the CIGARs and the stored
@@ -1369,8 +1477,17 @@ int lfq_readset_baq_fill(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want
     memset(&F, 0, sizeof(F));
     F.n_reads = n;
     c->fill_hmm = c->fill_merge = 0;
+    const uint8_t *bk = nullptr;                        /* targets: the reads they drop need no tag at all */
+    if (rs->bed && n > 0) {
+        LFQ_TRY(readset_bed_keep(c, rs));
+        bk = rs->bed_keep.data();
+    }
     if (rs->stored_fl.empty() || n == 0) {
-        const int rc = readset_baq_run(c, rs, baq_extended, want_idaq, nullptr, false, &F);
+        std::vector<uint8_t> bed_skip;
+        for (int64_t r = 0; bk && r < n; r++) {
+            bed_skip.push_back(bk[r] ? 0 : 1);
+        }
+        const int rc = readset_baq_run(c, rs, baq_extended, want_idaq, bk ? bed_skip.data() : nullptr, false, &F);
         c->fill_hmm = rc == LFQ_OK && F.n_hmm_launches > 0;
         return rc;
     }
@@ -1391,8 +1508,8 @@ int lfq_readset_baq_fill(lfq_ctx *c, lfq_readset *rs, int baq_extended, int want
                 has_ins = has_ins || op == 1;
                 has_del = has_del || op == 2;
             }
-            const uint8_t S = (uint8_t)(rs->stored_fl[(size_t)r] & keep_bits);
-            const bool need = !(S & 1u) || (want_idaq && ((has_del && !(S & 4u)) || (has_ins && !(S & 2u))));
+            const uint8_t S = (bk && !bk[r]) ? (uint8_t)0 : (uint8_t)(rs->stored_fl[(size_t)r] & keep_bits);
+            const bool need = (bk && !bk[r]) ? false : !(S & 1u) || (want_idaq && ((has_del && !(S & 4u)) || (has_ins && !(S & 2u))));
             skip[(size_t)r] = need ? 0 : 1;
             rs->take[(size_t)r] = S;
             for (int t = 0; t < 3; t++) {
@@ -1610,7 +1727,7 @@ int lfq_indelqual_batch(lfq_ctx *c, const lfq_baq_reads *rd, const lfq_indelqual
     pr.pos = rd->pos; pr.cigar_off = rd->cigar_off; pr.cigar = rd->cigar; pr.seq_off = rd->seq_off;
     pr.ref = rd->ref; pr.ref_len = rd->ref_len;
     lfq_readset *rs = nullptr;
-    LFQ_TRY(readset_create(c, &pr, nullptr, &rs));
+    LFQ_TRY(readset_create(c, &pr, nullptr, &rs, false, false));
     int rc = lfq_readset_indelqual(c, rs, conf);
     if (rc == LFQ_OK) {
         rc = lfq_readset_fetch_indelquals(c, rs, bi_out, bd_out);
@@ -1688,6 +1805,10 @@ int lfq_readset_pileup_snv(lfq_ctx *c, lfq_readset *rs, int64_t region_begin, in
     A.nb = (int32_t *)(d + o_nb);
     A.cursor = (int32_t *)(d + o_cur);
     LFQ_TRY(sorted ? lfq_launch_pileup_columns(A, 0, ps) : lfq_launch_pileup_count(A, ps));
+    if (rs->bed) {
+        /* plp.c:1412: a position outside every interval is no column, however many of the kept reads cover it */
+        LFQ_TRY(lfq_launch_bed_mask_columns(rs->bed->tab, region_begin, width, A.cov, A.nb, ps));
+    }
     /* columns from the counters on the device (lfq_launch_plp_compact_*): the host waits once, for three numbers */
     LfqPin<int64_t> tot(c, 4);
     LFQ_PIN_OK(tot);
@@ -1797,12 +1918,19 @@ int lfq_readset_sites_impl(lfq_ctx *c, lfq_readset *rs, const int64_t *site_pos,
     /* the window search needs position-sorted reads, and the reference's -d acts on the reads of each 1-bp query: a cap
      * that drops a read of the region is not that rule */
     LFQ_TRY(readset_keep(c, rs));
-    if (c->plp_max_depth != LFQ_NO_MAX_DEPTH && !rs->keep.empty()) {
+    if (c->plp_max_depth != LFQ_NO_MAX_DEPTH && !rs->keep.empty() && rs->n_kept < (rs->bed ? rs->n_bed_kept : rs->n)) {
         return LFQ_ERR_INVALID;
     }
     LfqSitesArgs A;
     memset(&A, 0, sizeof(A));
-    LFQ_TRY(readset_pileup_view(c, rs, ps, false, &A));   /* (the cap decided above drops nothing: only the running maximum goes up) */
+    if (rs->bed) {
+        /* `lofreq uniq` has no -l: every read, whatever the targets of the read set drop (the cap was decided on their survivors) */
+        readset_view(rs, &A);
+        LFQ_TRY(readset_pmax(c, rs, ps, false));
+        A.pmax_end = rs->d_pmax;
+    } else {
+        LFQ_TRY(readset_pileup_view(c, rs, ps, false, &A));   /* (the cap decided above drops nothing: only the running maximum goes up) */
+    }
     c->sites_times.n_sites = n_sites;
     const int64_t n = n_sites, n_key = key_off ? key_off[n] - key_off[0] : 0;
     /* what goes up in one copy: positions | key offsets | key sides | key letters; then the windows and the counts */
@@ -1957,7 +2085,7 @@ static LfqPlpReads readset_plp_reads(const lfq_ctx *c, const lfq_readset *rs)
     R.bi = rs->h_bi; R.bd = rs->h_bd; R.ai = rs->h_ai; R.ad = rs->h_ad; R.fl = rs->fl.data();
     R.sq = rs->h_sq ? rs->h_sq : (rs->sq32.empty() ? nullptr : rs->sq32.data());
     R.idq_mode = rs->idq_mode; R.idq_ins = rs->idq_ins; R.idq_del = rs->idq_del;
-    R.keep = (c->plp_max_depth != LFQ_NO_MAX_DEPTH && rs->keep_valid && !rs->keep.empty()) ? rs->keep.data() : nullptr;
+    R.keep = (readset_masked(c, rs) && rs->keep_valid && !rs->keep.empty()) ? rs->keep.data() : nullptr;
     return R;
 }
 
@@ -2030,6 +2158,10 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
     if (rc == LFQ_OK) {
         rc = A.pmax_end ? lfq_launch_plp_indel_columns(A, 0, ps) : lfq_launch_plp_indel(A, 0, ps);
     }
+    if (rc == LFQ_OK && rs->bed) {
+        /* plp.c:1412, as in lfq_readset_pileup_snv: the coverage the host makes the columns from is 0 outside the targets */
+        rc = lfq_launch_bed_mask_columns(rs->bed->tab, region_begin, width, A.cov, nullptr, ps);
+    }
     const bool have_qsum = A.pmax_end != nullptr;       /* the column-major kernel sums the qualities itself */
     for (int i = 0; i < (have_qsum ? 9 : 7) && rc == LFQ_OK; i++) {
         if (hipMemcpyAsync(h[i], *cnt[i], (size_t)width * 4, hipMemcpyDeviceToHost, ps) != hipSuccess) {
@@ -2047,6 +2179,12 @@ int lfq_readset_pileup_indels(lfq_ctx *c, lfq_readset *rs, int64_t region_begin,
         lfq_plp_scan_events(R, r_begin, r_end, region_begin, region_end, min_plp_idq, evs_part[part]);
     });
     lfq_plp_merge_events(evs_part, LFQ_HOST_PARTS, evs);
+    if (rs->bed) {
+        /* an event belongs to the column of its position: outside the targets there is none (the host copy of the same table) */
+        const LfqBedTab tab = rs->bed->host.tab();
+        evs.erase(std::remove_if(evs.begin(), evs.end(), [&](const LfqPlpEv &e) { return !lfq_bed_tab_overlap(tab, e.pos, e.pos + 1); }),
+                  evs.end());
+    }
     /* 4a. the event tables, part by part, while the counter kernel is still on its way (it waits for BI / BD, the end of
      * the upload): they need the events and the caller's arrays, nothing from the device */
     const int n_parts = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<long>(std::max<long>(lfq_knobs().host_loop_threads, 1), LFQ_HOST_PARTS), evs.size() / (size_t)std::max<int64_t>(lfq_knobs().host_par_min / 48, 1)));

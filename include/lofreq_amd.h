@@ -52,6 +52,8 @@ extern "C" {
 /* (10 still: lfq_bgzf_deflate, lfq_last_bgzf_deflate_times, lfq_bam_frame_encoded, and the lfq_bam_index_* / lfq_bam_record_* functions are
  * new functions with new structs; no existing layout changed.) */
 /* (10 still: lfq_bed_parse and the other lfq_bed_* functions, lfq_set_bed are new functions with a new opaque type; no existing layout changed.) */
+/* (10 still: the lfq_fasta_* functions, lfq_last_fasta_times, lfq_checkref, lfq_bgzf_gzi_bytes, lfq_readset_ref_from_device are new functions with
+ * new types; no existing layout changed.) */
 #define LFQ_ABI_VERSION 10
 
 typedef enum lfq_status {
@@ -1075,6 +1077,95 @@ int lfq_bed_overlap(const lfq_bed *bed, const char *name, int64_t beg, int64_t e
  * lfq_readset_indelqual compute their values for every read.
  * LFQ_ERR_INVALID: ctx NULL, or bed given and name NULL. */
 int lfq_set_bed(lfq_ctx *ctx, const lfq_bed *bed_or_null, const char *name_or_null);
+
+/* ---- `lofreq faidx`, the contig in front of every region, `lofreq checkref` ----------------------------------------------------------
+ * The `ref` every read-level entry takes (lfq_baq_reads.ref, lfq_pileup_reads.ref, lfq_bam_records.ref) is a whole contig of a FASTA:
+ * faidx_fetch_seq(fai, name, 0, 0x7fffffff, &len).  These functions make the index (`lofreq faidx`, fai_build) and the contig on the
+ * device from the file's bytes, by the rules of the 2.1.4 binary (lofreq_amd/csrc/lfq_fasta.h states them):
+ *   - a line is a header iff its first byte is '>'; its name: the bytes behind '>' after leading blanks up to the next blank (may be
+ *     empty); .fai line: name, length, offset, line_blen, line_len, tab-separated;
+ *   - length counts the graph bytes (0x21 .. 0x7e) of the sequence's lines, line_blen / line_len are the first line's graph bytes and
+ *     its bytes with the terminator ("\r" counts towards line_len only); a last line without '\n' counts as if it had one;
+ *   - a line with more BYTES than line_len: refused, LFQ_FASTA_LINE_LENGTH.  A line with fewer (the empty line too) ends the sequence,
+ *     and only "\n" and "\r\n" lines may follow before the next header; anything else, and any other text in front of the first
+ *     header: LFQ_FASTA_UNEXPECTED.  *bad_line is the 1-based line, *bad_byte the byte htslib's message shows (the line's first, or the
+ *     one behind a leading '\r'; -1: the file ends there);
+ *   - a header followed by an empty line, another header or nothing has no sequence: dropped silently in mid-file; the whole file is
+ *     refused when it is the LAST header (LFQ_FASTA_LAST_EMPTY).  A file without any header: LFQ_FASTA_EMPTY_FILE;
+ *   - of equal names the first stays (lfq_fasta_index_n_duplicates counts the others).
+ * Only whole contigs are fetched, as the reference does; FASTQ is not read; files are the caller's to read.
+ *
+ * lfq_fasta_open uploads the bytes (device to device when they lie inside the context's live lfq_bgzf_inflate result -- a bgzip-
+ * compressed FASTA --, lfq_fasta_times.n_from_device says so) and scans them; the file stays resident until lfq_fasta_close, which must
+ * come before lfq_destroy.  The caller's bytes are not needed after the call.  n_bytes == 0 is LFQ_OK: the index build then refuses.
+ * LFQ_ERR_INVALID: ctx / out NULL, n_bytes < 0, bytes NULL with n_bytes > 0.  Blocks. */
+typedef struct lfq_fasta lfq_fasta;
+typedef struct lfq_fasta_index lfq_fasta_index;
+#define LFQ_FASTA_OK 0
+#define LFQ_FASTA_UNEXPECTED 1
+#define LFQ_FASTA_LINE_LENGTH 2
+#define LFQ_FASTA_LAST_EMPTY 3
+#define LFQ_FASTA_EMPTY_FILE 4
+int lfq_fasta_open(lfq_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, lfq_fasta **out);
+void lfq_fasta_close(lfq_fasta *fa);
+/* the index of the resident file.  LFQ_OK and *out (the caller's, lfq_fasta_index_free), or LFQ_ERR_INVALID with *why_or_null one of
+ * LFQ_FASTA_* and the place of the FIRST offending line (found by an atomic minimum over the lines: the same on every run).  Blocks. */
+int lfq_fasta_index_build(lfq_fasta *fa, lfq_fasta_index **out, int *why_or_null, int64_t *bad_line_or_null, int *bad_byte_or_null);
+/* host only, no context.  The .fai text of an index (the index's, valid until it is freed) and an index from .fai text -- one the
+ * caller read from disk, possibly made by another tool for another version of the file.  Columns behind the fifth are ignored;
+ * LFQ_ERR_INVALID: fewer than five columns in a line, a column that is no non-negative decimal number */
+int lfq_fasta_index_text(const lfq_fasta_index *idx, const char **text, int64_t *n_bytes);
+int lfq_fasta_index_parse(const char *text, int64_t n_bytes, lfq_fasta_index **out);
+void lfq_fasta_index_free(lfq_fasta_index *idx);
+typedef struct lfq_fasta_entry {
+    int64_t length, offset;
+    int32_t line_blen, line_len;
+} lfq_fasta_entry;
+int64_t lfq_fasta_index_n(const lfq_fasta_index *idx);
+int64_t lfq_fasta_index_n_duplicates(const lfq_fasta_index *idx);
+const char *lfq_fasta_index_name(const lfq_fasta_index *idx, int64_t i);     /* in file order; NULL outside [0, n) */
+int lfq_fasta_index_entry(const lfq_fasta_index *idx, int64_t i, lfq_fasta_entry *entry);
+int64_t lfq_fasta_index_find(const lfq_fasta_index *idx, const char *name); /* -1: no such name */
+/* The whole contig `name`: the `length` graph bytes at or behind `offset`, in file order, case kept (every consumer of `ref` upper-
+ * cases for itself).  seq is pinned host memory with a NUL behind it, d_seq the same bytes on the device; both are the file's, valid
+ * until the next lfq_fasta_fetch on it or lfq_fasta_close.  WHILE IT IS VALID, a `ref` pointer inside [seq, seq + len) given to
+ * lfq_readset_create* on this context is copied device to device instead of across the link (lfq_readset_ref_from_device).
+ * The index may be a parsed one.  Its entry is checked before anything is launched: LFQ_ERR_INVALID when the name is not in the index,
+ * offset lies outside [0, n_bytes] or fewer than `length` graph bytes stand behind it.  Two kernels serve: LFQ_FASTA_PATH_REGULAR
+ * (base p from offset + p / line_blen * line_len + p % line_blen) only after a launch has proved from the line records that every line
+ * of the span but the last is line_blen graph bytes and '\n'; LFQ_FASTA_PATH_GENERAL (by graph rank) for everything else: blanks inside
+ * lines, "\r\n", an index that does not describe the file.  Blocks. */
+typedef struct lfq_fasta_contig {
+    const uint8_t *seq;
+    int64_t len;
+    const uint8_t *d_seq;
+} lfq_fasta_contig;
+int lfq_fasta_fetch(lfq_fasta *fa, const lfq_fasta_index *idx, const char *name, const lfq_fasta_contig **out);
+#define LFQ_FASTA_PATH_NONE 0       /* nothing fetched yet, or a contig of length 0 */
+#define LFQ_FASTA_PATH_REGULAR 1
+#define LFQ_FASTA_PATH_GENERAL 2
+/* the context's last lfq_fasta_open and what followed it: upload and download on the host's clock, the kernels on the device's.
+ * n_handovers: contigs read sets took from a live fetch result since that open */
+typedef struct lfq_fasta_times {
+    double upload_ms, scan_ms, lines_ms, fetch_ms, download_ms;
+    int64_t n_bytes, n_lines, n_headers, n_fetch_bytes;
+    int n_launches, n_from_device, fetch_path, n_handovers;
+} lfq_fasta_times;
+int lfq_last_fasta_times(lfq_ctx *ctx, lfq_fasta_times *t);
+int lfq_readset_ref_from_device(const lfq_readset *rs);     /* 1: this read set's contig came from a live fetch result */
+/* `lofreq checkref` (samutils.c:621-676; plp.c:1416 applies the same test): per @SQ of a BAM header, in order, the name must be in the
+ * index and the lengths equal.  The first failure ends it: *first_bad is its position (-1: none), *why says which.  Host only; the
+ * header's parse is the caller's.  LFQ_ERR_INVALID: idx NULL, n < 0, names / lens NULL with n > 0 */
+#define LFQ_CHECKREF_OK 0
+#define LFQ_CHECKREF_NO_SEQUENCE 1
+#define LFQ_CHECKREF_LENGTH 2
+int lfq_checkref(const lfq_fasta_index *idx, const char *const *names, const int64_t *lens, int64_t n, int64_t *first_bad_or_null,
+                 int *why_or_null);
+/* The .gzi `lofreq faidx` writes beside a bgzip-compressed FASTA, from the block tables of an lfq_bgzf_inflate result: a little-endian
+ * uint64 count, then per block with data behind the first such one the pair (compressed offset of the first block behind the previous
+ * block with data -- empty blocks in between belong to it --, uncompressed offset of the block).  *n_bytes is its size;
+ * out NULL: only that.  Host only.  LFQ_ERR_INVALID: res / n_bytes NULL, capacity below *n_bytes */
+int lfq_bgzf_gzi_bytes(const lfq_bgzf_result *res, uint8_t *out_or_null, int64_t capacity, int64_t *n_bytes);
 
 /* lfq_call_snvs_batch in two halves, for callers that keep more than one batch in flight (one context per batch in
  * flight): submit launches the kernels and returns; collect waits, fetches the sparse records and finishes them on

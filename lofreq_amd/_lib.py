@@ -290,6 +290,9 @@ EXPORTS = [
     "lfq_filter_conf_init", "lfq_filter_conf_defaults", "lfq_filter_vars", "lfq_filter_id", "lfq_filter_string",
     "lfq_filter_header_lines", "lfq_filter_var_from_snv", "lfq_filter_var_from_indel",
     "lfq_bed_parse", "lfq_bed_free", "lfq_bed_n_names", "lfq_bed_name", "lfq_bed_intervals", "lfq_bed_overlap", "lfq_set_bed",
+    "lfq_fasta_open", "lfq_fasta_close", "lfq_fasta_index_build", "lfq_fasta_index_text", "lfq_fasta_index_parse", "lfq_fasta_index_free",
+    "lfq_fasta_index_n", "lfq_fasta_index_n_duplicates", "lfq_fasta_index_name", "lfq_fasta_index_entry", "lfq_fasta_index_find",
+    "lfq_fasta_fetch", "lfq_last_fasta_times", "lfq_readset_ref_from_device", "lfq_checkref", "lfq_bgzf_gzi_bytes",
 ]
 
 class FilterConf(C.Structure):
@@ -311,6 +314,21 @@ _lib = None
 
 # lfq_host_allgather_fn (include/lofreq_amd.h): int (*)(void *user, int world, int rank, const void *send, void *recv, size_t bytes)
 HOST_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+
+
+class FastaEntry(C.Structure):
+    _fields_ = [("length", C.c_int64), ("offset", C.c_int64), ("line_blen", C.c_int32), ("line_len", C.c_int32)]
+
+
+class FastaContig(C.Structure):
+    _fields_ = [("seq", C.c_void_p), ("len", C.c_int64), ("d_seq", C.c_void_p)]
+
+
+class FastaTimes(C.Structure):
+    _fields_ = [("upload_ms", C.c_double), ("scan_ms", C.c_double), ("lines_ms", C.c_double), ("fetch_ms", C.c_double),
+                ("download_ms", C.c_double), ("n_bytes", C.c_int64), ("n_lines", C.c_int64), ("n_headers", C.c_int64),
+                ("n_fetch_bytes", C.c_int64), ("n_launches", C.c_int), ("n_from_device", C.c_int), ("fetch_path", C.c_int),
+                ("n_handovers", C.c_int)]
 
 
 def load():
@@ -495,6 +513,28 @@ def load():
                                     C.POINTER(C.c_int64)]
     L.lfq_bed_overlap.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int64]
     L.lfq_set_bed.argtypes = [vp, vp, C.c_char_p]
+    L.lfq_fasta_open.argtypes = [vp, vp, C.c_int64, C.POINTER(vp)]
+    L.lfq_fasta_close.argtypes = [vp]
+    L.lfq_fasta_close.restype = None
+    L.lfq_fasta_index_build.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.lfq_fasta_index_text.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_fasta_index_parse.argtypes = [C.c_char_p, C.c_int64, C.POINTER(vp)]
+    L.lfq_fasta_index_free.argtypes = [vp]
+    L.lfq_fasta_index_free.restype = None
+    L.lfq_fasta_index_n.argtypes = [vp]
+    L.lfq_fasta_index_n.restype = C.c_int64
+    L.lfq_fasta_index_n_duplicates.argtypes = [vp]
+    L.lfq_fasta_index_n_duplicates.restype = C.c_int64
+    L.lfq_fasta_index_name.argtypes = [vp, C.c_int64]
+    L.lfq_fasta_index_name.restype = C.c_char_p
+    L.lfq_fasta_index_entry.argtypes = [vp, C.c_int64, C.POINTER(FastaEntry)]
+    L.lfq_fasta_index_find.argtypes = [vp, C.c_char_p]
+    L.lfq_fasta_index_find.restype = C.c_int64
+    L.lfq_fasta_fetch.argtypes = [vp, vp, C.c_char_p, C.POINTER(C.POINTER(FastaContig))]
+    L.lfq_last_fasta_times.argtypes = [vp, C.POINTER(FastaTimes)]
+    L.lfq_readset_ref_from_device.argtypes = [vp]
+    L.lfq_checkref.argtypes = [vp, C.POINTER(C.c_char_p), vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.lfq_bgzf_gzi_bytes.argtypes = [C.POINTER(BgzfResult), vp, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 

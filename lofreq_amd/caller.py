@@ -135,6 +135,8 @@ class SnvCaller:
         if getattr(self, "h", None):
             for rs in list(getattr(self, "_readsets", ())):     # a read set is destroyed before its context
                 rs.close()
+            for fa in list(getattr(self, "_fastas", ())):       # ... and so is a resident FASTA (fasta.Fasta)
+                fa.close()
             self.L.lfq_destroy(self.h)
             self.h = None
 

@@ -12,6 +12,7 @@
  *   lfq_bgzf_deflate.hip   bytes cut into BGZF blocks and compressed on the device (over lfq_deflate.h)
  *   lfq_bamidx.hip         the .bai of a BAM from its records and block tables (over lfq_bamidx.h)
  *   lfq_bed.hip            the targets of `lofreq call -l`: the BED itself, lfq_set_bed, the read and column kernels (over lfq_bed.h)
+ *   lfq_fasta.hip          `lofreq faidx` and the contig of a FASTA: scan, line and entry kernels, both fetch paths (over lfq_fasta.h)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -435,7 +436,9 @@ struct lfq_ctx {
     struct LfqBgzfState *bgzf;       /* lfq_bgzf_inflate: its buffers, result and timing (lfq_bgzf.hip; created on first use) */
     struct LfqBgzfDefState *bgzf_def; /* lfq_bgzf_deflate: likewise (lfq_bgzf_deflate.hip) */
     struct LfqBamIdxState *bamidx;   /* lfq_bam_index_build: likewise (lfq_bamidx.hip) */
-    LfqBedDev *bed;                  /* lfq_set_bed: the targets the read sets created from now on take (null: none) */};
+    LfqBedDev *bed;                  /* lfq_set_bed: the targets the read sets created from now on take (null: none) */
+    struct LfqFastaState *fasta;     /* lfq_fasta_*: timing and the live fetch result (lfq_fasta.hip; created on first use) */
+};
 
 template <typename T>
 int grow(T **ptr, int64_t *cap, int64_t need)
@@ -604,6 +607,10 @@ const uint8_t *lfq_bgzf_resident_bytes(lfq_ctx *c, const uint8_t *p, int64_t byt
 const uint8_t *lfq_bam_framed_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 void lfq_bgzf_deflate_release(lfq_ctx *c);
 void lfq_bam_index_release(lfq_ctx *c);    /* lfq_bamidx.hip: what lfq_destroy frees of lfq_ctx::bamidx */
+/* lfq_fasta.hip.  What lfq_destroy frees of lfq_ctx::fasta; and for the read set's contig upload (lfq_readset.hip): the device address
+ * of host bytes [p, p + bytes) when they lie inside the context's live lfq_fasta_fetch result (counted as a hand-over), else null */
+void lfq_fasta_release(lfq_ctx *c);
+const uint8_t *lfq_fasta_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 /* lfq_bed.hip, for the read set (lfq_readset.hip).  keep_out[r] = 1 iff [pos, bam_endpos) of read r overlaps an interval, one lane
  * per read, from the resident start positions and CIGAR words; cov[p] (and nb[p], unless null) of every position of
  * [begin, begin + width) whose [p, p + 1) overlaps none go to 0, one lane per position: no column for the compaction behind it */

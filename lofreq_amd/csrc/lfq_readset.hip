@@ -153,6 +153,7 @@ struct lfq_readset {
     int bed_rc;
     std::vector<uint8_t> bed_keep;      /* [n] 1 = the read overlaps an interval */
     int64_t n_bed_kept;
+    bool ref_from_device;               /* the contig came from the context's live lfq_fasta_fetch result, device to device */
 };
 
 /* the reads, qualities, CIGARs and the contig are on the device (BI / BD may still be on their way: the BAQ kernels do
@@ -320,6 +321,7 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     rs->bed_valid = false;
     rs->bed_rc = LFQ_OK;
     rs->n_bed_kept = 0;
+    rs->ref_from_device = false;
     rs->has_lb = rs->has_idaq = rs->has_sqb = rs->has_bi = rs->has_bd = false;
     const int64_t n = rs->n, nb = rs->n_bases;
     {
@@ -366,12 +368,12 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     /* The order of the copies follows what lfq_readset_baq, usually the first step, needs: the small per-read arrays, then
      * bases and qualities in chunks of reads -- its launch over reads [a, b) starts when the chunks up to read b have
      * landed (readset_upload_wait_reads) --, BI / BD, which it does not read, last. */
-    struct Copy { uint8_t *dst; const void *src; int64_t bytes; int chunks_after, stage_after; };
+    struct Copy { uint8_t *dst; const void *src; int64_t bytes; int chunks_after, stage_after; bool from_device; };
     std::vector<Copy> todo;
     int64_t up_bytes = 0;
     auto add = [&](uint8_t *dst, const void *src, int64_t bytes) {
         if (src && bytes > 0) {
-            todo.push_back({dst, src, bytes, 0, 0});
+            todo.push_back({dst, src, bytes, 0, 0, false});
             up_bytes += bytes;
         }
     };
@@ -380,6 +382,13 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     add(rs->d_soff, rd->seq_off, (n + 1) * 8);
     add(rs->d_cig, rd->cigar, rs->n_cig * 4);
     add(rs->d_ref, rd->ref, rs->ref_len);
+    /* a contig that lfq_fasta_fetch left resident does not cross the link again */
+    if (const uint8_t *d_res = rs->ref_len > 0 ? lfq_fasta_resident(c, (const uint8_t *)rd->ref, rs->ref_len) : nullptr) {
+        todo.back().src = d_res;
+        todo.back().from_device = true;
+        up_bytes -= rs->ref_len;
+        rs->ref_from_device = true;
+    }
     add(rs->d_mapq, rd->mapq, n);
     add(rs->d_rev, rd->reverse, n);
     add(rs->d_lb, rd->baq, nb);
@@ -430,7 +439,7 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
     auto run = [rs, todo, n_chunks, device, ups]() {
         int rc = hipSetDevice(device) == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
         for (const Copy &x : todo) {
-            if (rc == LFQ_OK && hipMemcpyAsync(x.dst, x.src, (size_t)x.bytes, hipMemcpyHostToDevice, ups) != hipSuccess) {
+            if (rc == LFQ_OK && hipMemcpyAsync(x.dst, x.src, (size_t)x.bytes, x.from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ups) != hipSuccess) {
                 rc = LFQ_ERR_HIP;
             }
             if (x.chunks_after || x.stage_after) {      /* progress is published when the copies have landed */
@@ -464,7 +473,7 @@ static int readset_create(lfq_ctx *c, const lfq_pileup_reads *rd, const lfq_pile
         }
         bool stage0_done = false;
         for (const Copy &x : todo) {
-            if (rc == LFQ_OK && hipMemcpyAsync(x.dst, x.src, (size_t)x.bytes, hipMemcpyHostToDevice, ups) != hipSuccess) {
+            if (rc == LFQ_OK && hipMemcpyAsync(x.dst, x.src, (size_t)x.bytes, x.from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ups) != hipSuccess) {
                 rc = LFQ_ERR_HIP;
             }
             if (rc == LFQ_OK && x.chunks_after && hipEventRecord(rs->ev_chunk[x.chunks_after - 1], ups) != hipSuccess) {
@@ -895,6 +904,8 @@ static int readset_pileup_view(lfq_ctx *c, lfq_readset *rs, hipStream_t st, bool
     }
     return LFQ_OK;
 }
+
+int lfq_readset_ref_from_device(const lfq_readset *rs) { return rs && rs->ref_from_device ? 1 : 0; }
 
 int lfq_readset_kept_reads(lfq_ctx *c, lfq_readset *rs, uint8_t *keep_out, int64_t *n_kept_out)
 {

@@ -563,6 +563,9 @@ class ReadSet:
         rd.mapq, rd.reverse = keep["mapq"].ctypes.data, keep["rev"].ctypes.data
         rd.ref = C.cast(C.c_char_p(keep["ref"]), C.c_void_p)
         rd.ref_len = len(keep["ref"])
+        if hasattr(R["ref"], "seq_ptr"):            # a fasta.Contig: its own pointer, which the library recognises and hands over
+            keep["contig"] = R["ref"]               # on the device; it must stay the file's live fetch result while the read set lives
+            rd.ref = C.c_void_p(R["ref"].seq_ptr)
         if R.get("lb") is not None:
             keep["lb"] = np.ascontiguousarray(R["lb"], np.uint8)
             rd.baq = keep["lb"].ctypes.data
@@ -722,6 +725,11 @@ class ReadSet:
             self.close()
         except Exception:
             pass
+
+    @property
+    def ref_from_device(self):
+        """lfq_readset_ref_from_device: the contig was copied from a live Fasta.fetch result on the device, not across the link"""
+        return bool(self.L.lfq_readset_ref_from_device(self.h))
 
     def baq(self, extended=True, idaq=False):
         _lib.check(self.L.lfq_readset_baq(self.caller.h, self.h, 1 if extended else 0, 1 if idaq else 0), "lfq_readset_baq")

@@ -610,7 +610,7 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
      * columns; otherwise (a caller's array, or a submit whose collect may still ask for h_counts) only if the caller said
      * so (lfq_set_dense_counts) */
     P.sparse_counts = (P.lazy_strand && ((d_counts == c->d_counts && c->lazy_forced) || !c->dense_counts)) ? 1 : 0;
-    P.pad_ = 0;
+    P.scan_gate_maxk = 0;       /* (decided below, with bound_p_lo) */
     /* -t (snpcaller.c:1131); lofreq uniq hands snpcaller -1 (lofreq_uniq.c:311-312) */
     P.approx_n = (!P.detlim_af && conf->approx_threshold_n > 0) ? conf->approx_threshold_n : 0;
     LFQ_TRY(ensure_workspace(c, tr->ncols));
@@ -686,6 +686,13 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         const bool lb = !P.general && P.def_alt_bq == 0 && P.def_alt_jp < 0.0;
         P.bound_p_lo = (lb && !indel_mode && kn.bound_gate && lfq_count_is_lean(T, P, max_depth))
                            ? lfq_bound_p_lo(h_luts.bq, P.min_alt_bq4, LFQ_BOUND_QLO) : 0.0;
+        /* ... and its decision is made in the scan (lfq_scan_gate_kernel), for the MAXK of the screen variant this batch will
+         * launch, wherever a screen variant runs behind a plain scan: not with -t, whose second list pass and Poisson gate
+         * stay as they are, and not where the one-column-per-wavefront kernel takes the light class.  The columns the gate
+         * drops are then never listed: the screen kernel claims a list of survivors, the retry kernel walks their bytes. */
+        const int kreg = lfq_screen_kreg(c->kreg_hint);
+        const bool screen_runs = !kn.skip_light && kn.light_kernel != 2 && kreg > 0;
+        P.scan_gate_maxk = (P.bound_p_lo > 0.0 && P.approx_n == 0 && kn.scan_gate && screen_runs) ? kreg - 1 : 0;
     }
     const int64_t per_block = 3 * max_depth + 72;
     int n_big_blocks = c->n_cu;                         /* 8-wave workgroups: one per CU beside the light kernel */
@@ -737,12 +744,12 @@ int lfq_batch_device_impl(lfq_ctx *c, const lfq_conf *conf, const lfq_tracks *tr
         LFQ_TRY_HIP(hipEventRecord(c->ev_cnt[s][1], st));
 
         LFQ_TRY_HIP(hipStreamWaitEvent(dps, c->ev_cnt[s][1], 0));
-        LFQ_TRY(lfq_launch_scan(T, c0, c1, c->d_flags, d_counts, W, dps));
+        LFQ_TRY(lfq_launch_scan(T, c0, c1, P, c->d_flags, d_counts, W, dps));
         if (P.approx_n > 0) {
             /* -t: the Poisson gate over the listed columns, then the list without the ones it gave up */
             LFQ_TRY(grow(&c->d_approx_mu, &c->approx_mu_bytes, (c1 - c0) * 8));
             LFQ_TRY(lfq_launch_approx_gate(T, P, c->d_luts, d_counts, W, c1 - c0, (double *)c->d_approx_mu, c->d_flags, dps));
-            LFQ_TRY(lfq_launch_scan(T, c0, c1, c->d_flags, d_counts, W, dps, true));
+            LFQ_TRY(lfq_launch_scan(T, c0, c1, P, c->d_flags, d_counts, W, dps, true));
         }
         LFQ_TRY_HIP(hipEventRecord(c->ev_scan[s], dps));
         /* DP4 tuples of the mid / big class alleles with >= 16 alt bases -> host; Fisher tests start when they arrive.  On the

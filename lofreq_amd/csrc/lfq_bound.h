@@ -1,7 +1,8 @@
 /*
  * lfq_bound.h -- the binomial tail bound that gates light columns in front of the screen kernel's DP.
- * Host and device: lfq_dp_screen_kernel evaluates it per claimed column, the host computes p_lo beside the quality
- * tables, and tests/test_bound_gate.py compiles it with the host compiler into a stand-alone program.
+ * Host and device: lfq_scan_gate_kernel evaluates it per light column of a batch gated in the scan, lfq_dp_screen_kernel per
+ * claimed column of the others (lfq_bound_drops: one decision for both), the host computes p_lo beside the quality tables,
+ * and tests/test_bound_gate.py and tests/test_scan_gate.py compile it with the host compiler into a stand-alone program.
  *
  * The count kernel (lfq_count_column_lean) counts, on a fixed subset of a column, n_lo = the observations that are kept
  * rows whatever their allele (base code <= 3, bq >= max(min_bq, min_alt_bq)) and have bq <= LFQ_BOUND_QLO.  It is handed
@@ -107,6 +108,16 @@ LFQ_BOUND_FN double lfq_bound_tail(const LfqBoundTab *t, uint32_t code, int K)
         B += term;
     }
     return B;
+}
+
+/* THE decision: is a light column with the flag byte's statistic `code` and K alt bases dropped before its DP?  Stated once for
+ * the two places that make it -- lfq_scan_gate_kernel for a batch gated in the scan, lfq_dp_screen_kernel<.., GATE = true>
+ * for the others -- with the same operands in the same order, so that a knife-edge column falls the same way in both:
+ * bonf_d is the column's Bonferroni factor (lfq_bonf_of_prefix) as a double, sig_s = sig * (1 + prune_slack), maxk the
+ * launched screen variant's MAXK.  A column with K > maxk is not decided here: it goes to the retry kernel ungated. */
+LFQ_BOUND_FN bool lfq_bound_drops(const LfqBoundTab *t, uint32_t code, int K, int maxk, double bonf_d, double sig_s)
+{
+    return code != 0u && K <= maxk && lfq_bound_tail(t, code & (LFQ_BOUND_CODES - 1u), K) * bonf_d > sig_s;
 }
 
 #endif

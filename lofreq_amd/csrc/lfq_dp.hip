@@ -1097,7 +1097,7 @@ __global__ __launch_bounds__(256) void lfq_dp_retry_kernel(LfqTracksDev T, LfqPa
     __syncthreads();
     const int lane = lfq_lane();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int n_work = W.counters[LFQ_CNT_LIGHT];
+    const int n_work = W.counters[LFQ_CNT_LIST_LIGHT];
     const int n_waves_total = (int)gridDim.x * 4;
     LfqRow *rows = s_rows[wave];
     /* 16 list entries per wavefront and pass: flagged columns cluster (deep or noisy stretches), so a fine
@@ -1170,8 +1170,9 @@ __device__ __forceinline__ void lfq_screen_row(double (&v)[KREG], double p, doub
  * monotone in every p, so a tail computed from lower bounds that exceeds the pruning threshold proves that the exact
  * one does: the column is pruned a row or two later than it could be (the dropped terms are ~1 % of the error mass of
  * a typical column), never wrongly.  Everything the screen does not prune is redone exactly by the retry kernel.
- * GATE: the instantiation for batches whose count kernel left the bound gate's statistic in the entries (P.bound_p_lo > 0);
- * the other one is the kernel without a trace of it. */
+ * GATE: the instantiation for batches whose count kernel left the bound gate's statistic in the entries (P.bound_p_lo > 0)
+ * and whose scan did not make the decision itself (P.scan_gate_maxk == 0: the -t path, the tuning build's LFQ_SCAN_GATE=0);
+ * the other one is the kernel without a trace of it -- a batch gated in the scan lists only the columns the gate keeps. */
 template <int KREG, bool LB, bool GATE>
 __global__ __launch_bounds__(256) void lfq_dp_screen_kernel(LfqTracksDev T, LfqParams P,
                                                             const LfqLuts *__restrict__ g_luts, LfqWork W,
@@ -1192,7 +1193,7 @@ __global__ __launch_bounds__(256) void lfq_dp_screen_kernel(LfqTracksDev T, LfqP
     }
     __syncthreads();
     const int lane = lfq_lane();
-    const int n_work = W.counters[LFQ_CNT_LIGHT];
+    const int n_work = W.counters[LFQ_CNT_LIST_LIGHT];
     const LfqEntry *list = W.entries;               /* the light class leads the work list */
     const double sig_s = P.sig * (1.0 + P.prune_slack);
     const LfqEvalMasks EM = lfq_eval_masks(P);
@@ -1248,7 +1249,7 @@ __global__ __launch_bounds__(256) void lfq_dp_screen_kernel(LfqTracksDev T, LfqP
                     n_retry++;
                 } else {
                     int64_t bonf = P.bonf_base;
-                    if (P.bonf_dynamic) {           /* lfq_col_setup */
+                    if (P.bonf_dynamic) {           /* lfq_col_setup, lfq_bonf_of_prefix */
                         bonf = ((P.bonf_reset_first && P.bonf_base == 1) ? 0 : P.bonf_base)
                                + (int64_t)P.bonf_step * (int)b.x;
                     }
@@ -1258,7 +1259,7 @@ __global__ __launch_bounds__(256) void lfq_dp_screen_kernel(LfqTracksDev T, LfqP
                      * (neither rows nor cells to account for, no retry): the lane stays free and claims again */
                     active = true;
                     if constexpr (GATE) {
-                        active = !(b.w != 0u && lfq_bound_tail(&s_bound, b.w & (LFQ_BOUND_CODES - 1u), K) * bonf_d > sig_s);
+                        active = !lfq_bound_drops(&s_bound, b.w, K, MAXK, bonf_d, sig_s);
                     }
                     off0 = ((uint64_t)a.y << 32) | a.x;
                     n_obs = (int)a.z;
@@ -1605,7 +1606,7 @@ __global__ __launch_bounds__(LFQ_HEAVY_WAVES * 64, LFQ_DP512_WAVES) void lfq_dp_
         }
         /* the columns lfq_dp_big_prep_kernel could not (or need not) cut into row segments */
         const int h = W.unsplit[sh.col];
-        const LfqEntry en = lfq_load_entry(W.entries + W.counters[LFQ_CNT_LIGHT] + W.counters[LFQ_CNT_MID], h);
+        const LfqEntry en = lfq_load_entry(W.entries + W.counters[LFQ_CNT_LIST_LIGHT] + W.counters[LFQ_CNT_MID], h);
         const lfq_col_counts cnt = counts[en.col];
         LfqColCtx cx;
         lfq_col_setup(cx, en, P);
@@ -1683,7 +1684,7 @@ __global__ __launch_bounds__(LFQ_PREP_WAVES * 64, LFQ_DP512_WAVES) void lfq_dp_b
         if (h >= n_big) {
             break;
         }
-        const LfqEntry en = lfq_load_entry(W.entries + W.counters[LFQ_CNT_LIGHT] + W.counters[LFQ_CNT_MID], h);
+        const LfqEntry en = lfq_load_entry(W.entries + W.counters[LFQ_CNT_LIST_LIGHT] + W.counters[LFQ_CNT_MID], h);
         const lfq_col_counts cnt = counts[en.col];
         LfqColCtx cx;
         lfq_col_setup(cx, en, P);
@@ -2770,7 +2771,7 @@ __global__ __launch_bounds__(256) void lfq_approx_mu_kernel(LfqTracksDev T, LfqP
                                                             const lfq_col_counts *__restrict__ counts, LfqWork W,
                                                             double *__restrict__ mu_out)
 {
-    const int n_list = W.counters[LFQ_CNT_LIGHT] + W.counters[LFQ_CNT_MID] + W.counters[LFQ_CNT_BIG];
+    const int n_list = W.counters[LFQ_CNT_LIST_LIGHT] + W.counters[LFQ_CNT_MID] + W.counters[LFQ_CNT_BIG];
     const int n_waves = (int)gridDim.x * 4;
     const int lane = lfq_lane();
     for (int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); i < n_list; i += n_waves) {
@@ -2854,7 +2855,7 @@ __device__ double lfq_poisson_tail(int k, double mu)
 __global__ __launch_bounds__(256) void lfq_approx_gate_kernel(LfqParams P, LfqWork W, const double *__restrict__ mu_in,
                                                               uint8_t *__restrict__ flags)
 {
-    const int n_list = W.counters[LFQ_CNT_LIGHT] + W.counters[LFQ_CNT_MID] + W.counters[LFQ_CNT_BIG];
+    const int n_list = W.counters[LFQ_CNT_LIST_LIGHT] + W.counters[LFQ_CNT_MID] + W.counters[LFQ_CNT_BIG];
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i >= n_list) {
         return;
@@ -2896,7 +2897,7 @@ int lfq_launch_dp_light(const LfqTracksDev &t, const LfqParams &p, const LfqLuts
     }
     const unsigned blocks = (unsigned)((n_waves + 3) / 4);
     hipLaunchKernelGGL(lfq_dp_wave_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, p, d_luts,
-                       d_counts, w, -1, LFQ_CNT_LIGHT, d_pvals, pvals_capacity, 32, 0);
+                       d_counts, w, -1, LFQ_CNT_LIST_LIGHT, d_pvals, pvals_capacity, 32, 0);
     return hipGetLastError() == hipSuccess ? LFQ_OK : LFQ_ERR_HIP;
 }
 
@@ -2913,7 +2914,7 @@ int lfq_launch_dp_mid(const LfqTracksDev &t, const LfqParams &p, const LfqLuts *
     const dim3 grid((unsigned)((n_waves + wg_waves - 1) / wg_waves)), block(64u * wg_waves);
 #define LFQ_LAUNCH_MID(WG)                                                                                          \
     hipLaunchKernelGGL((lfq_dp_wave_kernel<4, WG>), grid, block, 0, (hipStream_t)stream, t, p, d_luts, d_counts, w, \
-                       LFQ_CNT_LIGHT, LFQ_CNT_MID, d_pvals, pvals_capacity, 1, 0)
+                       LFQ_CNT_LIST_LIGHT, LFQ_CNT_MID, d_pvals, pvals_capacity, 1, 0)
     if (wg_waves == 4) {
         LFQ_LAUNCH_MID(4);
     } else if (wg_waves == 8) {
@@ -3031,19 +3032,20 @@ int lfq_launch_dp_quad(const LfqTracksDev &t, const LfqParams &p, const LfqLuts 
     const dim3 grid((unsigned)((n_waves + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
     const LfqKnobs &kn = lfq_knobs();
-    int force = 0;
     if (phase != 2) {
         /* one light column per lane: ONE variant is launched, chosen on the host from the K histogram the scan of this
          * context's previous batch left behind (a batch cannot wait for its own scan without stalling the host).  Any
          * choice is correct: a column with more alt bases than the variant has cells goes to the retry kernel. */
-        if (!force) {
-            force = kreg_hint > 0 ? kreg_hint : 8;
+        const int kreg = lfq_screen_kreg(kreg_hint);
+        /* (a batch gated in the scan was gated for this variant's MAXK: lfq_batch_device_impl derives both from the hint) */
+        if (p.scan_gate_maxk > 0 && p.scan_gate_maxk != kreg - 1) {
+            return LFQ_ERR_INVALID;
         }
         /* lower-bound evaluation where the filters allow it (see the kernel) */
         const bool lb = !p.general && p.def_alt_bq == 0 && p.def_alt_jp < 0.0;
 #define LFQ_LAUNCH_SCREEN(KR)                                                                                        \
     do {                                                                                                             \
-        if (lb && p.bound_p_lo > 0.0) {                                                                              \
+        if (lb && p.bound_p_lo > 0.0 && p.scan_gate_maxk == 0) {                                                     \
             hipLaunchKernelGGL((lfq_dp_screen_kernel<KR, true, true>), grid, block, 0, st, t, p, d_luts, w, d_retry, \
                                kn.screen_rounds);                                                                    \
         } else if (lb) {                                                                                             \
@@ -3054,16 +3056,20 @@ int lfq_launch_dp_quad(const LfqTracksDev &t, const LfqParams &p, const LfqLuts 
                                kn.screen_rounds);                                                                    \
         }                                                                                                            \
     } while (0)
-        if (force <= 6) LFQ_LAUNCH_SCREEN(6);
-        else if (force <= 8) LFQ_LAUNCH_SCREEN(8);
-        else if (force <= 10) LFQ_LAUNCH_SCREEN(10);
-        else if (force <= 12) LFQ_LAUNCH_SCREEN(12);
-        else if (force <= 16) LFQ_LAUNCH_SCREEN(16);
-        else if (force <= 24) LFQ_LAUNCH_SCREEN(24);
-        else if (force <= 32) LFQ_LAUNCH_SCREEN(32);
-        else {
-            hipLaunchKernelGGL(lfq_dp_wave_kernel<1>, grid, block, 0, st, t, p, d_luts, d_counts, w, -1, LFQ_CNT_LIGHT,
+        switch (kreg) {                             /* every value lfq_screen_kreg returns */
+        case 6: LFQ_LAUNCH_SCREEN(6); break;
+        case 8: LFQ_LAUNCH_SCREEN(8); break;
+        case 10: LFQ_LAUNCH_SCREEN(10); break;
+        case 12: LFQ_LAUNCH_SCREEN(12); break;
+        case 16: LFQ_LAUNCH_SCREEN(16); break;
+        case 24: LFQ_LAUNCH_SCREEN(24); break;
+        case 32: LFQ_LAUNCH_SCREEN(32); break;
+        case 0:                                     /* a hint beyond the widest variant */
+            hipLaunchKernelGGL(lfq_dp_wave_kernel<1>, grid, block, 0, st, t, p, d_luts, d_counts, w, -1, LFQ_CNT_LIST_LIGHT,
                                d_pvals, pvals_capacity, 32, 0);
+            break;
+        default:
+            return LFQ_ERR_INVALID;
         }
 #undef LFQ_LAUNCH_SCREEN
     }

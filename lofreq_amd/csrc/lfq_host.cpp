@@ -106,6 +106,7 @@ const LfqKnobs &lfq_knobs(void)
         x.pileup_atomic = LFQ_TUNE_HAS("LFQ_PILEUP_ATOMIC");
         x.baq_lds = LFQ_TUNE_I("LFQ_BAQ_LDS", 1) != 0;
         x.bound_gate = LFQ_TUNE_I("LFQ_BOUND_GATE", 1) != 0;
+        x.scan_gate = LFQ_TUNE_I("LFQ_SCAN_GATE", 1) != 0;
         {
             const long w = LFQ_TUNE_I("LFQ_DP_WG_WAVES", 0);
             x.dp_wg_waves = w <= 0 ? 0 : (w >= 16 ? 16 : (w >= 8 ? 8 : 4));

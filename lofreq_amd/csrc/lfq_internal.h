@@ -49,7 +49,9 @@ struct LfqParams {
     int32_t approx_n;         /* > 0: columns with more error probabilities than this pass the Poisson gate first (snpcaller.c:1131) */
     int32_t sparse_counts;    /* 1: the shared-wavefront count kernel writes the dense entry of a column only if it is tested (nothing
                                * on the device reads the others: lfq_set_dense_counts) */
-    int32_t pad_;
+    int32_t scan_gate_maxk;   /* > 0: the scan makes the bound gate's decision (lfq_scan_gate_kernel) and lists only the light columns it
+                               * keeps; the value is MAXK of the screen variant this batch launches (lfq_screen_kreg() - 1).  0: the
+                               * screen kernel gates at claim time (or nothing does: bound_p_lo == 0) */
     double bound_p_lo;        /* the screen kernel's bound gate (lfq_bound.h): smallest bq-table entry a counted row can have; 0 = gate off */
 };
 
@@ -80,6 +82,23 @@ struct LfqEntry {
 /* the class byte the count kernels write per column: bit 0 tested, bit 1 mid, bit 2 big; bits 3..7 the bound gate's
  * statistic (lfq_count_column_lean only) */
 #define LFQ_FLAG_NLO_SHIFT 3
+/* ... and in a batch gated in the scan (LfqParams::scan_gate_maxk), from lfq_scan_gate_kernel on: the statistic of a light
+ * column is spent, and its five bits say what was decided -- this value = dropped (a tested column without a list entry),
+ * 0 = listed.  Mid and big columns keep their bits; nothing reads them. */
+#define LFQ_FLAG_DROPPED (1u << LFQ_FLAG_NLO_SHIFT)
+
+/* the running Bonferroni factor of the column whose inclusive tested prefix is `prefix` (lofreq_call.c:794-800) */
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline int64_t lfq_bonf_of_prefix(const LfqParams &P, int prefix)
+{
+    int64_t bonf = P.bonf_base;
+    if (P.bonf_dynamic) {
+        bonf = ((P.bonf_reset_first && P.bonf_base == 1) ? 0 : P.bonf_base) + (int64_t)P.bonf_step * prefix;
+    }
+    return bonf;
+}
 
 /* ---- row-split ("long") columns ------------------------------------------------------------------
  * The rows of a column are independent Bernoulli trials, so the count distribution of the whole column is
@@ -140,11 +159,19 @@ static inline int lfq_khist_thr(int f)
 {
     return f == 0 ? 5 : f == 1 ? 7 : f == 2 ? 9 : f == 3 ? 11 : f == 4 ? 15 : f == 5 ? 23 : 31;
 }
+/* KREG of the screen variant lfq_launch_dp_quad launches for a context's hint (0 = none yet: 8); 0 = beyond the widest one, the
+ * one-column-per-wavefront kernel runs instead */
+static inline int lfq_screen_kreg(int kreg_hint)
+{
+    const int want = kreg_hint > 0 ? kreg_hint : 8;
+    return want <= 6 ? 6 : want <= 8 ? 8 : want <= 10 ? 10 : want <= 12 ? 12 : want <= 16 ? 16 : want <= 24 ? 24 : want <= 32 ? 32 : 0;
+}
 
 /* work lists and counters produced by the scan kernels, consumed by the DP kernel */
 struct LfqWork {
     int32_t *tested_prefix;   /* [ncols] inclusive count of tested columns up to and incl. c */
-    LfqEntry *entries;        /* this segment's work list: [light | mid | big] = [kmax < LFQ_MID_K | < LFQ_BIG_K | rest] */
+    LfqEntry *entries;        /* this segment's work list: [light | mid | big] = [kmax < LFQ_MID_K | < LFQ_BIG_K | rest]; the light part
+                               * holds the LISTED light columns, LFQ_CNT_LIST_LIGHT of them (all of the class unless the scan gated) */
     int32_t *gcounters;       /* batch-wide counters shared by all segments, see LFQ_GC_* */
     int32_t *counters;        /* [16] of this segment, see LFQ_CNT_* */
     int32_t *block_sums;      /* scan scratch */
@@ -171,7 +198,9 @@ struct LfqWork {
 #define LFQ_CNT_TESTED 0
 #define LFQ_CNT_BIG 1
 #define LFQ_CNT_MID 2
-#define LFQ_CNT_LIGHT 3
+#define LFQ_CNT_LIGHT 3        /* light columns of the segment (the class size: lfq_dp_work.n_light, the screen variant's hint) */
+#define LFQ_CNT_LIST_LIGHT 31  /* length of the light part of the work list: what every kernel that walks or skips it reads.  Equal to
+                                * LFQ_CNT_LIGHT unless the scan dropped columns (LfqParams::scan_gate_maxk) */
 #define LFQ_CNT_HEAD 4        /* dequeue head of the big-column list */
 #define LFQ_CNT_CARRY_IN 15    /* tested columns in earlier segments of the batch */
 #define LFQ_CNT_HEAD_LIGHT 12  /* dynamic work distribution of the wave-per-column kernels */
@@ -270,6 +299,8 @@ struct LfqKnobs {
     long baq_scratch_mb;       /* LFQ_BAQ_SCRATCH_MB: -1 = from free HBM */
     int private_stream;        /* LFQ_PRIVATE_STREAM (0): lfq_create gives every context a launch stream of its own (lfq_set_private_stream) */
     int bound_gate;            /* LFQ_BOUND_GATE (1): 0 = every light column runs the screen's DP (A/B of the bound gate, lfq_bound.h) */
+    int scan_gate;             /* LFQ_SCAN_GATE (1): 0 = the bound gate's decision stays in the screen kernel and every light column is listed
+                                * (A/B of the gate in the scan, lfq_scan_gate_kernel) */
     int dp_wg_waves;           /* LFQ_DP_WG_WAVES (0 = 4): 4 / 8 / 16 wavefronts per workgroup of the mid kernel and the row-segment kernels of
                                 * a context that queues its batches without a gate (lfq_batch_device_impl) */
 };
@@ -515,7 +546,9 @@ int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqPar
                      lfq_col_counts *d_counts, uint8_t *d_flags, int64_t max_col_obs, void *stream, bool shallow_half_cu = false);
 /* (shallow_half_cu: the shared-wavefront count kernel keeps two workgroups per CU resident instead of as many as fit) */
 bool lfq_count_is_lean(const LfqTracksDev &t, const LfqParams &p, int64_t max_col_obs);
-int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const uint8_t *d_flags,
+/* p.scan_gate_maxk > 0 (never with relist): two more launches between the sums and the apply kernel make the bound gate's
+ * decision and rewrite the flag bytes of the light columns (LFQ_FLAG_DROPPED) */
+int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqParams &p, uint8_t *d_flags,
                     const lfq_col_counts *d_counts, const LfqWork &w, void *stream, bool relist = false);
 /* -t / --approx-threshold (snpcaller.c:1128-1142): clears the flag byte of the listed columns the Poisson gate gives up;
  * lfq_launch_scan(..., relist = true) then rebuilds the work list without them.  d_mu: one double per column of the segment */

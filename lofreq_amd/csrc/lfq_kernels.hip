@@ -1512,6 +1512,7 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_sums_kernel(int64_t
             counters[LFQ_CNT_MID] = (int32_t)carry.m;
             counters[LFQ_CNT_BIG] = (int32_t)carry.b;
             counters[LFQ_CNT_LIGHT] = (int32_t)(carry.t - carry.m - carry.b);
+            counters[LFQ_CNT_LIST_LIGHT] = (int32_t)(carry.t - carry.m - carry.b);
         }
         if (threadIdx.x < 3) {                      /* the K histograms of the light class are counted again */
             counters[LFQ_CNT_KLE7 + (int)threadIdx.x] = 0;
@@ -1526,6 +1527,8 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_sums_kernel(int64_t
         counters[LFQ_CNT_MID] = (int32_t)carry.m;
         counters[LFQ_CNT_BIG] = (int32_t)carry.b;
         counters[LFQ_CNT_LIGHT] = (int32_t)(carry.t - carry.m - carry.b);
+        /* (every light column is listed unless lfq_scan_drop_sums_kernel, behind this kernel, says otherwise) */
+        counters[LFQ_CNT_LIST_LIGHT] = (int32_t)(carry.t - carry.m - carry.b);
         /* running Bonferroni carry between the segments of a batch (stream-ordered) */
         const int32_t before = gcounters[LFQ_GC_TESTED];
         counters[LFQ_CNT_CARRY_IN] = before;
@@ -1533,13 +1536,169 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_sums_kernel(int64_t
     }
 }
 
-template <bool RELIST>
+/* K histograms of the light class (LFQ_CNT_KLE*, LFQ_CNT_KHIST: the screen variant of the context's next batch follows them),
+ * over ALL its columns, listed or not: counted by the apply kernel, or by the gate kernel where one runs */
+struct LfqKHist {
+    uint32_t kle7, kle15, kle31;
+    unsigned long long fine;        /* the screen kernel's register variants: 9-bit fields, <= 4 columns per thread */
+};
+
+__device__ __forceinline__ void lfq_khist_add(LfqKHist &h, int kmax)
+{
+    h.kle7 += kmax <= 7;
+    h.kle15 += kmax <= 15;
+    h.kle31 += kmax <= 31;
+#pragma unroll
+    for (int f = 0; f < LFQ_NKHIST; f++) {
+        h.fine += (unsigned long long)(kmax <= lfq_khist_thr(f)) << (9 * f);
+    }
+}
+
+/* every thread of the workgroup calls it; s_k: 3 + LFQ_NKHIST words of LDS.  One set of global atomics per workgroup (per
+ * wavefront they contend: +0.1 ms on a 1 M column batch) */
+__device__ __forceinline__ void lfq_khist_flush(LfqKHist h, uint32_t *s_k, int32_t *counters)
+{
+    if (threadIdx.x < 3 + LFQ_NKHIST) {
+        s_k[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    h.kle7 = lfq_wave_sum_u32(h.kle7);
+    h.kle15 = lfq_wave_sum_u32(h.kle15);
+    h.kle31 = lfq_wave_sum_u32(h.kle31);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        h.fine += __shfl_xor(h.fine, d, 64);        /* 64 lanes x <= 4: every field stays below 2^9 */
+    }
+    if (lfq_lane() == 0 && h.kle31) {
+        atomicAdd(&s_k[0], h.kle7);
+        atomicAdd(&s_k[1], h.kle15);
+        atomicAdd(&s_k[2], h.kle31);
+#pragma unroll
+        for (int f = 0; f < LFQ_NKHIST; f++) {
+            atomicAdd(&s_k[3 + f], (uint32_t)((h.fine >> (9 * f)) & 511ull));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_k[2]) {
+        atomicAdd(&counters[LFQ_CNT_KLE7 + (int)threadIdx.x], (int)s_k[threadIdx.x]);
+    }
+    if (threadIdx.x >= 3 && threadIdx.x < 3 + LFQ_NKHIST && s_k[2]) {
+        atomicAdd(&counters[LFQ_CNT_KHIST + (int)threadIdx.x - 3], (int)s_k[threadIdx.x]);
+    }
+}
+
+/* Only for a flag byte that lfq_scan_gate_kernel has rewritten: the same byte from a count kernel is a light column whose
+ * n_lo code is 1.  lfq_scan_apply_kernel<.., GATED> is launched strictly behind a gate kernel that rewrote the byte of every
+ * light column of the segment (lfq_launch_scan), and nothing else calls this. */
+__device__ __forceinline__ bool lfq_flag_is_dropped(uint32_t f) { return f == (1u | LFQ_FLAG_DROPPED); }
+
+/* The bound gate (lfq_bound.h) decided in the scan, for a batch with LfqParams::scan_gate_maxk: between the sums and the
+ * apply kernel, same tiling as the apply kernel.  Every light column's decision needs its n_lo code (the flag byte), its K
+ * and its Bonferroni factor, i.e. its inclusive tested prefix -- recomputed here exactly as the apply kernel stores it in
+ * LfqEntry::prefix: the tile's exclusive sum + the scan inside the tile + the batch's carry-in.  The flag byte of a light
+ * column is rewritten (LFQ_FLAG_DROPPED or 0 in the statistic's bits), the tile's count of dropped columns goes to
+ * tile_drop.  No atomic decides a position and no workgroup waits for another: positions come from the two scans. */
+__global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_gate_kernel(int64_t c0, int64_t c1, LfqParams P,
+                                                                        uint8_t *__restrict__ flags,
+                                                                        const lfq_col_counts *__restrict__ counts,
+                                                                        const LfqTriple *__restrict__ tile_sums,
+                                                                        uint32_t *__restrict__ tile_drop,
+                                                                        int32_t *__restrict__ counters)
+{
+    __shared__ LfqTriple s_wave[16];
+    __shared__ LfqBoundTab s_bound;
+    __shared__ uint32_t s_k[3 + LFQ_NKHIST];
+    __shared__ uint32_t s_drop;
+    if (threadIdx.x < LFQ_BOUND_CODES) {            /* the gate's two small tables, as the screen kernel builds them */
+        s_bound.qm[threadIdx.x] = lfq_bound_qm(P.bound_p_lo, threadIdx.x);
+    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + LFQ_BOUND_NRK) {
+        s_bound.rk[threadIdx.x - 64] = lfq_bound_rk(P.bound_p_lo, (int)threadIdx.x - 64);
+    }
+    if (threadIdx.x == 0) {
+        s_drop = 0;
+    }
+    __syncthreads();
+    const int64_t ncols = c1;
+    const int64_t base = c0 + (int64_t)blockIdx.x * LFQ_SCAN_TILE + (int64_t)threadIdx.x * LFQ_SCAN_ITEMS;
+    uint32_t f[LFQ_SCAN_ITEMS];
+    LfqTriple x = {0, 0, 0};
+    for (int i = 0; i < LFQ_SCAN_ITEMS; i++) {
+        f[i] = (base + i < ncols) ? flags[base + i] : 0u;
+        lfq_triple_add(x, lfq_triple_of_flag(f[i]));
+    }
+    LfqTriple total;
+    LfqTriple ex = lfq_block_excl_scan(x, &total, s_wave);
+    lfq_triple_add(ex, tile_sums[blockIdx.x]);
+    const uint32_t carry_in = (uint32_t)counters[LFQ_CNT_CARRY_IN];
+    const double sig_s = P.sig * (1.0 + P.prune_slack);
+    uint32_t n_drop = 0;
+    LfqKHist kh = {0, 0, 0, 0};
+    for (int i = 0; i < LFQ_SCAN_ITEMS; i++) {
+        const int64_t c = base + i;
+        if (c >= ncols) {
+            break;
+        }
+        if (!(f[i] & 1u)) {
+            continue;
+        }
+        ex.t++;
+        if (f[i] & 6u) {
+            continue;
+        }
+        const int K = counts[c].kmax;
+        lfq_khist_add(kh, K);
+        const double bonf_d = (double)lfq_bonf_of_prefix(P, (int)(int32_t)(carry_in + ex.t));
+        const bool drop = lfq_bound_drops(&s_bound, f[i] >> LFQ_FLAG_NLO_SHIFT, K, P.scan_gate_maxk, bonf_d, sig_s);
+        n_drop += drop ? 1u : 0u;
+        flags[c] = (uint8_t)(1u | (drop ? LFQ_FLAG_DROPPED : 0u));
+    }
+    n_drop = lfq_wave_sum_u32(n_drop);
+    if (lfq_lane() == 0 && n_drop) {
+        atomicAdd(&s_drop, n_drop);                 /* (a sum in LDS: its order decides nothing) */
+    }
+    lfq_khist_flush(kh, s_k, counters);             /* (its barriers order s_drop as well) */
+    if (threadIdx.x == 0) {
+        tile_drop[blockIdx.x] = s_drop;
+    }
+}
+
+/* single block: exclusive scan over the tiles' dropped counts; the list's light part is what is left of the class */
+__global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_drop_sums_kernel(int64_t ntiles, uint32_t *__restrict__ tile_drop,
+                                                                             int32_t *__restrict__ counters)
+{
+    __shared__ LfqTriple s_wave[16];
+    uint32_t carry = 0;
+    for (int64_t b = 0; b < ntiles; b += LFQ_SCAN_THREADS) {
+        const int64_t i = b + threadIdx.x;
+        LfqTriple x = {0, 0, 0};
+        if (i < ntiles) {
+            x.t = tile_drop[i];
+        }
+        LfqTriple total;
+        const LfqTriple ex = lfq_block_excl_scan(x, &total, s_wave);
+        if (i < ntiles) {
+            tile_drop[i] = carry + ex.t;
+        }
+        carry += total.t;
+    }
+    if (threadIdx.x == 0) {
+        counters[LFQ_CNT_LIST_LIGHT] = counters[LFQ_CNT_LIGHT] - (int32_t)carry;
+    }
+}
+
+/* GATED: a batch whose light columns lfq_scan_gate_kernel decided (never RELIST).  A dropped column gets its tested_prefix
+ * and no entry; a listed light column sits at its rank among the light columns minus the dropped ones in front of it -- the
+ * tiles' share of those from lfq_scan_drop_sums_kernel (tile_drop), the rest scanned here -- so `light` in the list layout
+ * means `listed light`, LFQ_CNT_LIST_LIGHT of them.  The K histograms were counted by the gate kernel. */
+template <bool RELIST, bool GATED>
 __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_apply_kernel(LfqTracksDev T, int64_t c0, int64_t c1,
                                                                          const uint8_t *__restrict__ flags,
                                                                          const lfq_col_counts *__restrict__ counts,
                                                                          const LfqTriple *__restrict__ tile_sums,
+                                                                         const uint32_t *__restrict__ tile_drop,
                                                                          LfqWork W)
 {
+    static_assert(!(RELIST && GATED), "the -t path is not gated in the scan");
     __shared__ LfqTriple s_wave[16];
     const int64_t ncols = c1;
     const int64_t base = c0 + (int64_t)blockIdx.x * LFQ_SCAN_TILE + (int64_t)threadIdx.x * LFQ_SCAN_ITEMS;
@@ -1552,16 +1711,30 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_apply_kernel(LfqTra
     LfqTriple total;
     LfqTriple ex = lfq_block_excl_scan(x, &total, s_wave);
     lfq_triple_add(ex, tile_sums[blockIdx.x]);
-    /* list layout [light | mid | big]; the class totals were published by lfq_scan_sums_kernel */
-    const uint32_t base_mid = (uint32_t)W.counters[LFQ_CNT_LIGHT];
+    uint32_t ex_drop = 0;                          /* GATED: dropped light columns in front of this thread's first column */
+    if (GATED) {
+        LfqTriple d = {0, 0, 0}, d_total;
+        for (int i = 0; i < LFQ_SCAN_ITEMS; i++) {
+            d.t += lfq_flag_is_dropped(f[i]) ? 1u : 0u;
+        }
+        ex_drop = lfq_block_excl_scan(d, &d_total, s_wave).t + tile_drop[blockIdx.x];
+    }
+    /* list layout [light | mid | big]; the list sizes were published by lfq_scan_sums_kernel (GATED: and
+     * lfq_scan_drop_sums_kernel) */
+    const uint32_t base_mid = (uint32_t)W.counters[LFQ_CNT_LIST_LIGHT];
     const uint32_t base_big = base_mid + (uint32_t)W.counters[LFQ_CNT_MID];
     const uint32_t carry_in = (uint32_t)W.counters[LFQ_CNT_CARRY_IN];
-    uint32_t kle7 = 0, kle15 = 0, kle31 = 0;       /* K histogram of the light class (lfq_light_group_lanes) */
-    unsigned long long khist = 0;
+    LfqKHist kh = {0, 0, 0, 0};
     for (int i = 0; i < LFQ_SCAN_ITEMS; i++) {
         const int64_t c = base + i;
         if (c >= ncols) {
             break;
+        }
+        if (GATED && lfq_flag_is_dropped(f[i])) {   /* tested and counted, not listed */
+            ex.t++;
+            ex_drop++;
+            W.tested_prefix[c] = (int32_t)(carry_in + ex.t);
+            continue;
         }
         if (f[i] & 1u) {
             uint32_t pos;
@@ -1571,14 +1744,9 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_apply_kernel(LfqTra
             } else if (f[i] & 2u) {
                 pos = base_mid + ex.m++;
             } else {
-                pos = ex.t - ex.m - ex.b;
-                kle7 += cn->kmax <= 7;
-                kle15 += cn->kmax <= 15;
-                kle31 += cn->kmax <= 31;
-                /* finer histogram for the screen kernel's register variants: 9-bit fields, <= 4 per thread */
-#pragma unroll
-                for (int f = 0; f < LFQ_NKHIST; f++) {
-                    khist += (unsigned long long)(cn->kmax <= lfq_khist_thr(f)) << (9 * f);
+                pos = ex.t - ex.m - ex.b - ex_drop;
+                if (!GATED) {
+                    lfq_khist_add(kh, cn->kmax);
                 }
             }
             ex.t++;
@@ -1593,41 +1761,17 @@ __global__ __launch_bounds__(LFQ_SCAN_THREADS) void lfq_scan_apply_kernel(LfqTra
             e.median_ref_bq = (int16_t)cn->median_ref_bq;
             e.ref_code = (uint8_t)((rb == 'A') ? 0 : (rb == 'C') ? 1 : (rb == 'G') ? 2 : 3);
             e.pad_ = 0;
-            e.pad2_ = (f[i] & 6u) ? 0 : (int32_t)(f[i] >> LFQ_FLAG_NLO_SHIFT);     /* light: the bound gate's n_lo code */
+            /* light: the bound gate's n_lo code for the screen kernel (GATED: spent -- the gate kernel left 0 in those bits) */
+            e.pad2_ = (GATED || (f[i] & 6u)) ? 0 : (int32_t)(f[i] >> LFQ_FLAG_NLO_SHIFT);
             W.entries[pos] = e;
         }
         if (!RELIST) {
             W.tested_prefix[c] = (int32_t)(carry_in + ex.t);   /* inclusive, batch-wide */
         }
     }
-    /* one set of global atomics per workgroup (per wavefront they contend: +0.1 ms on a 1 M column batch) */
-    __shared__ uint32_t s_k[3 + LFQ_NKHIST];
-    if (threadIdx.x < 3 + LFQ_NKHIST) {
-        s_k[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    kle7 = lfq_wave_sum_u32(kle7);
-    kle15 = lfq_wave_sum_u32(kle15);
-    kle31 = lfq_wave_sum_u32(kle31);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        khist += __shfl_xor(khist, d, 64);          /* 64 lanes x <= 4: every field stays below 2^9 */
-    }
-    if (lfq_lane() == 0 && kle31) {
-        atomicAdd(&s_k[0], kle7);
-        atomicAdd(&s_k[1], kle15);
-        atomicAdd(&s_k[2], kle31);
-#pragma unroll
-        for (int f = 0; f < LFQ_NKHIST; f++) {
-            atomicAdd(&s_k[3 + f], (uint32_t)((khist >> (9 * f)) & 511ull));
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && s_k[2]) {
-        atomicAdd(&W.counters[LFQ_CNT_KLE7 + (int)threadIdx.x], (int)s_k[threadIdx.x]);
-    }
-    if (threadIdx.x >= 3 && threadIdx.x < 3 + LFQ_NKHIST && s_k[2]) {
-        atomicAdd(&W.counters[LFQ_CNT_KHIST + (int)threadIdx.x - 3], (int)s_k[threadIdx.x]);
+    if (!GATED) {
+        __shared__ uint32_t s_k[3 + LFQ_NKHIST];
+        lfq_khist_flush(kh, s_k, W.counters);
     }
 }
 
@@ -1846,7 +1990,7 @@ int lfq_launch_count(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqPar
     return LFQ_OK;
 }
 
-int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const uint8_t *d_flags,
+int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const LfqParams &p, uint8_t *d_flags,
                     const lfq_col_counts *d_counts, const LfqWork &w, void *stream, bool relist)
 {
     const int64_t ncols = c1 - c0;
@@ -1855,18 +1999,37 @@ int lfq_launch_scan(const LfqTracksDev &t, int64_t c0, int64_t c1, const uint8_t
     }
     const int64_t ntiles = (ncols + LFQ_SCAN_TILE - 1) / LFQ_SCAN_TILE;
     LfqTriple *tile_sums = reinterpret_cast<LfqTriple *>(w.block_sums);
+    /* (the workspace holds 16 bytes per 1024 columns and 128 more per segment, lfq_api.hip: room for the 12 + 4 bytes per tile) */
+    static_assert(LFQ_SCAN_TILE >= 1024, "scan scratch per tile");
+    uint32_t *tile_drop = reinterpret_cast<uint32_t *>(tile_sums + ntiles);
     hipLaunchKernelGGL(lfq_scan_tiles_kernel, dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0,
-                       (hipStream_t)stream, ncols, d_flags + c0, tile_sums);
+                       (hipStream_t)stream, ncols, (const uint8_t *)d_flags + c0, tile_sums);
     if (relist) {
+        if (p.scan_gate_maxk > 0) {
+            return LFQ_ERR_INVALID;
+        }
         hipLaunchKernelGGL(lfq_scan_sums_kernel<true>, dim3(1), dim3(LFQ_SCAN_THREADS), 0, (hipStream_t)stream, ntiles,
                            tile_sums, w.counters, w.gcounters);
-        hipLaunchKernelGGL(lfq_scan_apply_kernel<true>, dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0,
-                           (hipStream_t)stream, t, c0, c1, d_flags, d_counts, (const LfqTriple *)tile_sums, w);
+        hipLaunchKernelGGL((lfq_scan_apply_kernel<true, false>), dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0,
+                           (hipStream_t)stream, t, c0, c1, (const uint8_t *)d_flags, d_counts, (const LfqTriple *)tile_sums,
+                           (const uint32_t *)nullptr, w);
+    } else if (p.scan_gate_maxk > 0) {
+        /* the bound gate's decision made here: the light columns it drops never get a list entry */
+        hipLaunchKernelGGL(lfq_scan_sums_kernel<false>, dim3(1), dim3(LFQ_SCAN_THREADS), 0, (hipStream_t)stream, ntiles,
+                           tile_sums, w.counters, w.gcounters);
+        hipLaunchKernelGGL(lfq_scan_gate_kernel, dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0, (hipStream_t)stream, c0, c1,
+                           p, d_flags, d_counts, (const LfqTriple *)tile_sums, tile_drop, w.counters);
+        hipLaunchKernelGGL(lfq_scan_drop_sums_kernel, dim3(1), dim3(LFQ_SCAN_THREADS), 0, (hipStream_t)stream, ntiles,
+                           tile_drop, w.counters);
+        hipLaunchKernelGGL((lfq_scan_apply_kernel<false, true>), dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0,
+                           (hipStream_t)stream, t, c0, c1, (const uint8_t *)d_flags, d_counts, (const LfqTriple *)tile_sums,
+                           (const uint32_t *)tile_drop, w);
     } else {
         hipLaunchKernelGGL(lfq_scan_sums_kernel<false>, dim3(1), dim3(LFQ_SCAN_THREADS), 0, (hipStream_t)stream, ntiles,
                            tile_sums, w.counters, w.gcounters);
-        hipLaunchKernelGGL(lfq_scan_apply_kernel<false>, dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0,
-                           (hipStream_t)stream, t, c0, c1, d_flags, d_counts, (const LfqTriple *)tile_sums, w);
+        hipLaunchKernelGGL((lfq_scan_apply_kernel<false, false>), dim3((unsigned)ntiles), dim3(LFQ_SCAN_THREADS), 0,
+                           (hipStream_t)stream, t, c0, c1, (const uint8_t *)d_flags, d_counts, (const LfqTriple *)tile_sums,
+                           (const uint32_t *)nullptr, w);
     }
     LFQ_HIP_TRY(hipGetLastError());
     return LFQ_OK;
@@ -1950,7 +2113,7 @@ __global__ __launch_bounds__(256) void lfq_strand_heavy_kernel(LfqTracksDev T, L
                                                                int32_t *__restrict__ tuples, int32_t *__restrict__ n_out,
                                                                int cap_entries, int min_alt)
 {
-    const int n_light = W.counters[LFQ_CNT_LIGHT];
+    const int n_light = W.counters[LFQ_CNT_LIST_LIGHT];
     const int n_heavy = min(W.counters[LFQ_CNT_MID] + W.counters[LFQ_CNT_BIG], cap_entries);
     const int i = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -2036,7 +2199,7 @@ __global__ __launch_bounds__(256) void lfq_gather_heavy_kernel(LfqWork W, const 
                                                                int32_t *__restrict__ tuples, int32_t *__restrict__ n_out,
                                                                int cap_entries, int min_alt)
 {
-    const int n_light = W.counters[LFQ_CNT_LIGHT];
+    const int n_light = W.counters[LFQ_CNT_LIST_LIGHT];
     const int n_heavy = min(W.counters[LFQ_CNT_MID] + W.counters[LFQ_CNT_BIG], cap_entries);
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i == 0) {

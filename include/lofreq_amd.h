@@ -1167,6 +1167,121 @@ int lfq_checkref(const lfq_fasta_index *idx, const char *const *names, const int
  * out NULL: only that.  Host only.  LFQ_ERR_INVALID: res / n_bytes NULL, capacity below *n_bytes */
 int lfq_bgzf_gzi_bytes(const lfq_bgzf_result *res, uint8_t *out_or_null, int64_t capacity, int64_t *n_bytes);
 
+/* ---- VCF text, parsed on the device, and `lofreq vcfset` -------------------------------------------------------------------------------
+ * (ABI version 10 still: new functions, new structs, a new opaque type; no existing layout changed.)
+ * lfq_vcf_open keeps the bytes of an UNCOMPRESSED VCF resident (device to device when they lie inside the context's live
+ * lfq_bgzf_inflate result -- a bgzipped VCF is inflated first --, lfq_vcf_times.n_from_device says so) and parses them by the rules of the
+ * 2.1.4 binary (lofreq_amd/csrc/lfq_vcf.h states them with their places in vcf.c):
+ *   LFQ_VCF_STREAM  as vcf_parse_header / vcf_parse_var read a file: the header is every line up to and including the first, among the
+ *                   first 10 000, whose first 38 bytes are "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"; the records start behind it, or
+ *                   at line 1 when there is none ('#' lines are records then); they END silently at the first line with fewer than five
+ *                   tab-separated fields (lfq_vcf_n_lines_behind counts that line and what follows).
+ *   LFQ_VCF_TABIX   as the second file of vcfset is read through its index: '#' lines are skipped anywhere; refused: a line with fewer
+ *                   than five fields (LFQ_VCF_FIELDS), a CHROM in two runs or a POS below the one before it in its run
+ *                   (LFQ_VCF_UNSORTED), POS < 1, an empty REF, an INFO END= below POS (LFQ_VCF_INTERVAL).
+ *   both            pos = atol(POS) - 1, qual = atoi(QUAL) or -1 for '.' / no QUAL; fewer than eight fields: FILTER and INFO are ".".
+ *                   Refused, departures from the reference: a line of more than 8 190 bytes (an fgets into vcf.c's LINE_BUF_SIZE 8192 would split it; THE 2.1.4 BINARY was built with
+ *                   half that buffer and already splits a line behind 4 095 bytes, silently: lines of 4 096 .. 8 190 bytes are read whole here;
+ *                   LFQ_VCF_LINE_TOO_LONG), a NUL byte (LFQ_VCF_NUL), more than 18 digits in POS or 9 in QUAL (LFQ_VCF_NUMBER).
+ * A refusal is LFQ_ERR_INVALID with *why_or_null and the 1-based line of the FIRST offending line (the smallest line, then the smallest
+ * reason: the same on every run).  n_bytes == 0: LFQ_OK, no records, nothing launched.  LFQ_ERR_INVALID before a device is touched: ctx /
+ * out NULL, n_bytes < 0, bytes NULL with n_bytes > 0, an unknown mode.  Blocks.  lfq_vcf_close must come before lfq_destroy. */
+typedef struct lfq_vcf lfq_vcf;
+typedef struct lfq_filter_var lfq_filter_var;           /* (both defined further down) */
+typedef struct lfq_uniq_variants lfq_uniq_variants;
+#define LFQ_VCF_STREAM 0
+#define LFQ_VCF_TABIX 1
+#define LFQ_VCF_OK 0
+#define LFQ_VCF_LINE_TOO_LONG 1
+#define LFQ_VCF_NUL 2
+#define LFQ_VCF_NUMBER 3
+#define LFQ_VCF_FIELDS 4
+#define LFQ_VCF_UNSORTED 5
+#define LFQ_VCF_INTERVAL 6
+#define LFQ_VCF_MULTIALLELIC 7
+int lfq_vcf_open(lfq_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, int mode, lfq_vcf **out, int *why_or_null, int64_t *bad_line_or_null);
+void lfq_vcf_close(lfq_vcf *vcf);
+int64_t lfq_vcf_n_records(const lfq_vcf *vcf);
+int64_t lfq_vcf_n_lines_behind(const lfq_vcf *vcf);
+/* the header's text (the file's own, valid until close; empty when *found = 0 -- the callers then write their default header) */
+int lfq_vcf_header(lfq_vcf *vcf, const char **text, int64_t *n_bytes, int *found);
+/* bits of flags[] */
+#define LFQ_VCF_F_PASSES 1u         /* VCF_VAR_PASSES (vcf.h:87), a PREFIX rule: FILTER starts with '.' or with "PASS" */
+#define LFQ_VCF_F_FILTERED 2u       /* vcf_var_filtered (vcf.c:315-326), an EXACT rule: FILTER is neither "." nor "PASS" */
+#define LFQ_VCF_F_INDEL_LEN 4u      /* strlen(REF) > 1 || strlen(ALT) > 1 */
+#define LFQ_VCF_F_INDEL_KEY 8u      /* INFO has the key INDEL (vcf_var_has_info_key: case-insensitive, '=' or the token's end) */
+#define LFQ_VCF_F_ALT_COMMA 16u
+/* host copies of the record table (the file's own, made on the first call, valid until close).  Record r is line line[r] (0-based);
+ * field j (0-based, j < n_fields[r], which is capped at 10: 9 = FORMAT alone, 10 = samples behind it; offsets exist for fields 1 - 9) starts field_off[10 r + j] bytes
+ * behind line_start[line[r]] and ends one byte in front of the next field; field_off[10 r + 9] is the line's end after chomp.
+ * run_id[r]: the run of equal CHROM strings the record stands in; run_name[i], run_begin[i] .. run_begin[i + 1]: its name and records */
+typedef struct lfq_vcf_table {
+    int64_t n_records, n_lines, n_runs;
+    const int64_t *line, *line_start, *pos;
+    const int32_t *qual;
+    const uint8_t *flags, *n_fields;
+    const uint16_t *field_off;
+    const int32_t *run_id;
+    const int64_t *run_begin;
+    const char *const *run_name;
+} lfq_vcf_table;
+int lfq_vcf_records(lfq_vcf *vcf, lfq_vcf_table *out);
+/* out[n_records], ready for lfq_filter_vars: is_indel = vcf_var_is_indel, qual, dp / sb by strtol / atoi of INFO DP / SB (0 where the key
+ * is missing), alt_fw / alt_rv from DP4 (-1 unless it has exactly four fields, vcf.c:566-604), af = the C library's strtof on the bytes
+ * of AF's value, which the device located (0 where missing) */
+int lfq_vcf_filter_vars(lfq_vcf *vcf, lfq_filter_var *out);
+/* the variants of CHROM `chrom` as `lofreq uniq` reads them (lofreq_uniq.c:684: with only_unfiltered, those vcf_var_filtered lets
+ * through), ready for lfq_readset_uniq; af = uni_freq when that is > 0, else strtof of AF -- a record without AF is then
+ * LFQ_ERR_INVALID with *bad_line_or_null its 1-based line (lofreq_uniq.c:257-261).  (*line_of_variant)[i]: the 0-based line of variant i.
+ * The arrays are the file's own, valid until the next call on it or close */
+int lfq_vcf_uniq_variants(lfq_vcf *vcf, const char *chrom, int only_unfiltered, float uni_freq, lfq_uniq_variants *out,
+                          int64_t **line_of_variant, int64_t *bad_line_or_null);
+/* -S / --ign-vcf (source_qual_load_ign_vcf, plp.c:337-399): mask[pos] |= 1 for every record of `chrom` with 0 <= pos < ref_len, under a
+ * BED only where [pos, pos + 1) overlaps its table of that name (plp.c:376).  ORs into the caller's array, so several files accumulate
+ * (lofreq_call.c:1453-1463); the result is what lfq_source_qual_batch and lfq_readset_source_qual take as ign_or_null */
+int lfq_vcf_ign_mask(lfq_vcf *vcf, const char *chrom, int64_t ref_len, const lfq_bed *bed_or_null, uint8_t *mask);
+/* `lofreq vcfset` (lofreq_vcfset.c): intersect / complement of vcf1 (stream mode) against vcf2 (tabix mode), or concat of vcf1 and
+ * more[0 .. n_more) (stream mode; their headers are skipped, no matching).  Per record of vcf1, in the reference's order (:387-411):
+ * --only-snvs / --only-indels drop it silently; then a ',' in ALT without --only-pos refuses the whole call (LFQ_VCF_MULTIALLELIC);
+ * then --only-passed (VCF_VAR_PASSES) skips it and counts it in n_ignored.  A candidate of vcf2 has the same CHROM string and the same
+ * POS, passes the same three filters (:452-477) and, without --only-pos, has bytewise the same REF and ALT.  A record of vcf1 with
+ * POS < 1 that reaches the match is refused (LFQ_VCF_INTERVAL).  The lines are WRITTEN, not copied (vcf_write_var, vcf.c:469-497): POS
+ * and QUAL from the parsed values, FILTER / INFO "." for short lines, add_info_or_null appended by vcf_var_add_to_info's rule.
+ * The result is the context's own, valid until its next lfq_vcfset: keep[n_keep] has LFQ_VCFSET_* per record (of every file in turn
+ * for concat), text (pinned memory) is vcf1's header, if found, and the lines; with count_only no text is made.
+ * LFQ_ERR_INVALID before a device is touched: a NULL vcf1 / conf / out, an unknown op, only_snvs && only_indels, no vcf2 or n_more > 0
+ * for intersect / complement, n_more < 0, files of different contexts.  A refusal is LFQ_ERR_INVALID with *out set and why, bad_file
+ * (0 = vcf1, i + 1 = more[i]) and bad_line filled in.  Blocks. */
+#define LFQ_VCFSET_INTERSECT 0
+#define LFQ_VCFSET_COMPLEMENT 1
+#define LFQ_VCFSET_CONCAT 2
+#define LFQ_VCFSET_DROPPED 0
+#define LFQ_VCFSET_IGNORED 1
+#define LFQ_VCFSET_TAKEN 2          /* counted in n_vars1, not written */
+#define LFQ_VCFSET_WRITTEN 3
+typedef struct lfq_vcfset_conf {
+    int op, only_passed, only_pos, only_snvs, only_indels, count_only;
+    const char *add_info_or_null;
+} lfq_vcfset_conf;
+typedef struct lfq_vcfset_result {
+    int64_t n_vars1, n_ignored, n_out, n_keep;
+    const uint8_t *keep;
+    const char *text;
+    int64_t text_bytes;
+    int64_t bad_line;
+    int why, bad_file;
+} lfq_vcfset_result;
+int lfq_vcfset(lfq_vcf *vcf1, lfq_vcf *vcf2_or_null, lfq_vcf *const *more, int64_t n_more, const lfq_vcfset_conf *conf,
+               const lfq_vcfset_result **out);
+/* the context's last lfq_vcf_open and what followed it on that context: the kernels on the device's clock, both link legs on the host's.
+ * n_launches counts every launch since that open, n_set_launches those of the last lfq_vcfset */
+typedef struct lfq_vcf_times {
+    double upload_ms, scan_ms, parse_ms, info_ms, match_ms, emit_ms, download_ms;
+    int64_t n_bytes, n_lines, n_records;
+    int n_launches, n_from_device, n_set_launches, pad_;
+} lfq_vcf_times;
+int lfq_last_vcf_times(lfq_ctx *ctx, lfq_vcf_times *t);
+
 /* lfq_call_snvs_batch in two halves, for callers that keep more than one batch in flight (one context per batch in
  * flight): submit launches the kernels and returns; collect waits, fetches the sparse records and finishes them on
  * the host.  While batch k is collected, the kernels of batch k+1 (submitted on another context) run.  conf's
@@ -1382,7 +1497,8 @@ int lfq_readset_pileup_sites(lfq_ctx *ctx, lfq_readset *rs, const int64_t *site_
  * per-observation byte crosses the link in either direction.  The read-level filters are the caller's, as for every read set.
  * LFQ_ERR_INVALID, before anything is launched: a NULL ctx, rs, vars or out (before a device is touched); n < 0; a NULL array of
  * vars with n > 0 (indel_key_or_null excepted); offsets that decrease; a NaN in af; and everything lfq_readset_pileup_sites
- * refuses.  n = 0: LFQ_OK, no launch.  More than one contig per call, VCF text and the per-query -d rule are not covered. */
+ * refuses.  n = 0: LFQ_OK, no launch.  More than one contig per call and the per-query -d rule are not covered; the variants of a VCF
+ * text: lfq_vcf_uniq_variants. */
 typedef struct lfq_uniq_variants {
     int64_t n;
     const int64_t *pos;               /* [n] var->pos, 0-based */

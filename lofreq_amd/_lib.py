@@ -293,6 +293,8 @@ EXPORTS = [
     "lfq_fasta_open", "lfq_fasta_close", "lfq_fasta_index_build", "lfq_fasta_index_text", "lfq_fasta_index_parse", "lfq_fasta_index_free",
     "lfq_fasta_index_n", "lfq_fasta_index_n_duplicates", "lfq_fasta_index_name", "lfq_fasta_index_entry", "lfq_fasta_index_find",
     "lfq_fasta_fetch", "lfq_last_fasta_times", "lfq_readset_ref_from_device", "lfq_checkref", "lfq_bgzf_gzi_bytes",
+    "lfq_vcf_open", "lfq_vcf_close", "lfq_vcf_n_records", "lfq_vcf_n_lines_behind", "lfq_vcf_header", "lfq_vcf_records",
+    "lfq_vcf_filter_vars", "lfq_vcf_uniq_variants", "lfq_vcf_ign_mask", "lfq_vcfset", "lfq_last_vcf_times",
 ]
 
 class FilterConf(C.Structure):
@@ -329,6 +331,33 @@ class FastaTimes(C.Structure):
                 ("download_ms", C.c_double), ("n_bytes", C.c_int64), ("n_lines", C.c_int64), ("n_headers", C.c_int64),
                 ("n_fetch_bytes", C.c_int64), ("n_launches", C.c_int), ("n_from_device", C.c_int), ("fetch_path", C.c_int),
                 ("n_handovers", C.c_int)]
+
+
+class VcfTable(C.Structure):
+    """lfq_vcf_table"""
+    _fields_ = [("n_records", C.c_int64), ("n_lines", C.c_int64), ("n_runs", C.c_int64), ("line", C.c_void_p), ("line_start", C.c_void_p),
+                ("pos", C.c_void_p), ("qual", C.c_void_p), ("flags", C.c_void_p), ("n_fields", C.c_void_p), ("field_off", C.c_void_p),
+                ("run_id", C.c_void_p), ("run_begin", C.c_void_p), ("run_name", C.POINTER(C.c_char_p))]
+
+
+class VcfsetConf(C.Structure):
+    """lfq_vcfset_conf"""
+    _fields_ = [("op", C.c_int), ("only_passed", C.c_int), ("only_pos", C.c_int), ("only_snvs", C.c_int), ("only_indels", C.c_int),
+                ("count_only", C.c_int), ("add_info_or_null", C.c_char_p)]
+
+
+class VcfsetResult(C.Structure):
+    """lfq_vcfset_result"""
+    _fields_ = [("n_vars1", C.c_int64), ("n_ignored", C.c_int64), ("n_out", C.c_int64), ("n_keep", C.c_int64), ("keep", C.c_void_p),
+                ("text", C.c_void_p), ("text_bytes", C.c_int64), ("bad_line", C.c_int64), ("why", C.c_int), ("bad_file", C.c_int)]
+
+
+class VcfTimes(C.Structure):
+    """lfq_vcf_times"""
+    _fields_ = [("upload_ms", C.c_double), ("scan_ms", C.c_double), ("parse_ms", C.c_double), ("info_ms", C.c_double),
+                ("match_ms", C.c_double), ("emit_ms", C.c_double), ("download_ms", C.c_double), ("n_bytes", C.c_int64),
+                ("n_lines", C.c_int64), ("n_records", C.c_int64), ("n_launches", C.c_int), ("n_from_device", C.c_int),
+                ("n_set_launches", C.c_int), ("pad_", C.c_int)]
 
 
 def load():
@@ -535,6 +564,20 @@ def load():
     L.lfq_readset_ref_from_device.argtypes = [vp]
     L.lfq_checkref.argtypes = [vp, C.POINTER(C.c_char_p), vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     L.lfq_bgzf_gzi_bytes.argtypes = [C.POINTER(BgzfResult), vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.lfq_vcf_open.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.lfq_vcf_close.argtypes = [vp]
+    L.lfq_vcf_close.restype = None
+    L.lfq_vcf_n_records.argtypes = [vp]
+    L.lfq_vcf_n_records.restype = C.c_int64
+    L.lfq_vcf_n_lines_behind.argtypes = [vp]
+    L.lfq_vcf_n_lines_behind.restype = C.c_int64
+    L.lfq_vcf_header.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.lfq_vcf_records.argtypes = [vp, C.POINTER(VcfTable)]
+    L.lfq_vcf_filter_vars.argtypes = [vp, vp]
+    L.lfq_vcf_uniq_variants.argtypes = [vp, C.c_char_p, C.c_int, C.c_float, C.POINTER(UniqVariants), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_vcf_ign_mask.argtypes = [vp, C.c_char_p, C.c_int64, vp, vp]
+    L.lfq_vcfset.argtypes = [vp, vp, C.POINTER(vp), C.c_int64, C.POINTER(VcfsetConf), C.POINTER(C.POINTER(VcfsetResult))]
+    L.lfq_last_vcf_times.argtypes = [vp, C.POINTER(VcfTimes)]
     _lib = L
     return L
 

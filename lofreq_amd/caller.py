@@ -135,7 +135,7 @@ class SnvCaller:
         if getattr(self, "h", None):
             for rs in list(getattr(self, "_readsets", ())):     # a read set is destroyed before its context
                 rs.close()
-            for fa in list(getattr(self, "_fastas", ())):       # ... and so is a resident FASTA (fasta.Fasta)
+            for fa in list(getattr(self, "_fastas", ())) + list(getattr(self, "_vcfs", ())):    # ... and so is a resident FASTA or VCF
                 fa.close()
             self.L.lfq_destroy(self.h)
             self.h = None

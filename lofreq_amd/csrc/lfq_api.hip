@@ -505,6 +505,7 @@ void lfq_destroy(lfq_ctx *c)
         lfq_bgzf_deflate_release(c);
         lfq_bam_index_release(c);
         lfq_fasta_release(c);
+        lfq_vcf_release(c);
         lfq_bed_dev_release(c->bed);
         if (c->h_tuples) (void)hipHostFree(c->h_tuples);
         if (c->h_nheavy) (void)hipHostFree(c->h_nheavy);

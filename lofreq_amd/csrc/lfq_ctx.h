@@ -13,6 +13,7 @@
  *   lfq_bamidx.hip         the .bai of a BAM from its records and block tables (over lfq_bamidx.h)
  *   lfq_bed.hip            the targets of `lofreq call -l`: the BED itself, lfq_set_bed, the read and column kernels (over lfq_bed.h)
  *   lfq_fasta.hip          `lofreq faidx` and the contig of a FASTA: scan, line and entry kernels, both fetch paths (over lfq_fasta.h)
+ *   lfq_vcf.hip            VCF text parsed on the device and `lofreq vcfset`: scan, parse, runs, match, plan / copy (over lfq_vcf.h)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -438,6 +439,7 @@ struct lfq_ctx {
     struct LfqBamIdxState *bamidx;   /* lfq_bam_index_build: likewise (lfq_bamidx.hip) */
     LfqBedDev *bed;                  /* lfq_set_bed: the targets the read sets created from now on take (null: none) */
     struct LfqFastaState *fasta;     /* lfq_fasta_*: timing and the live fetch result (lfq_fasta.hip; created on first use) */
+    struct LfqVcfState *vcf;         /* lfq_vcf_* / lfq_vcfset: timing and the last vcfset result (lfq_vcf.hip; created on first use) */
 };
 
 template <typename T>
@@ -611,6 +613,7 @@ void lfq_bam_index_release(lfq_ctx *c);    /* lfq_bamidx.hip: what lfq_destroy f
  * of host bytes [p, p + bytes) when they lie inside the context's live lfq_fasta_fetch result (counted as a hand-over), else null */
 void lfq_fasta_release(lfq_ctx *c);
 const uint8_t *lfq_fasta_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
+void lfq_vcf_release(lfq_ctx *c);          /* lfq_vcf.hip: what lfq_destroy frees of lfq_ctx::vcf */
 /* lfq_bed.hip, for the read set (lfq_readset.hip).  keep_out[r] = 1 iff [pos, bam_endpos) of read r overlaps an interval, one lane
  * per read, from the resident start positions and CIGAR words; cov[p] (and nb[p], unless null) of every position of
  * [begin, begin + width) whose [p, p + 1) overlaps none go to 0, one lane per position: no column for the compaction behind it */

@@ -199,16 +199,24 @@ def _binom_tail(k, n, p):
 
 
 def exact_tail(k, spec):
-    """P(X >= k) for a column of edge_column(**spec): X = Bin(n - n_q2, lut_p(q)) + Bin(n_q2, lut_p(q2))"""
+    """P(X >= k) for a column of edge_column(**spec): X = Bin(n - n_q2, lut_p(q)) + Bin(n_q2, lut_p(q2)).
+    A spec may give the probability of the body as "p" instead of "q" (a merged probability is no LUT value), and rows at
+    further levels as "levels": [(rows, probability)] -- X is then the sum of all those binomials."""
     with mpmath.workdps(DPS):
-        n, n2 = spec["n"], spec.get("n_q2", 0)
-        if not n2:
-            return _binom_tail(k, n, lut_p(spec["q"]))
-        p2 = mpmath.mpf(lut_p(spec["q2"]))
-        s = mpmath.mpf(0)
-        for j in range(n2 + 1):
-            s += mpmath.binomial(n2, j) * p2 ** j * (1 - p2) ** (n2 - j) * _binom_tail(k - j, n - n2, lut_p(spec["q"]))
-        return s
+        n = spec["n"]
+        p1 = spec["p"] if "p" in spec else lut_p(spec["q"])
+        levels = [(int(r), mpmath.mpf(p)) for r, p in spec.get("levels", ())]
+        if spec.get("n_q2", 0):
+            levels.append((spec["n_q2"], mpmath.mpf(lut_p(spec["q2"]))))
+        if not levels:
+            return _binom_tail(k, n, p1)
+        pmf = [mpmath.mpf(1)]                           # of the rows beside the body
+        for rows, p in levels:
+            b = [mpmath.binomial(rows, j) * p ** j * (1 - p) ** (rows - j) for j in range(rows + 1)]
+            pmf = [mpmath.fsum(pmf[i] * b[j - i] for i in range(max(0, j - rows), min(j, len(pmf) - 1) + 1))
+                   for j in range(len(pmf) + rows)]
+        body = n - sum(r for r, _ in levels)
+        return mpmath.fsum(w * _binom_tail(k - j, body, p1) for j, w in enumerate(pmf))
 
 
 def exact_log_tail(k, spec):

@@ -26,6 +26,9 @@ DP = ["tests/test_gpu_parity.py", "-k", "default_conf_random or row_split or rag
 BAQ = ["tests/test_gpu_baq.py"]
 PLP = ["tests/test_gpu_pileup.py", "tests/test_gpu_plpindel.py", "-k", "not host_loops and not window_search"]
 CHAIN = ["tests/test_gpu_plpindel.py", "-k", "chain or device_only or device_packing", "tests/test_gpu_indel.py"]
+# ... and the indel boundary rows (-k holds for every file of a run: the module's name selects its tests)
+HOST_PACK = ["tests/test_gpu_plpindel.py", "-k", "chain or device_only or device_packing or test_gpu_indel_edges", "tests/test_gpu_indel.py",
+             "tests/test_gpu_indel_edges.py"]
 
 CASES = [
     ("LFQ_SPLIT_POOL_CELLS=0", DP),          # no row split: every long column on the unsplit kernels
@@ -47,7 +50,7 @@ CASES = [
     ("LFQ_BAQ_ONE_VARIANT=1", BAQ),          # every wavefront through the register kernel's instantiation with the N case
     ("LFQ_BAQ_LDS=0", BAQ),                  # every read through the all-HBM BAQ kernel (what wide bands get)
     ("LFQ_PILEUP_ATOMIC=1", PLP),            # read-major pileup kernels (what unsorted reads get)
-    ("LFQ_INDEL_HOST_PACK=1", CHAIN),        # indel pseudo-columns packed on the host
+    ("LFQ_INDEL_HOST_PACK=1", HOST_PACK),    # indel pseudo-columns packed on the host
     ("LFQ_SYNC_UPLOAD=1", CHAIN),            # lfq_readset_create waits for its copies itself
     ("LFQ_HOST_SPIN_US=-1", CHAIN),          # host loops on threads created per loop
 ]

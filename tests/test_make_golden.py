@@ -28,3 +28,18 @@ def test_regenerated_snv_fixtures_are_byte_identical(tmp_path):
         a = open(tmp_path / f, "rb").read()
         b = open(os.path.join(ROOT, "tests", "golden", f), "rb").read()
         assert a == b, f
+
+
+def test_regenerated_indel_edges_fixture_is_byte_identical(tmp_path):
+    """tests/make_indel_edges_golden.py: the gate and poly-AT rows of tests/indel_edges.py through the 2.1.4 binary"""
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True)
+    env = {k: v for k, v in os.environ.items()}
+    env["LFQ_GOLDEN_OUT"] = str(tmp_path)
+    env["PATH"] = "/usr/bin:/bin"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "make_indel_edges_golden.py")], env=env, capture_output=True,
+                       text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path)) == ["indel_edges.json"]
+    a = open(tmp_path / "indel_edges.json", "rb").read()
+    b = open(os.path.join(ROOT, "tests", "golden", "indel_edges.json"), "rb").read()
+    assert a == b

@@ -1282,6 +1282,69 @@ typedef struct lfq_vcf_times {
 } lfq_vcf_times;
 int lfq_last_vcf_times(lfq_ctx *ctx, lfq_vcf_times *t);
 
+/* ---- the index of a bgzipped VCF: its .tbi built on the device, written, read, queried, and a region opened through it ---------------
+ * (ABI version 10 still: new functions, a new struct, a new opaque type; no existing layout changed.)
+ * lfq_vcf_index_build makes the tabix index of a file opened in LFQ_VCF_TABIX mode whose text lies in BGZF blocks with the tables
+ * data_off / comp_off ([n_blocks + 1] each, as lfq_bgzf_deflated and lfq_bgzf_result give them; data_off[0] = 0, data_off[n_blocks] =
+ * the text's length): block b holds the text's bytes [data_off[b], data_off[b + 1]) and starts at byte comp_off[b] + file_off of the
+ * .vcf.gz; empty blocks at the tables' end (the end-of-file marker an lfq_bgzf_result lists) are dropped, so that the text ends where the
+ * marker starts.  The index is the one the reference's 2.1.4 binary writes beside every .vcf.gz (vcf_file_close, vcf.c:256-270), name for
+ * name, bin for bin and chunk for chunk; lofreq_amd/csrc/lfq_tbx.h states the rules, INTEGRATION.md section 14 lists them and
+ * tests/golden/tbi_binary.json holds them to the binary: a record's interval is [POS - 1, END= value, or POS - 1 + len(REF)), its
+ * chunk begins where the record in front of it ends ('#' lines between two records therefore belong to the second one's chunk) and
+ * the last record's ends at the text's end.  One lane per record reads the table the open left on the device (the text is neither
+ * uploaded nor read again, except for END= values), then lfq_bam_index_build's own compaction kernels and host pass run: four launches
+ * whatever the record count, device memory O(records + blocks).
+ * Refused with LFQ_ERR_INVALID, *why_or_null = LFQ_VCF_RANGE and the 1-based FIRST such line: an interval a .tbi cannot hold -- an end
+ * above 2^29 (POS 2^29 is taken, POS 2^29 + 1 and END=2^29 + 1 are not; the binary then writes no index), or an END= of more than 18
+ * digits.  LFQ_ERR_INVALID before a launch: a NULL vcf / out / table, a file opened in stream mode, a negative n_blocks or file_off,
+ * comp_off not strictly increasing or negative, data_off decreasing, data_off[0] != 0, data_off[n_blocks] != the text's length.
+ * A file without records: LFQ_OK, an index of no names (as the binary's .tbi of a header-only file), nothing launched.
+ * No result of the context is invalidated.  *out is the CALLER'S, a host object with no tie to the context or the file: free it with
+ * lfq_vcf_index_free.  Blocks.
+ * The cuts of lfq_bgzf_deflate that keep lines whole -- the binary's blocks end on line boundaries -- are what lfq_bam_record_cuts gives
+ * for rec_off = the table's line_start[0 .. n_lines) followed by the text's length: no function of their own. */
+#define LFQ_VCF_RANGE 8
+typedef struct lfq_vcf_index lfq_vcf_index;
+int lfq_vcf_index_build(lfq_vcf *vcf, const int64_t *data_off, const int64_t *comp_off, int64_t n_blocks, int64_t file_off,
+                        lfq_vcf_index **out, int *why_or_null, int64_t *bad_line_or_null);
+/* the last lfq_vcf_index_build on the context of its file: the four kernels and the lists' way back on the device's clock, the host's
+ * finishing pass on the wall clock */
+typedef struct lfq_vcf_index_times {
+    double kernels_ms, download_ms, host_ms;
+    int64_t n_records, n_chunks, n_intervals;
+    int n_launches, pad_;
+} lfq_vcf_index_times;
+int lfq_last_vcf_index_times(lfq_ctx *ctx, lfq_vcf_index_times *t);
+/* Host only, no context.  The UNCOMPRESSED .tbi (on disk it is BGZF-compressed: lfq_bgzf_deflate with LFQ_BGZF_PUT_EOF, lfq_bgzf_inflate):
+ * "TBI\1", n_ref, format (2), col_seq (1), col_beg (2), col_end (0), meta ('#'), skip (0), l_nm, the names NUL-terminated, then per name
+ * what a .bai holds per reference (lfq_bam_index_bytes) and n_no_coor (0).  *tbi is idx's, valid until lfq_vcf_index_free. */
+int lfq_vcf_index_bytes(const lfq_vcf_index *idx, const uint8_t **tbi, int64_t *n_bytes);
+/* any writer's .tbi, inflated: bins in any order, the trailing n_no_coor optional; format, columns, meta and skip are kept and given back
+ * by lfq_vcf_index_bytes.  LFQ_ERR_INVALID (*out = NULL): a NULL argument, no magic, a count that runs past n_bytes, l_nm that is not
+ * exactly n_ref NUL-terminated names, a name twice, and everything lfq_bam_index_parse refuses of the rest. */
+int lfq_vcf_index_parse(const uint8_t *tbi, int64_t n_bytes, lfq_vcf_index **out);
+int64_t lfq_vcf_index_n_names(const lfq_vcf_index *idx);
+const char *lfq_vcf_index_name(const lfq_vcf_index *idx, int64_t i);           /* idx's, NULL outside [0, n_names) */
+/* the chunks that hold every record of `chrom` overlapping [beg, end) (0-based, half-open): by name, then lfq_bam_index_query's list
+ * and contract -- every such record's line starts inside one of the chunks, they are sorted and disjoint, none begins in front of the
+ * linear value.  A name the index lacks or an empty region: n_chunks = 0, LFQ_OK.  LFQ_ERR_INVALID: a NULL argument.  The arrays are
+ * idx's, valid until its next query or lfq_vcf_open_indexed (an index is not to be queried from two threads at once). */
+int lfq_vcf_index_query(const lfq_vcf_index *idx, const char *chrom, int64_t beg, int64_t end, const uint64_t **chunk_beg,
+                        const uint64_t **chunk_end, int64_t *n_chunks);
+void lfq_vcf_index_free(lfq_vcf_index *idx);
+/* A region of a large second file (dbSNP for a viral contig): `comp` is the whole .vcf.gz as it lies on disk and idx its index.  The
+ * index is queried; the BGZF blocks from the one the first chunk begins in to the one the last chunk ends in are inflated with
+ * lfq_bgzf_inflate -- only that slice of comp goes down the link --; the bytes from the first chunk's begin to the last chunk's end are
+ * opened in LFQ_VCF_TABIX mode, device to device.  Chunks begin and end on line boundaries, and a span of a sorted file is sorted with
+ * one run per CHROM, so the result is a file like any other: it holds every record of `chrom` overlapping [beg, end), MAY HOLD MORE
+ * (records in front of, behind and between them, of other names too) and never less.  No chunk: an open of zero bytes, nothing
+ * inflated.  The call REPLACES the context's live lfq_bgzf_inflate result, as any inflate does.  why / bad_line as lfq_vcf_open, the
+ * line counted from the span's first.  LFQ_ERR_INVALID before a device is touched: a NULL argument, n_comp < 0, chunks that lie outside
+ * comp or not on its block boundaries (another file's index). */
+int lfq_vcf_open_indexed(lfq_ctx *ctx, const uint8_t *comp, int64_t n_comp, const lfq_vcf_index *idx, const char *chrom, int64_t beg,
+                         int64_t end, lfq_vcf **out, int *why_or_null, int64_t *bad_line_or_null);
+
 /* lfq_call_snvs_batch in two halves, for callers that keep more than one batch in flight (one context per batch in
  * flight): submit launches the kernels and returns; collect waits, fetches the sparse records and finishes them on
  * the host.  While batch k is collected, the kernels of batch k+1 (submitted on another context) run.  conf's

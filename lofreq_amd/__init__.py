@@ -23,7 +23,7 @@ from .pileup import (DeviceTracks, PlpQuals, PlpSummary, ReadSet, format_plp_ind
 from .bamindex import BamIndex, BamIndexError, bam_index_build, bam_record_chain, bam_record_cuts, last_bam_index_times
 from .bed import Bed, BedError
 from .fasta import Contig, Fasta, FastaError, FastaIndex, bgzf_gzi, bgzf_inflate_view, checkref, last_fasta_times
-from .vcf import Vcf, VcfError, last_vcf_times, vcfset
+from .vcf import Vcf, VcfError, VcfIndex, last_vcf_index_times, last_vcf_times, vcf_write_gz, vcfset
 from .srcq import source_qual_batch
 from .indel import IndelColumns, call_indels, filter_indel_records, format_indel_record
 
@@ -44,5 +44,5 @@ __all__ = [
     "BamIndex", "BamIndexError", "bam_index_build", "last_bam_index_times", "bam_record_chain", "bam_record_cuts",
     "Bed", "BedError",
     "Fasta", "FastaIndex", "FastaError", "Contig", "checkref", "bgzf_gzi", "bgzf_inflate_view", "last_fasta_times",
-    "Vcf", "VcfError", "vcfset", "last_vcf_times",
+    "Vcf", "VcfError", "vcfset", "last_vcf_times", "VcfIndex", "last_vcf_index_times", "vcf_write_gz",
 ]

@@ -295,6 +295,8 @@ EXPORTS = [
     "lfq_fasta_fetch", "lfq_last_fasta_times", "lfq_readset_ref_from_device", "lfq_checkref", "lfq_bgzf_gzi_bytes",
     "lfq_vcf_open", "lfq_vcf_close", "lfq_vcf_n_records", "lfq_vcf_n_lines_behind", "lfq_vcf_header", "lfq_vcf_records",
     "lfq_vcf_filter_vars", "lfq_vcf_uniq_variants", "lfq_vcf_ign_mask", "lfq_vcfset", "lfq_last_vcf_times",
+    "lfq_vcf_index_build", "lfq_last_vcf_index_times", "lfq_vcf_index_bytes", "lfq_vcf_index_parse", "lfq_vcf_index_n_names",
+    "lfq_vcf_index_name", "lfq_vcf_index_query", "lfq_vcf_index_free", "lfq_vcf_open_indexed",
 ]
 
 class FilterConf(C.Structure):
@@ -358,6 +360,12 @@ class VcfTimes(C.Structure):
                 ("match_ms", C.c_double), ("emit_ms", C.c_double), ("download_ms", C.c_double), ("n_bytes", C.c_int64),
                 ("n_lines", C.c_int64), ("n_records", C.c_int64), ("n_launches", C.c_int), ("n_from_device", C.c_int),
                 ("n_set_launches", C.c_int), ("pad_", C.c_int)]
+
+
+class VcfIndexTimes(C.Structure):
+    """lfq_vcf_index_times"""
+    _fields_ = [("kernels_ms", C.c_double), ("download_ms", C.c_double), ("host_ms", C.c_double), ("n_records", C.c_int64),
+                ("n_chunks", C.c_int64), ("n_intervals", C.c_int64), ("n_launches", C.c_int), ("pad_", C.c_int)]
 
 
 def load():
@@ -578,6 +586,19 @@ def load():
     L.lfq_vcf_ign_mask.argtypes = [vp, C.c_char_p, C.c_int64, vp, vp]
     L.lfq_vcfset.argtypes = [vp, vp, C.POINTER(vp), C.c_int64, C.POINTER(VcfsetConf), C.POINTER(C.POINTER(VcfsetResult))]
     L.lfq_last_vcf_times.argtypes = [vp, C.POINTER(VcfTimes)]
+    L.lfq_vcf_index_build.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.lfq_last_vcf_index_times.argtypes = [vp, C.POINTER(VcfIndexTimes)]
+    L.lfq_vcf_index_bytes.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_vcf_index_parse.argtypes = [vp, C.c_int64, C.POINTER(vp)]
+    L.lfq_vcf_index_n_names.argtypes = [vp]
+    L.lfq_vcf_index_n_names.restype = C.c_int64
+    L.lfq_vcf_index_name.argtypes = [vp, C.c_int64]
+    L.lfq_vcf_index_name.restype = C.c_char_p
+    L.lfq_vcf_index_query.argtypes = [vp, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.lfq_vcf_index_free.argtypes = [vp]
+    L.lfq_vcf_index_free.restype = None
+    L.lfq_vcf_open_indexed.argtypes = [vp, vp, C.c_int64, vp, C.c_char_p, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int64)]
     _lib = L
     return L
 

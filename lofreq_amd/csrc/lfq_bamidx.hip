@@ -269,6 +269,8 @@ struct LfqBamIdxState {
     uint8_t *h_out = nullptr;           /* the three lists on the host, pinned */
     int64_t h_out_bytes = 0;
     lfq_bam_index_times times = {};
+    lfq_vcf_index_times vcf_times = {}; /* of lfq_vcf_index_build (lfq_tbx.hip), which compacts in these buffers */
+    LfqBaiArgs lay = {};                /* what lfq_bai_reserve laid out in d_buf: the compaction's part of the kernels' arguments */
     LfqEvPair up_t = {}, kern_t = {}, down_t = {};
 };
 
@@ -302,6 +304,98 @@ static int bam_idx_add_ms(const LfqEvPair &t, double *acc)
     *acc += ms;
     return LFQ_OK;
 }
+
+/* ---- the compaction both index builders run (lfq_ctx.h): lfq_bam_index_build below, lfq_vcf_index_build in lfq_tbx.hip ---------------
+ * reserve: d_buf = head_bytes of the caller's own | n_recs LfqBaiRec | parts | counters | chunks | runs | intervals.  The caller's
+ * record pass fills rec[] and sets the four counters (0: its own, 1 .. 3: zero) in front of lfq_bai_compact, which launches
+ * part / scan / emit on the context's stream and brings the three lists to pinned host memory: valid until the next reserve. */
+int lfq_bai_reserve(lfq_ctx *c, int64_t head_bytes, int64_t n_recs, int64_t max_runs, LfqBaiDev *out)
+{
+    LfqBamIdxState *S = bam_idx_state(c);
+    const int64_t n_parts = (n_recs + LFQ_BAI_THREADS - 1) / LFQ_BAI_THREADS;
+    const int64_t o_rec = lfq_al(head_bytes), o_part = o_rec + lfq_al(n_recs * (int64_t)sizeof(LfqBaiRec)),
+                  o_pre = o_part + lfq_al(n_parts * (int64_t)sizeof(LfqBaiPart)),
+                  o_cnt = o_pre + lfq_al(n_parts * (int64_t)sizeof(LfqBaiPart)), o_chunks = o_cnt + lfq_al(64),
+                  o_runs = o_chunks + lfq_al(n_recs * (int64_t)sizeof(LfqBaiChunk)),
+                  o_intvs = o_runs + lfq_al(max_runs * (int64_t)sizeof(LfqBaiRun)),
+                  total = o_intvs + lfq_al(n_recs * (int64_t)sizeof(LfqBaiIntv));
+    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
+    LfqBaiArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_recs = n_recs;
+    A.rec = (LfqBaiRec *)(S->d_buf + o_rec);
+    A.part = (LfqBaiPart *)(S->d_buf + o_part);
+    A.pre = (LfqBaiPart *)(S->d_buf + o_pre);
+    A.n_parts = n_parts;
+    A.counters = (unsigned long long *)(S->d_buf + o_cnt);
+    A.chunks = (LfqBaiChunk *)(S->d_buf + o_chunks);
+    A.runs = (LfqBaiRun *)(S->d_buf + o_runs);
+    A.intvs = (LfqBaiIntv *)(S->d_buf + o_intvs);
+    A.max_chunks = n_recs;
+    A.max_runs = max_runs;
+    A.max_intvs = n_recs;
+    S->lay = A;
+    out->head = S->d_buf;
+    out->rec = A.rec;
+    out->counters = A.counters;
+    return LFQ_OK;
+}
+
+int lfq_bai_compact(lfq_ctx *c, LfqBaiLists *out)
+{
+    LfqBamIdxState *S = bam_idx_state(c);
+    const LfqBaiArgs &A = S->lay;
+    hipStream_t st = c->stream;
+    memset(out, 0, sizeof(*out));
+    LfqPin<unsigned long long> cnt(c, 4);
+    LFQ_PIN_OK(cnt);
+    const dim3 grid((unsigned)A.n_parts), block(LFQ_BAI_THREADS);
+    LFQ_TRY(S->kern_t.begin(st));
+    hipLaunchKernelGGL(lfq_bai_part_kernel, grid, block, 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lfq_bai_scan_kernel, dim3(1), dim3(64), 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    hipLaunchKernelGGL(lfq_bai_emit_kernel, grid, block, 0, st, A);
+    LFQ_TRY_HIP(hipGetLastError());
+    LFQ_TRY(S->kern_t.end(st));
+    LFQ_TRY(S->down_t.begin(st));
+    LFQ_TRY_HIP(hipMemcpyAsync(cnt.data(), A.counters, 32, hipMemcpyDeviceToHost, st));
+    LFQ_TRY(S->down_t.end(st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    LFQ_TRY(bam_idx_add_ms(S->kern_t, &out->kernels_ms));
+    LFQ_TRY(bam_idx_add_ms(S->down_t, &out->download_ms));
+    const int64_t n_chunks = (int64_t)cnt[1], n_runs = (int64_t)cnt[2], n_intvs = (int64_t)cnt[3];
+    if (n_chunks > A.max_chunks || n_runs > A.max_runs || n_intvs > A.max_intvs) {
+        return LFQ_ERR_HIP;             /* (the kernels disagree with the record pass) */
+    }
+    const int64_t h_runs = lfq_al(n_chunks * (int64_t)sizeof(LfqBaiChunk)), h_intvs = h_runs + lfq_al(n_runs * (int64_t)sizeof(LfqBaiRun)),
+                  h_total = h_intvs + lfq_al(n_intvs * (int64_t)sizeof(LfqBaiIntv));
+    if (h_total > S->h_out_bytes) {
+        LFQ_TRY(grow_pinned(&S->h_out, &S->h_out_bytes, std::max<int64_t>(h_total + h_total / 4, 1 << 16)));
+    }
+    LFQ_TRY(S->down_t.begin(st));
+    if (n_chunks) {
+        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out, A.chunks, (size_t)n_chunks * sizeof(LfqBaiChunk), hipMemcpyDeviceToHost, st));
+    }
+    if (n_runs) {
+        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out + h_runs, A.runs, (size_t)n_runs * sizeof(LfqBaiRun), hipMemcpyDeviceToHost, st));
+    }
+    if (n_intvs) {
+        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out + h_intvs, A.intvs, (size_t)n_intvs * sizeof(LfqBaiIntv), hipMemcpyDeviceToHost, st));
+    }
+    LFQ_TRY(S->down_t.end(st));
+    LFQ_TRY_HIP(hipStreamSynchronize(st));
+    LFQ_TRY(bam_idx_add_ms(S->down_t, &out->download_ms));
+    out->chunks = (const LfqBaiChunk *)S->h_out;
+    out->runs = (const LfqBaiRun *)(S->h_out + h_runs);
+    out->intvs = (const LfqBaiIntv *)(S->h_out + h_intvs);
+    out->n_chunks = n_chunks;
+    out->n_runs = n_runs;
+    out->n_intvs = n_intvs;
+    return LFQ_OK;
+}
+
+lfq_vcf_index_times *lfq_bai_vcf_times(lfq_ctx *c) { return &bam_idx_state(c)->vcf_times; }
 
 extern "C" int lfq_bam_index_build(lfq_ctx *c, const uint8_t *body, int64_t n_bytes, const int64_t *rec_off, int64_t n_recs,
                                    const int64_t *data_off, const int64_t *comp_off, int64_t n_blocks, int64_t file_off, int32_t n_ref,
@@ -338,14 +432,9 @@ extern "C" int lfq_bam_index_build(lfq_ctx *c, const uint8_t *body, int64_t n_by
     if (!d_recs) {
         d_recs = lfq_bam_framed_resident(c, body + first, rec_bytes);
     }
-    const int64_t n_parts = (n_recs + LFQ_BAI_THREADS - 1) / LFQ_BAI_THREADS, max_runs = std::min<int64_t>(n_recs, n_ref);
-    const int64_t o_doff = lfq_al((n_recs + 1) * 8), o_coff = o_doff + lfq_al((n_blocks + 1) * 8), o_rec = o_coff + lfq_al((n_blocks + 1) * 8),
-                  o_part = o_rec + lfq_al(n_recs * (int64_t)sizeof(LfqBaiRec)), o_pre = o_part + lfq_al(n_parts * (int64_t)sizeof(LfqBaiPart)),
-                  o_cnt = o_pre + lfq_al(n_parts * (int64_t)sizeof(LfqBaiPart)), o_chunks = o_cnt + lfq_al(64),
-                  o_runs = o_chunks + lfq_al(n_recs * (int64_t)sizeof(LfqBaiChunk)),
-                  o_intvs = o_runs + lfq_al(max_runs * (int64_t)sizeof(LfqBaiRun)),
-                  total = o_intvs + lfq_al(n_recs * (int64_t)sizeof(LfqBaiIntv));
-    LFQ_TRY(grow(&S->d_buf, &S->d_bytes, total));
+    const int64_t o_doff = lfq_al((n_recs + 1) * 8), o_coff = o_doff + lfq_al((n_blocks + 1) * 8), o_rec = o_coff + lfq_al((n_blocks + 1) * 8);
+    LfqBaiDev dev;
+    LFQ_TRY(lfq_bai_reserve(c, o_rec, n_recs, std::min<int64_t>(n_recs, n_ref), &dev));
     const int64_t n_tab = (n_recs + 1) + 2 * (n_blocks + 1);
     LfqPin<int64_t> tab(c, (size_t)n_tab);
     LFQ_PIN_OK(tab);
@@ -376,30 +465,17 @@ extern "C" int lfq_bam_index_build(lfq_ctx *c, const uint8_t *body, int64_t n_by
     LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_doff, tab.data() + n_recs + 1, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st));
     LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_coff, tab.data() + n_recs + 1 + n_blocks + 1, (size_t)(n_blocks + 1) * 8,
                                hipMemcpyHostToDevice, st));
-    LFQ_TRY_HIP(hipMemcpyAsync(S->d_buf + o_cnt, cnt.data(), 32, hipMemcpyHostToDevice, st));
+    LFQ_TRY_HIP(hipMemcpyAsync(dev.counters, cnt.data(), 32, hipMemcpyHostToDevice, st));
     LFQ_TRY(S->up_t.end(st));
-    LfqBaiArgs A;
-    memset(&A, 0, sizeof(A));
+    LfqBaiArgs A = S->lay;
     A.body = d_recs - first;            /* (never read in front of rec_off[0]) */
     A.rec_off = (const int64_t *)S->d_buf;
     A.data_off = (const int64_t *)(S->d_buf + o_doff);
     A.comp_off = (const int64_t *)(S->d_buf + o_coff);
-    A.n_recs = n_recs;
     A.n_blocks = n_blocks;
     A.file_off = file_off;
     A.n_ref = n_ref;
-    A.rec = (LfqBaiRec *)(S->d_buf + o_rec);
-    A.part = (LfqBaiPart *)(S->d_buf + o_part);
-    A.pre = (LfqBaiPart *)(S->d_buf + o_pre);
-    A.n_parts = n_parts;
-    A.counters = (unsigned long long *)(S->d_buf + o_cnt);
-    A.chunks = (LfqBaiChunk *)(S->d_buf + o_chunks);
-    A.runs = (LfqBaiRun *)(S->d_buf + o_runs);
-    A.intvs = (LfqBaiIntv *)(S->d_buf + o_intvs);
-    A.max_chunks = n_recs;
-    A.max_runs = max_runs;
-    A.max_intvs = n_recs;
-    const dim3 grid((unsigned)n_parts), block(LFQ_BAI_THREADS);
+    const dim3 grid((unsigned)A.n_parts), block(LFQ_BAI_THREADS);
     LFQ_TRY(S->kern_t.begin(st));
     hipLaunchKernelGGL(lfq_bai_record_kernel, grid, block, 0, st, A);
     LFQ_TRY_HIP(hipGetLastError());
@@ -417,48 +493,16 @@ extern "C" int lfq_bam_index_build(lfq_ctx *c, const uint8_t *body, int64_t n_by
         S->times.first_bad_record = (int64_t)cnt[0];
         return LFQ_ERR_INVALID;
     }
-    LFQ_TRY(S->kern_t.begin(st));
-    hipLaunchKernelGGL(lfq_bai_part_kernel, grid, block, 0, st, A);
-    LFQ_TRY_HIP(hipGetLastError());
-    hipLaunchKernelGGL(lfq_bai_scan_kernel, dim3(1), dim3(64), 0, st, A);
-    LFQ_TRY_HIP(hipGetLastError());
-    hipLaunchKernelGGL(lfq_bai_emit_kernel, grid, block, 0, st, A);
-    LFQ_TRY_HIP(hipGetLastError());
-    LFQ_TRY(S->kern_t.end(st));
+    LfqBaiLists L;
+    LFQ_TRY(lfq_bai_compact(c, &L));
     S->times.n_launches = 4;
-    LFQ_TRY(S->down_t.begin(st));
-    LFQ_TRY_HIP(hipMemcpyAsync(cnt.data(), A.counters, 32, hipMemcpyDeviceToHost, st));
-    LFQ_TRY(S->down_t.end(st));
-    LFQ_TRY_HIP(hipStreamSynchronize(st));
-    LFQ_TRY(bam_idx_add_ms(S->kern_t, &S->times.kernels_ms));
-    LFQ_TRY(bam_idx_add_ms(S->down_t, &S->times.download_ms));
-    const int64_t n_chunks = (int64_t)cnt[1], n_runs = (int64_t)cnt[2], n_intvs = (int64_t)cnt[3];
-    if (n_chunks > A.max_chunks || n_runs > A.max_runs || n_intvs > A.max_intvs) {
-        return LFQ_ERR_HIP;             /* (the kernels disagree with the record pass) */
-    }
-    const int64_t h_runs = lfq_al(n_chunks * (int64_t)sizeof(LfqBaiChunk)), h_intvs = h_runs + lfq_al(n_runs * (int64_t)sizeof(LfqBaiRun)),
-                  h_total = h_intvs + lfq_al(n_intvs * (int64_t)sizeof(LfqBaiIntv));
-    if (h_total > S->h_out_bytes) {
-        LFQ_TRY(grow_pinned(&S->h_out, &S->h_out_bytes, std::max<int64_t>(h_total + h_total / 4, 1 << 16)));
-    }
-    LFQ_TRY(S->down_t.begin(st));
-    if (n_chunks) {
-        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out, A.chunks, (size_t)n_chunks * sizeof(LfqBaiChunk), hipMemcpyDeviceToHost, st));
-    }
-    if (n_runs) {
-        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out + h_runs, A.runs, (size_t)n_runs * sizeof(LfqBaiRun), hipMemcpyDeviceToHost, st));
-    }
-    if (n_intvs) {
-        LFQ_TRY_HIP(hipMemcpyAsync(S->h_out + h_intvs, A.intvs, (size_t)n_intvs * sizeof(LfqBaiIntv), hipMemcpyDeviceToHost, st));
-    }
-    LFQ_TRY(S->down_t.end(st));
-    LFQ_TRY_HIP(hipStreamSynchronize(st));
-    LFQ_TRY(bam_idx_add_ms(S->down_t, &S->times.download_ms));
+    S->times.kernels_ms += L.kernels_ms;
+    S->times.download_ms += L.download_ms;
+    const int64_t n_chunks = L.n_chunks, n_intvs = L.n_intvs;
     S->times.n_chunks = n_chunks;
     S->times.n_intervals = n_intvs;
     const auto t0 = std::chrono::steady_clock::now();
-    if (!lfq_bai_finish((const LfqBaiChunk *)S->h_out, n_chunks, (const LfqBaiRun *)(S->h_out + h_runs), n_runs,
-                        (const LfqBaiIntv *)(S->h_out + h_intvs), n_intvs, n_ref, n_recs, idx)) {
+    if (!lfq_bai_finish(L.chunks, n_chunks, L.runs, L.n_runs, L.intvs, n_intvs, n_ref, n_recs, idx)) {
         return LFQ_ERR_HIP;
     }
     S->times.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

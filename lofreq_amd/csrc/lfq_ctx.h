@@ -14,6 +14,7 @@
  *   lfq_bed.hip            the targets of `lofreq call -l`: the BED itself, lfq_set_bed, the read and column kernels (over lfq_bed.h)
  *   lfq_fasta.hip          `lofreq faidx` and the contig of a FASTA: scan, line and entry kernels, both fetch paths (over lfq_fasta.h)
  *   lfq_vcf.hip            VCF text parsed on the device and `lofreq vcfset`: scan, parse, runs, match, plan / copy (over lfq_vcf.h)
+ *   lfq_tbx.hip            the .tbi of a bgzipped VCF from an open file's table, and a region opened through one (over lfq_tbx.h)
  *   lfq_shard.hip      device choice of a worker, the exchange of a sharded run
  */
 #ifndef LFQ_CTX_H
@@ -609,11 +610,38 @@ const uint8_t *lfq_bgzf_resident_bytes(lfq_ctx *c, const uint8_t *p, int64_t byt
 const uint8_t *lfq_bam_framed_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 void lfq_bgzf_deflate_release(lfq_ctx *c);
 void lfq_bam_index_release(lfq_ctx *c);    /* lfq_bamidx.hip: what lfq_destroy frees of lfq_ctx::bamidx */
+/* lfq_bamidx.hip: the compaction its build shares with lfq_vcf_index_build (lfq_tbx.hip).  reserve lays out, in the context's grow-only
+ * buffer, head_bytes of the caller's own, n_recs LfqBaiRec and the compaction's lists; the caller's record pass fills rec[] and sets
+ * counters[0 .. 4) (0: its own word, 1 .. 3: zero); compact launches the part / scan / emit kernels on the context's stream and brings
+ * chunks, runs and intervals to pinned host memory, valid until the context's next reserve.  lfq_bai_vcf_times: where
+ * lfq_last_vcf_index_times reads, freed with the rest of lfq_ctx::bamidx */
+struct LfqBaiRec;
+struct LfqBaiChunk;
+struct LfqBaiRun;
+struct LfqBaiIntv;
+struct LfqBaiDev {
+    uint8_t *head;
+    LfqBaiRec *rec;
+    unsigned long long *counters;
+};
+struct LfqBaiLists {
+    const LfqBaiChunk *chunks;
+    const LfqBaiRun *runs;
+    const LfqBaiIntv *intvs;
+    int64_t n_chunks, n_runs, n_intvs;
+    double kernels_ms, download_ms;
+};
+int lfq_bai_reserve(lfq_ctx *c, int64_t head_bytes, int64_t n_recs, int64_t max_runs, LfqBaiDev *out);
+int lfq_bai_compact(lfq_ctx *c, LfqBaiLists *out);
+lfq_vcf_index_times *lfq_bai_vcf_times(lfq_ctx *c);
 /* lfq_fasta.hip.  What lfq_destroy frees of lfq_ctx::fasta; and for the read set's contig upload (lfq_readset.hip): the device address
  * of host bytes [p, p + bytes) when they lie inside the context's live lfq_fasta_fetch result (counted as a hand-over), else null */
 void lfq_fasta_release(lfq_ctx *c);
 const uint8_t *lfq_fasta_resident(lfq_ctx *c, const uint8_t *p, int64_t bytes);
 void lfq_vcf_release(lfq_ctx *c);          /* lfq_vcf.hip: what lfq_destroy frees of lfq_ctx::vcf */
+/* lfq_vcf.hip, for lfq_tbx.hip: an open file's context, mode, table on the device and run names */
+struct LfqVcTab;
+void lfq_vcf_view(const lfq_vcf *v, lfq_ctx **c, int *mode, LfqVcTab *T, const std::vector<std::string> **names);
 /* lfq_bed.hip, for the read set (lfq_readset.hip).  keep_out[r] = 1 iff [pos, bam_endpos) of read r overlaps an interval, one lane
  * per read, from the resident start positions and CIGAR words; cov[p] (and nb[p], unless null) of every position of
  * [begin, begin + width) whose [p, p + 1) overlaps none go to 0, one lane per position: no column for the compaction behind it */

@@ -498,6 +498,14 @@ void lfq_vcf_release(lfq_ctx *c)
     }
 }
 
+void lfq_vcf_view(const lfq_vcf *v, lfq_ctx **c, int *mode, LfqVcTab *T, const std::vector<std::string> **names)
+{
+    *c = v->c;
+    *mode = v->mode;
+    *T = v->D.T;
+    *names = &v->run_name;
+}
+
 static inline unsigned vc_grid(int64_t n) { return (unsigned)((std::max<int64_t>(n, 1) + 255) / 256); }
 static bool vc_launched() { return hipGetLastError() == hipSuccess; }
 
